@@ -12,7 +12,13 @@ on a side stream while frame i + 1 renders (double-buffered frames).
 itself (torch.distributed.run, 127.0.0.1) before anything touches a GPU, and fails when fewer than
 N GPUs are visible; under a launcher (WORLD_SIZE set) it is one rank.
 
-Prints ONE JSON line on rank 0 (see the repo contract), with
+A plain run does what the headline figure needs and no more: set-up, warm-up, the timed steps, the
+outputs when `--dump-outputs DIR` asks for them (DIR/frame.npy: the frame the last timed step
+assembled, float64; the inputs are seeded, so two builds compare output for output), and ONE JSON
+line on rank 0 (see the repo contract): metric, value, unit, ms_per_step (wall milliseconds per
+timed step), dtype, the workload. `--full` adds everything else to that line, each from work of its
+own after the timed steps: the frame self-check (`frame_check`), the two instrumented passes
+(per-phase shares, lane utilization, the algorithmic-byte basis), the dielectric guard count, and
   roofline:     the resource that binds the render kernel. The scene is LDS/L2-resident and the
                 kernel moves ~7 GB per launch to/from HBM (~1% of peak), so the bound is VALU
                 issue: bound "valu", frac = the share of SIMD cycles the VALU issue port is busy
@@ -160,7 +166,13 @@ def parse():
                     help="spp of the secondary, oversubscribed one-run figure (every affinity CPU a thread); 0 = skip")
     ap.add_argument("--launch-check", action="store_true",
                     help="ranks only join the process group and report (tests the N-rank launch on CPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the frame self-check, the instrumented passes, the "
+                         "roofline figures and the CPU baseline, and add them to the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 saves the frame the last timed step assembled to DIR/frame.npy (float64; a "
+                         "fixed seeded sample of its values when the frame exceeds 32 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--dump-frame", default="", help="save every rank's last assembled frame to PATH.rank<r>.npy")
     ap.add_argument("--pmc-json", default=str(ROOT / "profiles" / "pmc_latest.json"))
     return ap.parse_args()
@@ -310,7 +322,7 @@ def main() -> int:
     import torch.distributed as dist
     import cpp_raytracer_amd as crt
     from cpp_raytracer_amd import Tiling, camera_with
-    from cpp_raytracer_amd.tiles import TileGather, digests_agree, frame_digest, owned_rows
+    from cpp_raytracer_amd.tiles import TileGather, owned_rows
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -410,11 +422,77 @@ def main() -> int:
     if args.dump_frame:  # every rank's last assembled frame (tests: equal to the 1-rank frame)
         import numpy as np
         np.save(f"{args.dump_frame}.rank{rank}.npy", assembled[0].cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), assembled[0])
+    if distributed:
+        t = torch.tensor([elapsed, kernel_ms], dtype=torch.float64, device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed, kernel_ms = float(t[0]), float(t[1])
+    samples_total = h * w * args.spp * args.steps
+    ms_per_step = elapsed * 1e3 / max(1, args.steps)
+    workload = f"{args.scene} seed {args.seed}, {w}x{h}, {args.spp} spp, max_depth {args.depth}"
+    if (args.scene, w, h, args.spp, args.depth) == ("rtow_final", 1200, 800, 500, 50):
+        workload += " (BASELINE config 2)"
+    out = {
+        "metric": "Msamples/sec + achieved HBM GB/s, RTOW final scene at 1/2/4/8 MI355X",
+        "value": round(samples_total / elapsed / 1e6, 3),
+        "unit": "Msamples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": SCENE_DATA.get(args.scene, f"synthetic: {args.scene} scene of the reference's src/main.cpp"),
+        "config": {"workload": workload,
+                   "samples_per_step": h * w * args.spp, "primitives": int(info.num_primitives),
+                   "bvh_nodes": int(info.num_nodes), "scene_setup_ms": round(setup_ms, 1), "partition": f"{rb}-row blocks over {world} ranks, "
+                   "RCCL all-gather of tiles overlapped with the next frame" if distributed else "whole frame on one GPU",
+                   "process_group": {"backend": dist.get_backend() if distributed else None,
+                                     "world_size": dist.get_world_size() if distributed else 1,
+                                     "visible_gpus": torch.cuda.device_count()}},
+    }
+    if args.full:  # every rank takes part (collectives); rank 0 gets the fields
+        extra = full_report(args, scene, data, cam, tiling, assembled[0], kernel_ms, len(owned), workload,
+                            world, rank, local, log)
+        if rank == 0:
+            out.update(extra)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if distributed:
+        dist.destroy_process_group()
+    return 0
+
+
+def dump_outputs(folder: Path, frame) -> None:
+    """--dump-outputs: what a caller of the timed path receives from its last step, the assembled
+    h x w x 3 float64 frame, as <folder>/frame.npy. A frame above 32 MB is saved as a sample of its
+    values at positions drawn once from a fixed seed (the same positions in every run and build)."""
+    import numpy as np
+    a = frame.cpu().numpy()
+    limit = 4 << 20  # values: 32 MB of float64
+    if a.size > limit:
+        a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, limit, replace=False))]
+    folder.mkdir(parents=True, exist_ok=True)
+    np.save(folder / "frame.npy", np.ascontiguousarray(a, dtype=np.float64))
+
+
+def full_report(args, scene, data, cam, tiling, frame, kernel_ms, rows_owned, workload, world, rank, local, log):
+    """--full: what the line reports beyond the headline figure, each from work of its own after
+    the timed steps (frame self-check, instrumented passes, roofline, guard count, CPU baseline).
+    Every rank calls it (the checks gather over the process group); rank 0 gets the fields."""
+    import torch
+    import torch.distributed as dist
+    from cpp_raytracer_amd.tiles import digests_agree, frame_digest
+    distributed = world > 1
+    w = args.width
     # self-check of the assembled frame (untimed): every rank hashes the frame it holds, the digests
     # are all-gathered, and rank 0 compares them with each other and with the recorded N=1 digest
     # of this workload (frames are bit-identical for any rank count). CRT_BENCH_CORRUPT_RANK=k
     # (tests only) flips one value of rank k's frame first, which must flip ranks_agree.
-    final = assembled[0]
+    final = frame
     if os.environ.get("CRT_BENCH_CORRUPT_RANK", "") == str(rank):
         final = final.clone()
         final.view(-1)[final.numel() // 2] += 1.0
@@ -423,12 +501,6 @@ def main() -> int:
         agree, rank_digests = digests_agree(digest, "cuda" if dist.get_backend() == "nccl" else "cpu")
     else:
         agree, rank_digests = True, [digest]
-    if distributed:
-        t = torch.tensor([elapsed, kernel_ms], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, kernel_ms = float(t[0]), float(t[1])
-    samples_total = h * w * args.spp * args.steps
-    ms_per_step = elapsed * 1e3 / max(1, args.steps)
 
     # algorithmic bytes of one launch (this rank's tile), from the instrumented pass (untimed),
     # which walks like the reference (its node counts are the byte basis); a second instrumented
@@ -441,13 +513,10 @@ def main() -> int:
     finally:
         del os.environ["CRT_COUNT_SPEC"]
     alg_bytes = (cnt.nodes_visited * NODE_B + cnt.sphere_tests * SPHERE_B + cnt.parallelogram_tests * QUAD_B
-                 + len(owned) * w * PIXEL_B)
+                 + rows_owned * w * PIXEL_B)
     rays_per_sample = cnt.rays / max(1, cnt.samples)
     flops = cnt.nodes_visited * 12 + cnt.sphere_tests * 23 + cnt.parallelogram_tests * 40 + cnt.rays * 50
     achieved_gbs = alg_bytes / (kernel_ms * 1e-3) / 1e9
-    workload = f"{args.scene} seed {args.seed}, {w}x{h}, {args.spp} spp, max_depth {args.depth}"
-    if (args.scene, w, h, args.spp, args.depth) == ("rtow_final", 1200, 800, 500, 50):
-        workload += " (BASELINE config 2)"
     # counters of the timed kernel from the rocprofv3 PMC passes (tools/gpu_pmc.sh +
     # tools/pmc_summary.py) of this workload on this exact build
     pmc_data, pmc_src = None, None
@@ -521,25 +590,6 @@ def main() -> int:
     if rank == 0:
         cpu = None if args.no_cpu_baseline else cpu_baseline(args, data, log)
         out = {
-            "metric": "Msamples/sec + achieved HBM GB/s, RTOW final scene at 1/2/4/8 MI355X",
-            "value": round(samples_total / elapsed / 1e6, 3),
-            "unit": "Msamples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": SCENE_DATA.get(args.scene, f"synthetic: {args.scene} scene of the reference's src/main.cpp"),
-            "config": {"workload": workload,
-                       "samples_per_step": h * w * args.spp, "primitives": int(info.num_primitives),
-                       "bvh_nodes": int(info.num_nodes), "scene_setup_ms": round(setup_ms, 1), "partition": f"{rb}-row blocks over {world} ranks, "
-                       "RCCL all-gather of tiles overlapped with the next frame" if distributed else "whole frame on one GPU",
-                       "process_group": {"backend": dist.get_backend() if distributed else None,
-                                         "world_size": dist.get_world_size() if distributed else 1,
-                                         "visible_gpus": torch.cuda.device_count()}},
             "roofline": roofline,
             "fp64": {"achieved_tflops": round(flops / (kernel_ms * 1e-3) / 1e12, 3),
                      "peak_tflops": FP64_VECTOR_PEAK_TFLOPS, "rays_per_sample": round(rays_per_sample, 4),
@@ -575,10 +625,8 @@ def main() -> int:
             "cpu_baseline": cpu,
             "frame_check": frame_check(workload, args.base_seed, digest, agree, rank_digests, world),
         }
-        print(json.dumps(out), flush=True)
-    if distributed:
-        dist.destroy_process_group()
-    return 0
+        return out
+    return None
 
 
 if __name__ == "__main__":

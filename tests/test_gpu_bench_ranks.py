@@ -15,7 +15,8 @@ import pytest
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
-ARGS = ["--width", "160", "--height", "98", "--spp", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+TINY = ["--width", "160", "--height", "98", "--spp", "8", "--steps", "2", "--warmup", "1"]
+ARGS = [*TINY, "--full", "--no-cpu-baseline"]  # frame_check is part of the --full line
 
 
 def _env():
@@ -60,6 +61,24 @@ def test_bench_ranks_assemble_the_one_rank_frame(tmp_path, ranks):
     assert fc1["ranks_agree"] is True
     assert fc["ranks_agree"] is True and fc["frame_digest"] == fc1["frame_digest"]
     assert fc["rank_digests"] == [fc1["frame_digest"]] * ranks
+
+
+def test_plain_run_reports_the_headline_only_and_dumps_its_frame(tmp_path):
+    """Without --full the line holds the headline figure and the workload, none of the figures
+    that take work of their own; --dump-outputs saves the last timed frame, equal to --dump-frame's."""
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", *TINY, "--dump-outputs", str(out),
+                        "--dump-frame", str(tmp_path / "f")], capture_output=True, text=True, timeout=600, env=_env())
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"} <= set(line)
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(160 * 98 * 8 / (line["ms_per_step"] * 1e-3) / 1e6, rel=5e-2)  # both rounded to 3 decimals
+    assert not {"cpu_baseline", "roofline", "frame_check", "instrumented_counts", "schlick_guard"} & set(line)
+    assert [p.name for p in out.iterdir()] == ["frame.npy"]
+    frame = np.load(out / "frame.npy")
+    assert frame.dtype == np.float64 and frame.shape == (98, 160, 3)
+    assert np.array_equal(frame, np.load(f"{tmp_path / 'f'}.rank0.npy"))
 
 
 def test_bench_frame_check_flags_a_rank_that_differs():

@@ -48,7 +48,7 @@ for r in $(seq ${REPS:-1}); do
         *:*) n=${v%%:*}; IFS=, read -ra envs <<< "${v#*:}" ;;
       esac
       tag=c${c}_${n}_r$r
-      env "${envs[@]}" timeout -k 10 900 python bench.py --steps $steps --warmup 1 --no-cpu-baseline $args \
+      env "${envs[@]}" timeout -k 10 900 python bench.py --steps $steps --warmup 1 --full --no-cpu-baseline $args \
         > gpurun_out/bench_$tag.json 2> gpurun_out/bench_$tag.err || { echo "bench $tag FAILED"; tail -5 gpurun_out/bench_$tag.err; exit 1; }
       python -c "import json; j=json.load(open('gpurun_out/bench_$tag.json')); print('$tag', j['value'], 'Msamples/s', j['ms_per_step'], 'ms', j['roofline']['kernel_ms'], 'kernel ms')"
     done

@@ -19,7 +19,7 @@ for c in $CFGS; do
     5) a="--scene rtow_final --seed 42 --width 3840 --height 2160 --spp 10000 --depth 50" ;;
   esac
   steps=3; [ "$c" = 5 ] && steps=1
-  timeout -k 10 600 python bench.py --steps $steps --warmup 1 --no-cpu-baseline $a > "$OUT/bench_c$c.json" 2> "$OUT/bench_c$c.err" \
+  timeout -k 10 600 python bench.py --steps $steps --warmup 1 --full --no-cpu-baseline $a > "$OUT/bench_c$c.json" 2> "$OUT/bench_c$c.err" \
     || { echo "bench c$c FAILED"; tail -5 "$OUT/bench_c$c.err"; exit 1; }
   python -c "import json; j=json.load(open('$OUT/bench_c$c.json')); print('c$c', j['ms_per_step'], 'ms', j['roofline']['kernel_ms'], 'kernel ms', j['frame_check']['frame_digest'], j['config']['workload'])"
 done

@@ -25,8 +25,9 @@ print(('pmc: library ' if ok else 'pmc: REFUSED, library ') + st['build_info'] +
 sys.exit(0 if ok else 3)") || exit 3
 export TMPDIR=/tmp
 cd /tmp
-[ -s "$R/gpurun_out/counters_list.txt" ] || timeout -k 10 120 rocprofv3 -L > "$R/gpurun_out/counters_list.txt" 2>&1
-have() { grep -qw "$1" "$R/gpurun_out/counters_list.txt"; }
+LIST=$(dirname "$OUT")/counters_list.txt  # the device's counter list, kept beside the pass folders
+[ -s "$LIST" ] || timeout -k 10 120 rocprofv3 -L > "$LIST" 2>&1
+have() { grep -qw "$1" "$LIST"; }
 pick() { local out=""; for c in "$@"; do have "${c%_sum}" && out="$out $c"; done; echo $out; }
 P1=$(pick FETCH_SIZE GRBM_GUI_ACTIVE)
 P2=$(pick WRITE_SIZE TCC_HIT_sum TCC_MISS_sum)

@@ -14,7 +14,8 @@ Classes: f64, f32 (arith and transcendental), pk_f32, int (add/sub/mul/mad/cvt/m
 min/max/med3, bit/shift (and/or/xor/bfe/lshl/lshr/bitop3/perm), mov/lane (mov, readlane, writelane).
 The SQ_INSTS_VALU_* hardware classes count f32 / f64 add, mul, fma, trans, INT32, INT64, CVT; the rest
 (cmp/cndmask, min/max, bit ops, movs, packed f32) is the counters' unclassified "other".
-usage: python tools/valu_attribution.py listing.s kernel_substring bench.json [pmc.json]"""
+usage: python tools/valu_attribution.py listing.s kernel_substring bench.json [pmc.json]
+(bench.json: the line of a `bench.py --full` run)"""
 import collections
 import json
 import re
