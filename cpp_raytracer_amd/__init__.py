@@ -24,6 +24,7 @@ from ._capi import (CRT_BOX, CRT_DIELECTRIC, CRT_DIFFUSE_LIGHT, CRT_LAMBERTIAN, 
 __all__ = [
     "SceneData", "GpuScene", "CameraSettings", "Camera", "Tiling", "RenderStats", "CrtError",
     "resolve_camera", "sample_seed", "rand_double", "device_count", "lib", "ppm_values", "write_ppm",
+    "sample_chunk_len", "noise_estimate",
     "CRT_LAMBERTIAN", "CRT_METAL", "CRT_DIELECTRIC", "CRT_DIFFUSE_LIGHT",
     "CRT_SPHERE", "CRT_PARALLELOGRAM", "CRT_BOX",
 ]
@@ -41,6 +42,23 @@ def rand_double(state: int, lo: float = 0.0, hi: float = 1.0) -> tuple[int, floa
     s = C.c_uint32(state & 0xFFFFFFFF)
     v = lib().crt_rand_double(C.byref(s), lo, hi)
     return s.value, v
+
+
+def sample_chunk_len(spp: int) -> int:
+    """Samples per chunk of an spp-sample render (crt_sample_chunk_len): the boundaries of
+    progressive passes are multiples of it."""
+    return int(lib().crt_sample_chunk_len(spp & 0xFFFFFFFF))
+
+
+def noise_estimate(device: int, noise_ptr: int, pixels: int, spp: int, samples_done: int,
+                   stream: int = 0) -> tuple[float, float]:
+    """(sum of the pixels' standard errors, sum of their means) from the noise state a progressive
+    render keeps (crt_noise_estimate); their ratio is the frame's relative noise. NaN before two
+    chunks are done."""
+    se, mean = C.c_double(0), C.c_double(0)
+    check(lib().crt_noise_estimate(device, C.c_void_p(noise_ptr), pixels, spp, samples_done,
+                                   C.byref(se), C.byref(mean), C.c_void_p(stream)), "crt_noise_estimate")
+    return se.value, mean.value
 
 
 def device_count() -> int:
@@ -201,6 +219,45 @@ class GpuScene:
         t = C.byref(tiling) if tiling is not None else None
         check(lib().crt_render_async(self._h, device, C.byref(cam), t, C.c_void_p(out_ptr),
                                      C.c_void_p(stream)), "crt_render_async")
+
+    def render_pass(self, device: int, cam: Camera, first: int, count: int, sum_ptr: int,
+                    noise_ptr: int = 0, out_ptr: int = 0, stream: int = 0,
+                    tiling: Optional[Tiling] = None) -> None:
+        """Enqueue samples [first, first + count) of a cam.samples_per_pixel job into the running
+        sums at sum_ptr (crt_render_pass_async; boundaries are multiples of sample_chunk_len).
+        noise_ptr: 2 doubles a pixel of noise state; out_ptr: the frame so far. 0 = not wanted."""
+        t = C.byref(tiling) if tiling is not None else None
+        check(lib().crt_render_pass_async(self._h, device, C.byref(cam), t, first, count,
+                                          C.c_void_p(sum_ptr), C.c_void_p(noise_ptr or None),
+                                          C.c_void_p(out_ptr or None), C.c_void_p(stream)),
+              "crt_render_pass_async")
+
+    def render_progressive(self, cam: Camera, samples_per_pass: int = 0, callback=None, num_devices: int = 1,
+                           preview: bool = False, noise: bool = False) -> tuple[np.ndarray, int]:
+        """Blocking whole-frame render in passes (crt_render_progressive). After every pass
+        callback(samples_done, samples_total, noise, frame) is called: noise is the frame's
+        relative noise with noise=True (else NaN), frame the (h, w, 3) picture so far with
+        preview=True (else None; a view of the returned array: copy it to keep it). A true return
+        stops the render. Returns (frame, samples_done): the mean of the samples rendered."""
+        out = np.empty((cam.image_h, cam.image_w, 3), np.float64)
+        raised = []
+
+        def trampoline(_user, done, total, figure, h_rgb):
+            try:
+                return 1 if callback(done, total, figure, out if h_rgb else None) else 0
+            except BaseException as e:  # not through the C frames: stop, raise after the call
+                raised.append(e)
+                return 1
+
+        fn = _capi.PROGRESS_FN(trampoline) if callback is not None else _capi.PROGRESS_FN()
+        flags = (_capi.CRT_PROGRESS_NOISE if noise else 0) | (_capi.CRT_PROGRESS_PREVIEW if preview else 0)
+        done = C.c_uint32(0)
+        rc = lib().crt_render_progressive(self._h, C.byref(cam), num_devices, samples_per_pass, flags, fn,
+                                          None, out.ctypes.data, C.byref(done))
+        if raised:
+            raise raised[0]
+        check(rc, "crt_render_progressive")
+        return out, int(done.value)
 
     def render_count(self, device: int, cam: Camera, tiling: Optional[Tiling] = None) -> RenderStats:
         st = RenderStats()

@@ -100,6 +100,9 @@ assert NODE_DTYPE.itemsize == C.sizeof(BVHNode) == 64
 assert HIT_DTYPE.itemsize == C.sizeof(Hit)
 
 P = C.POINTER
+# crt_progress_fn(user, samples_done, samples_total, noise, h_rgb) -> non-zero stops the render
+CRT_PROGRESS_NOISE, CRT_PROGRESS_PREVIEW = 1, 2
+PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.c_void_p)
 EXPORTS = {
     "crt_abi_version": (C.c_int, []),
     "crt_last_error": (C.c_char_p, []),
@@ -119,6 +122,13 @@ EXPORTS = {
     "crt_scene_destroy": (None, [C.c_void_p]),
     "crt_camera_resolve": (C.c_int, [P(CameraSettings), P(Camera)]),
     "crt_render_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Tiling), C.c_void_p, C.c_void_p]),
+    "crt_sample_chunk_len": (C.c_uint32, [C.c_uint32]),
+    "crt_render_pass_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Tiling), C.c_uint32, C.c_uint32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "crt_noise_estimate": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                     P(C.c_double), P(C.c_double), C.c_void_p]),
+    "crt_render_progressive": (C.c_int, [C.c_void_p, P(Camera), C.c_int, C.c_uint32, C.c_uint32, PROGRESS_FN,
+                                         C.c_void_p, C.c_void_p, P(C.c_uint32)]),
     "crt_render_count": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Tiling), P(RenderStats)]),
     "crt_render": (C.c_int, [C.c_void_p, P(Camera), C.c_int, C.c_void_p, P(RenderStats)]),
     "crt_render_ppm": (C.c_int, [C.c_void_p, P(Camera), C.c_int, C.c_void_p, P(RenderStats)]),

@@ -103,7 +103,11 @@ struct Work {
     // stay within the partial-sum budget)
     uint32_t col0, k0, bw, bh;
     uint32_t tiles_x, tiles_y, tiles;
-    uint32_t chunks, chunk_len;        // sample chunks per pixel
+    uint32_t chunks, chunk_len;        // sample chunks per pixel in this launch
+    // first sample of the launch (a multiple of chunk_len; 0 for a one-shot render): chunk c of
+    // the launch holds samples [s0 + c * chunk_len, min(spp, s0 + (c + 1) * chunk_len)), which is
+    // chunk s0 / chunk_len + c of the whole job (crt_render_pass_async)
+    uint32_t s0;
     // work queue, taken in order by the waves of a persistent grid (render_kernel): bulk items
     // (tile i / groups, chunks [(i % groups) * item_chunks, + item_chunks)), then tail items
     // (tile j / tail_chunks, chunk bulk_chunks + j % tail_chunks); 64 units per chunk
@@ -1962,7 +1966,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kMa
                 // band-local column and owned row
                 const uint32_t col = (item_txy & 0xffffu) * kTileW + pix % kTileW, k = (item_txy >> 16) * kTileH + pix / kTileW;
                 if (chunk < W.chunks && col < W.bw && k < W.bh) {
-                    s = chunk * W.chunk_len;
+                    s = W.s0 + chunk * W.chunk_len;
                     if (C.max_depth > 0) {
                         need = false;
                         start = true;
@@ -2083,7 +2087,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kMa
                 cont = true;  // the scattered ray: traversal set-up with the new samples' (above)
             } else {
                 const uint32_t chunk = u_cp >> 6;
-                if (++s < min(C.spp, (chunk + 1) * W.chunk_len)) {
+                if (++s < min(C.spp, W.s0 + (chunk + 1) * W.chunk_len)) {
                     start = true;  // the unit's next sample (started after the draw, with the drawers)
                 } else {  // the unit is done: its sum (samples in order) to partial[chunk][pixel]
                     if (!COUNT) {
@@ -2146,6 +2150,134 @@ __global__ __launch_bounds__(256) void resolve_kernel(const double* __restrict__
     out[pix * 3 + 0] = r * inv_spp;
     out[pix * 3 + 1] = g * inv_spp;
     out[pix * 3 + 2] = b * inv_spp;
+}
+
+// resolve_kernel for one pass of a progressive render (crt_render_pass_async): the pass's chunk
+// sums are added in chunk order to the pixel's running sum in `sum` (the layout of the frame), with
+// resolve_kernel's own additions: a pass from sample 0 starts from partial[0], a later one from the
+// stored sum, so passes issued in order add exactly what the one-shot resolve adds. out (may be
+// null) receives sum * inv_done, inv_done = 1 / (double)(samples done after this pass): the frame
+// so far, and after the last pass resolve_kernel's frame.
+// noise (may be null; 2 doubles a pixel, the frame's pixel addressing): t += y and q += y * y over
+// the pass's first full_chunks chunks, y = (r + g) + b of the chunk's sum. The ragged last chunk of
+// a job has fewer samples, so its sum is not distributed like the others, and is left out.
+__global__ __launch_bounds__(256) void accumulate_kernel(const double* __restrict__ partial,
+                                                         double* __restrict__ sum, double* __restrict__ noise,
+                                                         double* __restrict__ out, Work W, uint32_t w,
+                                                         uint32_t full_chunks, double inv_done) {
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+    const uint64_t band = static_cast<uint64_t>(W.bh) * W.bw;
+    if (i >= band) return;
+    const uint32_t k = W.k0 + static_cast<uint32_t>(i / W.bw), col = W.col0 + static_cast<uint32_t>(i % W.bw);
+    const size_t pix = static_cast<size_t>(W.packed ? k : owned_row(W, k)) * w + col;
+    const size_t plane = band * 3;
+    const bool fresh = W.s0 == 0;
+    double r, g, b;
+    if (fresh) {
+        r = partial[i * 3 + 0];
+        g = partial[i * 3 + 1];
+        b = partial[i * 3 + 2];
+    } else {
+        r = sum[pix * 3 + 0];
+        g = sum[pix * 3 + 1];
+        b = sum[pix * 3 + 2];
+    }
+    double t = 0, q = 0;
+    if (noise && !fresh) {
+        t = noise[pix * 2 + 0];
+        q = noise[pix * 2 + 1];
+    }
+    for (uint32_t c = 0; c < W.chunks; ++c) {
+        const double pr = partial[c * plane + i * 3 + 0], pg = partial[c * plane + i * 3 + 1],
+                     pb = partial[c * plane + i * 3 + 2];
+        if (c > 0 || !fresh) {
+            r = r + pr;
+            g = g + pg;
+            b = b + pb;
+        }
+        if (c < full_chunks) {
+            const double y = (pr + pg) + pb;
+            t = t + y;
+            q = q + y * y;
+        }
+    }
+    sum[pix * 3 + 0] = r;
+    sum[pix * 3 + 1] = g;
+    sum[pix * 3 + 2] = b;
+    if (noise) {
+        noise[pix * 2 + 0] = t;
+        noise[pix * 2 + 1] = q;
+    }
+    if (out) {
+        out[pix * 3 + 0] = r * inv_done;
+        out[pix * 3 + 1] = g * inv_done;
+        out[pix * 3 + 2] = b * inv_done;
+    }
+}
+
+// out[i] = sum[i] * inv_done over n doubles: the frame of a progressive render that stops between
+// previews (crt_render_progressive), accumulate_kernel's last step on its own.
+__global__ __launch_bounds__(256) void scale_kernel(const double* __restrict__ sum, double* __restrict__ out,
+                                                    uint64_t n, double inv_done) {
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i < n) out[i] = sum[i] * inv_done;
+}
+
+// Noise figure of a progressive render (crt_noise_estimate). A pixel's K full chunk sums y_c (L
+// samples each) are independent, identically distributed estimates of L times the pixel's value
+// v = r + g + b; accumulate_kernel keeps t = sum y_c and q = sum y_c^2. Then m = t / (K L)
+// estimates v, and the standard error of m is se = sqrt(max(0, q / L^2 - K m^2) / (K (K - 1))):
+// the sample variance of y_c / L over K. The kernels return sum se and sum m over the pixels in
+// two stages, both fixed trees (no atomics): stage 1, kNoiseBlocks blocks, thread j of block b
+// sums pixels b * 256 + j, + kNoiseBlocks * 256, ... in order, then the block halves its 256
+// values in LDS eight times; stage 2, one block does the same over the block results. The order of
+// every addition depends on the pixel count only, so repeated calls give the same bits.
+constexpr uint32_t kNoiseBlocks = 256;
+
+__device__ __forceinline__ void noise_tree(double (*sh)[256], double& a, double& b) {
+    sh[0][threadIdx.x] = a;
+    sh[1][threadIdx.x] = b;
+    __syncthreads();
+    for (uint32_t h = 128; h > 0; h >>= 1) {
+        if (threadIdx.x < h) {
+            sh[0][threadIdx.x] = sh[0][threadIdx.x] + sh[0][threadIdx.x + h];
+            sh[1][threadIdx.x] = sh[1][threadIdx.x] + sh[1][threadIdx.x + h];
+        }
+        __syncthreads();
+    }
+    a = sh[0][0];
+    b = sh[1][0];
+}
+
+__global__ __launch_bounds__(256) void noise_stage1_kernel(const double* __restrict__ noise, uint64_t pixels,
+                                                           double K, double L, double* __restrict__ block_sums) {
+    __shared__ double sh[2][256];
+    double se = 0, mean = 0;
+    for (uint64_t p = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x; p < pixels;
+         p += static_cast<uint64_t>(kNoiseBlocks) * 256) {
+        const double t = noise[p * 2 + 0], q = noise[p * 2 + 1];
+        const double m = t / (K * L);
+        const double var = q / (L * L) - K * m * m;
+        se = se + sqrt(fmax(0.0, var) / (K * (K - 1)));
+        mean = mean + m;
+    }
+    noise_tree(sh, se, mean);
+    if (threadIdx.x == 0) {
+        block_sums[blockIdx.x * 2 + 0] = se;
+        block_sums[blockIdx.x * 2 + 1] = mean;
+    }
+}
+
+__global__ __launch_bounds__(256) void noise_stage2_kernel(const double* __restrict__ block_sums,
+                                                           double* __restrict__ out) {
+    __shared__ double sh[2][256];
+    static_assert(kNoiseBlocks == 256, "stage 2 reads one block result per thread");
+    double se = block_sums[threadIdx.x * 2 + 0], mean = block_sums[threadIdx.x * 2 + 1];
+    noise_tree(sh, se, mean);
+    if (threadIdx.x == 0) {
+        out[0] = se;
+        out[1] = mean;
+    }
 }
 
 // Image::send_as_ppm's integers (image.h:38-56; RGB::as_string rgb.h:99-115 with its defaults):
@@ -2545,9 +2677,18 @@ static size_t partial_budget() {
     return size_t{4} << 30;
 }
 
+// Samples per chunk: a function of spp only (launch_render; crt_sample_chunk_len)
+#ifndef CRT_CHUNK_MIN
+#define CRT_CHUNK_MIN 4
+#endif
+uint32_t sample_chunk_len(uint32_t spp) {
+    return std::max<uint32_t>(CRT_CHUNK_MIN, (spp + 191) / 192);
+}
+
 template <typename SE, bool GSTACK, bool LSCENE, int PM, bool W5 = false>
 static int launch_render(const crt_scene* s, int device, const crt_camera* cam, const dev::Work& w0,
-                         size_t lds, double* d_rgb, hipStream_t stream, crt_render_stats* count_stats) {
+                         size_t lds, double* d_rgb, hipStream_t stream, crt_render_stats* count_stats,
+                         const RenderPass* pass) {
     const DeviceCopy& c = s->dev[device];
     dev::Work W = w0;
     W.lds_cam = static_cast<uint32_t>(align16(lds));  // the camera copy after the rest
@@ -2570,11 +2711,20 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
     // the partial sums double to 2.9 GB per config-2 frame). The persistent grid's waves take
     // (tile, chunk) items from a queue in tile-major order (render_kernel).
     const uint32_t spp = cam->samples_per_pixel;
-#ifndef CRT_CHUNK_MIN
-#define CRT_CHUNK_MIN 4
-#endif
-    W.chunk_len = std::max<uint32_t>(CRT_CHUNK_MIN, (spp + 191) / 192);
+    W.chunk_len = sample_chunk_len(spp);
     W.chunks = (spp + W.chunk_len - 1) / W.chunk_len;
+    // A pass of a progressive render launches its own chunks only (chunk s0 / chunk_len onwards,
+    // numbered from 0 in the launch and in `partial`), so its bands are sized by the pass; the
+    // chunks that hold chunk_len samples (all but a job's ragged last one) feed the noise state.
+    uint32_t full_chunks = 0;
+    double inv_done = 0;
+    if (pass) {
+        const uint32_t end = pass->first + pass->count;
+        W.s0 = pass->first;
+        W.chunks = (end + W.chunk_len - 1) / W.chunk_len - pass->first / W.chunk_len;
+        full_chunks = end / W.chunk_len - pass->first / W.chunk_len;
+        inv_done = 1 / static_cast<double>(end);
+    }
     W.rb_shift = 32;
     for (uint32_t sh = 0; sh < 31; ++sh)
         if ((1u << sh) == W.row_block) W.rb_shift = sh;
@@ -2687,8 +2837,12 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
                                    dim3(dev::kBlock), lds, stream, S, C, W, partial, gstack, ctr);
                 HIP_TRY(hipGetLastError());
                 const uint64_t rb = (static_cast<uint64_t>(W.bw) * W.bh + 255) / 256;
-                hipLaunchKernelGGL(dev::resolve_kernel, dim3(static_cast<uint32_t>(rb)), dim3(256), 0, stream, partial,
-                                   d_rgb, W, cam->image_w, cam->image_h, C.inv_spp);
+                if (pass)
+                    hipLaunchKernelGGL(dev::accumulate_kernel, dim3(static_cast<uint32_t>(rb)), dim3(256), 0, stream, partial,
+                                       pass->sum, pass->noise, d_rgb, W, cam->image_w, full_chunks, inv_done);
+                else
+                    hipLaunchKernelGGL(dev::resolve_kernel, dim3(static_cast<uint32_t>(rb)), dim3(256), 0, stream, partial,
+                                       d_rgb, W, cam->image_w, cam->image_h, C.inv_spp);
                 HIP_TRY(hipGetLastError());
             }
         }
@@ -2743,7 +2897,7 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
 // and the stack fit the LDS budget, else the stack alone in LDS, else everything in HBM.
 template <typename SE>
 static int dispatch_render(const crt_scene* s, int device, const crt_camera* cam, dev::Work W,
-                           double* d_rgb, hipStream_t st, crt_render_stats* count_stats) {
+                           double* d_rgb, hipStream_t st, crt_render_stats* count_stats, const RenderPass* pass) {
     // depth + 1 levels: walk_step stores the far child at level sp unconditionally
     const size_t stack_bytes = align16(static_cast<size_t>(s->depth + 1) * dev::kBlock * sizeof(SE));
     W.bytes_nodes = static_cast<uint32_t>(align16(s->num_dnodes * sizeof(DevNodeF)));
@@ -2796,12 +2950,12 @@ static int dispatch_render(const crt_scene* s, int device, const crt_camera* cam
         W.lds_stack = stack_at(scene_bytes + W.bytes_sph64);
         const size_t lds = W.lds_stack + stack_bytes;
         if (W.sphere_only)
-            return w5 ? launch_render<SE, false, true, 0, true>(s, device, cam, W, lds, d_rgb, st, count_stats)
-                      : launch_render<SE, false, true, 0, false>(s, device, cam, W, lds, d_rgb, st, count_stats);
+            return w5 ? launch_render<SE, false, true, 0, true>(s, device, cam, W, lds, d_rgb, st, count_stats, pass)
+                      : launch_render<SE, false, true, 0, false>(s, device, cam, W, lds, d_rgb, st, count_stats, pass);
         if (W.quads_flat)
-            return w5 ? launch_render<SE, false, true, 2, true>(s, device, cam, W, lds, d_rgb, st, count_stats)
-                      : launch_render<SE, false, true, 2, false>(s, device, cam, W, lds, d_rgb, st, count_stats);
-        return launch_render<SE, false, true, 1>(s, device, cam, W, W.lds_stack + stack_bytes, d_rgb, st, count_stats);
+            return w5 ? launch_render<SE, false, true, 2, true>(s, device, cam, W, lds, d_rgb, st, count_stats, pass)
+                      : launch_render<SE, false, true, 2, false>(s, device, cam, W, lds, d_rgb, st, count_stats, pass);
+        return launch_render<SE, false, true, 1>(s, device, cam, W, W.lds_stack + stack_bytes, d_rgb, st, count_stats, pass);
     }
     // HBM scene: the top of the (breadth-first) node array goes to LDS as far as it fits beside
     // the stack without costing resident blocks (CRT_WAVES_PER_EU blocks of 4 waves, the VGPR
@@ -2820,17 +2974,17 @@ static int dispatch_render(const crt_scene* s, int device, const crt_camera* cam
         W.lds_nodes = 0;
         W.lds_stack = stack_at(align16(W.ntop));
         if (W.sphere_only)
-            return launch_render<SE, false, false, 0>(s, device, cam, W, W.lds_stack + stack_bytes, d_rgb, st, count_stats);
-        return launch_render<SE, false, false, 1>(s, device, cam, W, W.lds_stack + stack_bytes, d_rgb, st, count_stats);
+            return launch_render<SE, false, false, 0>(s, device, cam, W, W.lds_stack + stack_bytes, d_rgb, st, count_stats, pass);
+        return launch_render<SE, false, false, 1>(s, device, cam, W, W.lds_stack + stack_bytes, d_rgb, st, count_stats, pass);
     }
     W.ntop = top_bytes(per_block);
     W.lds_nodes = 0;
-    if (W.sphere_only) return launch_render<SE, true, false, 0>(s, device, cam, W, W.ntop, d_rgb, st, count_stats);
-    return launch_render<SE, true, false, 1>(s, device, cam, W, W.ntop, d_rgb, st, count_stats);
+    if (W.sphere_only) return launch_render<SE, true, false, 0>(s, device, cam, W, W.ntop, d_rgb, st, count_stats, pass);
+    return launch_render<SE, true, false, 1>(s, device, cam, W, W.ntop, d_rgb, st, count_stats, pass);
 }
 
 int device_render(const crt_scene* s, int device, const crt_camera* cam, const crt_tiling* t,
-                  double* d_rgb, void* stream, crt_render_stats* count_stats) {
+                  double* d_rgb, void* stream, crt_render_stats* count_stats, const RenderPass* pass) {
     int rc = check_device(device);
     if (rc) return rc;
     if (!s->dev[device].valid)
@@ -2880,9 +3034,9 @@ int device_render(const crt_scene* s, int device, const crt_camera* cam, const c
     if (count_stats) HIP_TRY(hipStreamCreate(&st));
     int r;
     if ((s->num_dnodes << kNodeFShift) <= 65536)  // every ref fits a u16 stack entry
-        r = dispatch_render<uint16_t>(s, device, cam, W, d_rgb, st, count_stats);
+        r = dispatch_render<uint16_t>(s, device, cam, W, d_rgb, st, count_stats, pass);
     else
-        r = dispatch_render<uint32_t>(s, device, cam, W, d_rgb, st, count_stats);
+        r = dispatch_render<uint32_t>(s, device, cam, W, d_rgb, st, count_stats, pass);
     if (count_stats) (void)hipStreamDestroy(st);
     return r;
 }
@@ -3237,6 +3391,187 @@ int render_multi(crt_scene* s, const crt_camera* cam, int num_devices, double* h
 int render_multi_ppm(crt_scene* s, const crt_camera* cam, int num_devices, int32_t* h_values,
                      crt_render_stats* stats) {
     return render_multi_impl(s, cam, num_devices, nullptr, h_values, stats);
+}
+
+// crt_noise_estimate: sum se and sum m over `pixels` noise records (noise_stage1_kernel). K = the
+// full chunks among the first samples_done samples; fewer than two give no variance: both NaN.
+int device_noise_estimate(int device, const double* d_noise, size_t pixels, uint32_t spp, uint32_t samples_done,
+                          double* sum_se, double* sum_mean, void* stream) {
+    int rc = check_device(device);
+    if (rc) return rc;
+    const uint32_t L = sample_chunk_len(spp);
+    const uint32_t K = samples_done / L;
+    *sum_se = *sum_mean = std::numeric_limits<double>::quiet_NaN();
+    if (K < 2 || pixels == 0) return CRT_OK;
+    DeviceGuard g(device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* d_tmp = nullptr;  // kNoiseBlocks block results, then the two sums
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_tmp), (dev::kNoiseBlocks + 1) * 2 * sizeof(double), st));
+    double h[2] = {0, 0};
+    hipLaunchKernelGGL(dev::noise_stage1_kernel, dim3(dev::kNoiseBlocks), dim3(256), 0, st, d_noise,
+                       static_cast<uint64_t>(pixels), static_cast<double>(K), static_cast<double>(L), d_tmp);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(dev::noise_stage2_kernel, dim3(1), dim3(256), 0, st, d_tmp, d_tmp + 2 * dev::kNoiseBlocks);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h, d_tmp + 2 * dev::kNoiseBlocks, sizeof h, hipMemcpyDeviceToHost, st);
+    (void)hipFreeAsync(d_tmp, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(CRT_E_HIP, std::string("noise kernels: ") + hipGetErrorString(e));
+    *sum_se = h[0];
+    *sum_mean = h[1];
+    return CRT_OK;
+}
+
+// crt_render_progressive: render_multi_impl's layout (rows dealt in 4-row blocks, one stream per
+// logical device, the gather into device 0, CRT_EMULATE_DEVICES) with the samples cut into passes.
+// Every device keeps its packed running sums (and noise state) for the whole job and renders each
+// pass into them (device_render with a RenderPass); a frame is resolved and gathered only when
+// somebody looks at it: after every pass with CRT_PROGRESS_PREVIEW, else once at the end or when
+// the callback stops the job. A pixel's samples stay on one device, in order, so the final frame
+// is crt_render's bit for bit.
+int render_progressive(crt_scene* s, const crt_camera* cam, int num_devices, uint32_t samples_per_pass,
+                       uint32_t flags, crt_progress_fn fn, void* user, double* h_rgb, uint32_t* samples_done) {
+    int avail = 0;
+    if (hipGetDeviceCount(&avail) != hipSuccess || avail == 0)
+        return fail(CRT_E_NODEVICE, "no HIP device visible (the render path has no CPU fallback)");
+    if (num_devices <= 0) num_devices = avail;
+    num_devices = std::min(num_devices, std::min(avail, kMaxDevices));
+    bool emulate = false;
+    if (const char* e = std::getenv("CRT_EMULATE_DEVICES")) {
+        num_devices = std::max(1, std::min(std::atoi(e), 64));
+        emulate = true;
+    }
+    const int n = num_devices;
+    auto phys = [&](int d) { return emulate ? 0 : d; };
+    const size_t W = cam->image_w, H = cam->image_h;
+    const uint32_t N = cam->samples_per_pixel, L = sample_chunk_len(N);
+    const uint32_t rb = 4;
+    const bool want_noise = (flags & CRT_PROGRESS_NOISE) != 0, want_preview = (flags & CRT_PROGRESS_PREVIEW) != 0;
+    // samples per pass: whole chunks; 0 = a tenth of the job
+    uint64_t per_pass = samples_per_pass ? samples_per_pass : std::max<uint32_t>(1, N / 10);
+    per_pass = (per_pass + L - 1) / L * L;
+    const int n_phys = emulate ? 1 : n;
+    for (int d = 0; d < n_phys; ++d) {
+        const int rc = device_upload(s, d);
+        if (rc) return rc;
+    }
+    std::vector<double*> sums(n, nullptr), noise(n, nullptr), bufs(n, nullptr);
+    std::vector<size_t> px(n, 0);
+    std::vector<hipStream_t> streams(n, nullptr);
+    std::vector<hipEvent_t> ev(n, nullptr);
+    double* frame = nullptr;
+    int rc = CRT_OK;
+    for (int d = 0; d < n && rc == CRT_OK; ++d) {
+        DeviceGuard g(phys(d));
+        px[d] = static_cast<size_t>(count_owned(cam->image_h, rb, static_cast<uint32_t>(n), static_cast<uint32_t>(d))) * W;
+        const size_t bytes = std::max<size_t>(1, px[d]) * 3 * sizeof(double);
+        if (hipStreamCreateWithFlags(&streams[d], hipStreamNonBlocking) != hipSuccess ||
+            hipMalloc(&sums[d], bytes) != hipSuccess || hipMalloc(&bufs[d], bytes) != hipSuccess ||
+            (want_noise && hipMalloc(&noise[d], std::max<size_t>(1, px[d]) * 2 * sizeof(double)) != hipSuccess) ||
+            hipEventCreate(&ev[d]) != hipSuccess) {
+            (void)hipGetLastError();
+            rc = fail(CRT_E_HIP, "progressive render: per-device setup failed on device " + std::to_string(phys(d)));
+        }
+    }
+    if (rc == CRT_OK) {
+        DeviceGuard g(0);
+        if (hipMalloc(&frame, std::max<size_t>(1, H * W) * 3 * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            rc = fail(CRT_E_HIP, "progressive render: frame buffer");
+        }
+    }
+    // every device's resolved rows (bufs) into the frame on device 0, then to h_rgb; blocking
+    auto gather = [&]() -> int {
+        DeviceGuard g(0);
+        for (int d = 0; d < n; ++d) {
+            if (!emulate && d > 0) enable_peer_once(0, d);
+            {
+                DeviceGuard gd(phys(d));
+                if (hipEventRecord(ev[d], streams[d]) != hipSuccess) return fail(CRT_E_HIP, "progressive render: event");
+            }
+            if (d > 0 && hipStreamWaitEvent(streams[0], ev[d], 0) != hipSuccess)
+                return fail(CRT_E_HIP, "progressive render: gather wait failed");
+            const hipError_t e = gather_packed(reinterpret_cast<char*>(frame), reinterpret_cast<const char*>(bufs[d]), H, rb,
+                                               n, d, W * 3 * sizeof(double), streams[0]);
+            if (e != hipSuccess)
+                return fail(CRT_E_HIP, std::string("progressive render: gather from device ") + std::to_string(d) + ": " +
+                                           hipGetErrorString(e));
+        }
+        hipError_t e = hipMemcpyAsync(h_rgb, frame, H * W * 3 * sizeof(double), hipMemcpyDeviceToHost, streams[0]);
+        if (e == hipSuccess) e = hipStreamSynchronize(streams[0]);
+        if (e != hipSuccess) return fail(CRT_E_HIP, std::string("progressive render: ") + hipGetErrorString(e));
+        return CRT_OK;
+    };
+    uint32_t done = 0;
+    bool have_frame = false;
+    while (rc == CRT_OK && done < N) {
+        const uint32_t count = static_cast<uint32_t>(std::min<uint64_t>(per_pass, N - done));
+        const bool last = done + count == N;
+        have_frame = last || (want_preview && fn);
+        for (int d = 0; d < n && rc == CRT_OK; ++d) {
+            crt_tiling t{rb, static_cast<uint32_t>(n), static_cast<uint32_t>(d), CRT_TILING_PACKED};
+            const RenderPass pass{done, count, sums[d], noise[d]};
+            rc = device_render(s, phys(d), cam, &t, have_frame ? bufs[d] : nullptr, streams[d], nullptr, &pass);
+        }
+        if (rc != CRT_OK) break;
+        done += count;
+        double figure = std::numeric_limits<double>::quiet_NaN();
+        if (want_noise && fn) {  // sum se / sum m over the devices' pixels, in device order
+            double se = 0, mean = 0;
+            bool any = false;
+            for (int d = 0; d < n && rc == CRT_OK; ++d) {
+                if (!px[d]) continue;
+                double a = 0, b = 0;
+                rc = device_noise_estimate(phys(d), noise[d], px[d], N, done, &a, &b, streams[d]);
+                se += a;
+                mean += b;
+                any = true;
+            }
+            if (rc != CRT_OK) break;
+            if (any) figure = se / mean;
+        }
+        if (have_frame) {
+            rc = gather();
+        } else {
+            for (int d = 0; d < n && rc == CRT_OK; ++d) {
+                DeviceGuard g(phys(d));
+                const hipError_t e = hipStreamSynchronize(streams[d]);
+                if (e != hipSuccess)
+                    rc = fail(CRT_E_HIP, std::string("render on device ") + std::to_string(phys(d)) + ": " + hipGetErrorString(e));
+            }
+        }
+        if (rc != CRT_OK) break;
+        if (fn && fn(user, done, N, figure, want_preview ? h_rgb : nullptr) != 0) break;
+    }
+    // stopped between previews: the mean of the samples so far from the running sums
+    if (rc == CRT_OK && !have_frame && done > 0) {
+        for (int d = 0; d < n && rc == CRT_OK; ++d) {
+            if (!px[d]) continue;
+            DeviceGuard g(phys(d));
+            const uint64_t cnt = static_cast<uint64_t>(px[d]) * 3;
+            hipLaunchKernelGGL(dev::scale_kernel, dim3(static_cast<uint32_t>((cnt + 255) / 256)), dim3(256), 0, streams[d],
+                               sums[d], bufs[d], cnt, 1 / static_cast<double>(done));
+            if (hipGetLastError() != hipSuccess) rc = fail(CRT_E_HIP, "progressive render: scale_kernel launch");
+        }
+        if (rc == CRT_OK) rc = gather();
+    }
+    for (int d = 0; d < n; ++d) {
+        DeviceGuard g(phys(d));
+        if (streams[d]) (void)hipStreamSynchronize(streams[d]);
+        if (sums[d]) (void)hipFree(sums[d]);
+        if (noise[d]) (void)hipFree(noise[d]);
+        if (bufs[d]) (void)hipFree(bufs[d]);
+        if (streams[d]) (void)hipStreamDestroy(streams[d]);
+        if (ev[d]) (void)hipEventDestroy(ev[d]);
+    }
+    if (frame) {
+        DeviceGuard g(0);
+        (void)hipFree(frame);
+    }
+    if (samples_done) *samples_done = done;
+    return rc;
 }
 
 // The compile-time switches this library was built with (bench.py hashes them with the kernel

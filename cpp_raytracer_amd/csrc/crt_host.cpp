@@ -1198,6 +1198,53 @@ int crt_render_async(const crt_scene* s, int device, const crt_camera* cam,
     return device_render(s, device, cam, tiling, d_rgb, stream, nullptr);
 }
 
+uint32_t crt_sample_chunk_len(uint32_t samples_per_pixel) { return sample_chunk_len(samples_per_pixel); }
+
+int crt_render_pass_async(const crt_scene* s, int device, const crt_camera* cam, const crt_tiling* tiling,
+                          uint32_t first_sample, uint32_t num_samples, double* d_sum, double* d_noise,
+                          double* d_rgb, void* stream) {
+    clear_error();
+    if (!s || !cam) return fail(CRT_E_INVALID, "crt_render_pass_async: null argument");
+    if (!d_sum) return fail(CRT_E_INVALID, "crt_render_pass_async: d_sum is null (the running sums are required)");
+    const uint32_t N = cam->samples_per_pixel, L = sample_chunk_len(N);
+    const std::string len = " (chunk length " + std::to_string(L) + " at " + std::to_string(N) + " spp)";
+    if (num_samples == 0) return fail(CRT_E_INVALID, "crt_render_pass_async: num_samples is 0");
+    if (first_sample % L != 0)
+        return fail(CRT_E_INVALID, "crt_render_pass_async: first_sample " + std::to_string(first_sample) +
+                                       " is not a multiple of the chunk length" + len);
+    const uint64_t end = static_cast<uint64_t>(first_sample) + num_samples;
+    if (end > N)
+        return fail(CRT_E_INVALID, "crt_render_pass_async: first_sample + num_samples = " + std::to_string(end) +
+                                       " exceeds samples_per_pixel = " + std::to_string(N));
+    if (end != N && end % L != 0)
+        return fail(CRT_E_INVALID, "crt_render_pass_async: the pass ends at sample " + std::to_string(end) +
+                                       ", neither a multiple of the chunk length nor samples_per_pixel" + len);
+    const RenderPass pass{first_sample, num_samples, d_sum, d_noise};
+    return device_render(s, device, cam, tiling, d_rgb, stream, nullptr, &pass);
+}
+
+int crt_noise_estimate(int device, const double* d_noise, size_t pixels, uint32_t samples_per_pixel,
+                       uint32_t samples_done, double* sum_se, double* sum_mean, void* stream) {
+    clear_error();
+    if (!sum_se || !sum_mean || (pixels && !d_noise)) return fail(CRT_E_INVALID, "crt_noise_estimate: null argument");
+    if (samples_done > samples_per_pixel)
+        return fail(CRT_E_INVALID, "crt_noise_estimate: samples_done exceeds samples_per_pixel");
+    return device_noise_estimate(device, d_noise, pixels, samples_per_pixel, samples_done, sum_se, sum_mean, stream);
+}
+
+int crt_render_progressive(crt_scene* s, const crt_camera* cam, int num_devices, uint32_t samples_per_pass,
+                           uint32_t flags, crt_progress_fn fn, void* user, double* h_rgb,
+                           uint32_t* samples_done) {
+    clear_error();
+    if (samples_done) *samples_done = 0;
+    if (!s || !cam || !h_rgb) return fail(CRT_E_INVALID, "crt_render_progressive: null argument");
+    if (flags & ~(CRT_PROGRESS_NOISE | CRT_PROGRESS_PREVIEW))
+        return fail(CRT_E_INVALID, "crt_render_progressive: unknown flags");
+    if (cam->samples_per_pixel == 0) return fail(CRT_E_INVALID, "crt_render_progressive: samples_per_pixel is 0");
+    if (cam->image_w == 0 || cam->image_h == 0) return fail(CRT_E_INVALID, "empty image");
+    return render_progressive(s, cam, num_devices, samples_per_pass, flags, fn, user, h_rgb, samples_done);
+}
+
 int crt_render_count(const crt_scene* s, int device, const crt_camera* cam,
                      const crt_tiling* tiling, crt_render_stats* stats) {
     clear_error();

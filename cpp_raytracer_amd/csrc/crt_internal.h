@@ -372,8 +372,23 @@ void clear_error();
 // device side (crt_device.hip)
 int device_upload(crt_scene* s, int device);
 void device_release(crt_scene* s);
+// One pass of a progressive render (crt_render_pass_async, which checks the alignment rules):
+// samples [first, first + count) of every owned pixel go into the running sums `sum` and the noise
+// state `noise` (may be null), and d_rgb (may be null) gets the frame so far.
+struct RenderPass {
+    uint32_t first, count;
+    double* sum;
+    double* noise;
+};
+uint32_t sample_chunk_len(uint32_t spp);
 int device_render(const crt_scene* s, int device, const crt_camera* cam, const crt_tiling* t,
-                  double* d_rgb, void* stream, crt_render_stats* count_stats);
+                  double* d_rgb, void* stream, crt_render_stats* count_stats,
+                  const RenderPass* pass = nullptr);
+int device_noise_estimate(int device, const double* d_noise, size_t pixels, uint32_t spp,
+                          uint32_t samples_done, double* sum_se, double* sum_mean, void* stream);
+int render_progressive(crt_scene* s, const crt_camera* cam, int num_devices, uint32_t samples_per_pass,
+                       uint32_t flags, crt_progress_fn fn, void* user, double* h_rgb,
+                       uint32_t* samples_done);
 int device_closest_hits(crt_scene* s, int device, const double* rays, size_t n, double t_min,
                         double t_max, crt_hit* out);
 int device_count(int* n);

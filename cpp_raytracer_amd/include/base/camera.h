@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <iostream>
 #include <numbers>
 #include <optional>
@@ -25,6 +26,7 @@
 #include "acceleration/bvh.h"
 #include "math/ray3d.h"
 #include "util/image.h"
+#include "util/progressbar.h"
 
 class Camera {
     size_t image_w = 1280, image_h = 720;
@@ -152,7 +154,73 @@ class Camera {
         return img;
     }
 
+    // render_scene in passes (crt_render_progressive): one ProgressBar tick and one on_pass call
+    // per pass; on_pass returning false stops the render with the image of the samples so far
+    struct ProgressiveCtx {
+        ProgressBar<>* bar;
+        const std::function<bool(size_t, size_t, double)>* on_pass;
+    };
+    static int progressive_pass(void* user, uint32_t done, uint32_t total, double noise, const double*) {
+        auto* ctx = static_cast<ProgressiveCtx*>(user);
+        ctx->bar->complete_iteration();
+        return (*ctx->on_pass && !(*ctx->on_pass)(done, total, noise)) ? 1 : 0;
+    }
+
+    Image render_scene_progressive(const crt_api::GpuScene& g, size_t samples_per_pass,
+                                   const std::function<bool(size_t, size_t, double)>& on_pass) {
+        crt_scene* scene = g.get();
+        init();
+        if (const char* dump = std::getenv("CRT_DUMP_SCENE")) dump_and_exit(g, dump);
+        resolved.base_seed = SeedSeqGenerator::get_instance().next_seed();
+        int devices = 0;
+        if (crt_device_count(&devices) || devices == 0) crt_api::die("Camera::render_progressive");
+        if (const char* e = std::getenv("CRT_NUM_DEVICES")) devices = std::max(1, std::min(devices, std::atoi(e)));
+        if (samples_per_pass > UINT32_MAX) samples_per_pass = UINT32_MAX;
+        // the passes crt_render_progressive will run: whole chunks, 0 = a tenth of the samples
+        const size_t chunk = crt_sample_chunk_len(resolved.samples_per_pixel);
+        size_t per_pass = samples_per_pass ? samples_per_pass : std::max<size_t>(1, samples_per_pixel / 10);
+        per_pass = (per_pass + chunk - 1) / chunk * chunk;
+        ProgressBar<> bar((samples_per_pixel + per_pass - 1) / per_pass,
+                          "Rendering " + std::to_string(image_w) + " x " + std::to_string(image_h) + " image (" +
+                              std::to_string(samples_per_pixel) + " spp) in passes on " + std::to_string(devices) +
+                              " GPU" + (devices > 1 ? "s" : ""));
+        std::vector<double> rgb(image_w * image_h * 3);
+        ProgressiveCtx ctx{&bar, &on_pass};
+        uint32_t done = 0;
+        if (crt_render_progressive(scene, &resolved, devices, static_cast<uint32_t>(samples_per_pass),
+                                   on_pass ? CRT_PROGRESS_NOISE : 0u, progressive_pass, &ctx, rgb.data(), &done))
+            crt_api::die("Camera::render_progressive");
+        if (done < samples_per_pixel)
+            std::cout << "Rendering stopped after " << done << " of " << samples_per_pixel << " spp\n" << std::endl;
+        auto img = Image::with_dimensions(image_w, image_h);
+        for (size_t r = 0; r < image_h; ++r)
+            for (size_t c = 0; c < image_w; ++c) {
+                const double* p = &rgb[(r * image_w + c) * 3];
+                img[r][c] = RGB::from_mag(p[0], p[1], p[2]);
+            }
+        return img;
+    }
+
 public:
+    // Extension (not in the reference): render in passes of samples_per_pass samples per pixel
+    // (0 = a tenth of them; rounded up to whole sample chunks), ticking a ProgressBar once a pass.
+    // on_pass(samples done, samples in all, relative noise of the frame so far) returning false
+    // stops the render and returns the image of the samples rendered so far. Rendered to the end,
+    // the image is render()'s bit for bit.
+    template <typename T>
+    requires std::is_base_of_v<Hittable, T>
+    Image render_progressive(const T& world, size_t samples_per_pass = 0,
+                             std::function<bool(size_t done, size_t total, double noise)> on_pass = {}) {
+        if constexpr (std::is_same_v<T, BVH>) {
+            return render_scene_progressive(world.gpu_scene(), samples_per_pass, on_pass);
+        } else if constexpr (std::is_same_v<T, Scene>) {
+            return render_progressive(BVH(world), samples_per_pass, on_pass);
+        } else {
+            crt_api::GpuScene s(world, 32, 12, true);
+            return render_scene_progressive(s, samples_per_pass, on_pass);
+        }
+    }
+
     // camera.h:264-297: a BVH renders through its own node arrays; any other Hittable renders
     // with the semantics of its own hit_by (one always-entered leaf in object order)
     template <typename T>

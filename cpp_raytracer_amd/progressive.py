@@ -1,0 +1,128 @@
+"""A render driven pass by pass on one device: previews, a noise readout, checkpoint and resume.
+
+ProgressiveRender keeps the pixels' running sums (and the noise state) in device tensors and
+issues crt_render_pass_async passes in order at chunk boundaries, so the frame after the last pass
+is bit-identical to GpuScene.render_async's. state() / resume() carry a render across processes:
+the sums are copied exactly, so a resumed render ends on the same bits too.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+
+from . import Camera, CrtError, GpuScene, Tiling, noise_estimate, sample_chunk_len
+
+
+def _owned_rows(height: int, tiling: Optional[Tiling]) -> int:
+    if tiling is None or not (tiling.flags & 1):  # CRT_TILING_PACKED
+        return height
+    return sum(1 for r in range(height) if (r // tiling.row_block) % tiling.tile_count == tiling.tile_index)
+
+
+class ProgressiveRender:
+    """Samples [0, cam.samples_per_pixel) of `scene` on `device`, a step at a time.
+
+    tiling: the rows this render owns (crt_tiling semantics; with CRT_TILING_PACKED the buffers
+    hold the owned rows only). noise=False drops the noise state (2 doubles a pixel)."""
+
+    def __init__(self, scene: GpuScene, cam: Camera, device: int = 0, tiling: Optional[Tiling] = None,
+                 noise: bool = True):
+        import torch
+        if cam.samples_per_pixel == 0:
+            raise CrtError("ProgressiveRender: samples_per_pixel is 0")
+        self.scene, self.cam, self.device, self.tiling = scene, cam, device, tiling
+        self.chunk_len = sample_chunk_len(cam.samples_per_pixel)
+        self.samples_done = 0
+        scene.upload(device)
+        rows = _owned_rows(cam.image_h, tiling)
+        dev = torch.device("cuda", device)
+        self._sum = torch.zeros(rows, cam.image_w, 3, dtype=torch.float64, device=dev)
+        self._noise = torch.zeros(rows, cam.image_w, 2, dtype=torch.float64, device=dev) if noise else None
+        self._out = torch.zeros(rows, cam.image_w, 3, dtype=torch.float64, device=dev)
+
+    @property
+    def samples_total(self) -> int:
+        return int(self.cam.samples_per_pixel)
+
+    @property
+    def finished(self) -> bool:
+        return self.samples_done >= self.samples_total
+
+    def step(self, count: int = 0):
+        """Render the next `count` samples per pixel, rounded up to whole chunks and cut at the
+        job's end (0: one chunk). Returns the frame so far: the same device tensor every call,
+        (rows, w, 3) float64, valid once the current stream reaches this point."""
+        import torch
+        if self.finished:
+            raise CrtError("ProgressiveRender.step: every sample is already rendered")
+        if count < 0:
+            raise CrtError("ProgressiveRender.step: negative count")
+        L = self.chunk_len
+        count = max(L, (count + L - 1) // L * L)
+        count = min(count, self.samples_total - self.samples_done)
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream().cuda_stream
+        self.scene.render_pass(self.device, self.cam, self.samples_done, count, self._sum.data_ptr(),
+                               self._noise.data_ptr() if self._noise is not None else 0,
+                               self._out.data_ptr(), st, self.tiling)
+        self.samples_done += count
+        return self._out
+
+    def noise(self) -> float:
+        """The frame's relative noise so far: the pixels' standard errors summed over their means
+        summed (crt_noise_estimate). NaN before two chunks are done."""
+        import torch
+        if self._noise is None:
+            raise CrtError("ProgressiveRender.noise: built with noise=False")
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream().cuda_stream
+        se, mean = noise_estimate(self.device, self._noise.data_ptr(), self._noise.shape[0] * self._noise.shape[1],
+                                  self.samples_total, self.samples_done, st)
+        return se / mean if mean == mean and mean != 0 else float("nan")
+
+    def state(self) -> dict:
+        """A checkpoint: the running sums (and noise state) as numpy arrays, and what identifies
+        the job. np.savez(path, **state) stores it."""
+        t = self.tiling
+        d = {
+            "sum": self._sum.cpu().numpy(),
+            "samples_done": self.samples_done,
+            "spp": self.samples_total,
+            "base_seed": int(self.cam.base_seed),
+            "width": int(self.cam.image_w),
+            "height": int(self.cam.image_h),
+            "tiling": np.array([t.row_block, t.tile_count, t.tile_index, t.flags] if t is not None else [1, 1, 0, 0],
+                               np.uint32),
+        }
+        if self._noise is not None:
+            d["noise"] = self._noise.cpu().numpy()
+        return d
+
+    @classmethod
+    def resume(cls, scene: GpuScene, cam: Camera, state: dict, device: int = 0) -> "ProgressiveRender":
+        """Continue the render of a state() checkpoint. The state must be of this job: the same
+        samples per pixel (they fix the chunking), base seed and frame size as `cam`."""
+        for key, want in (("spp", cam.samples_per_pixel), ("base_seed", cam.base_seed),
+                          ("width", cam.image_w), ("height", cam.image_h)):
+            got = int(state[key])
+            if got != int(want):
+                raise CrtError(f"ProgressiveRender.resume: the state's {key} is {got}, the camera's {int(want)}")
+        done = int(state["samples_done"])
+        L = sample_chunk_len(cam.samples_per_pixel)
+        if done < 0 or done > cam.samples_per_pixel or (done % L and done != cam.samples_per_pixel):
+            raise CrtError(f"ProgressiveRender.resume: samples_done = {done} is not a pass boundary")
+        tl = [int(v) for v in np.asarray(state["tiling"]).reshape(-1)]
+        tiling = None if tl == [1, 1, 0, 0] else Tiling(*tl)
+        rows = _owned_rows(cam.image_h, tiling)
+        total = np.asarray(state["sum"])
+        if total.shape != (rows, cam.image_w, 3) or total.dtype != np.float64:
+            raise CrtError(f"ProgressiveRender.resume: the state's sums have shape {total.shape}, "
+                           f"the job's {(rows, int(cam.image_w), 3)}")
+        import torch
+        r = cls(scene, cam, device, tiling, noise="noise" in state)
+        r._sum.copy_(torch.from_numpy(np.ascontiguousarray(total)))
+        if r._noise is not None:
+            r._noise.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(state["noise"], np.float64))))
+        r.samples_done = done
+        return r

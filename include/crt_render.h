@@ -239,6 +239,66 @@ int crt_camera_resolve(const crt_camera_settings* settings, crt_camera* out);
 int crt_render_async(const crt_scene* scene, int device, const crt_camera* cam,
                      const crt_tiling* tiling, double* d_rgb, void* stream);
 
+/* ---- progressive rendering ---------------------------------------------------------------
+ * A render's samples are grouped into chunks of crt_sample_chunk_len(samples_per_pixel) samples
+ * (the last chunk of a pixel may be shorter); a pixel's value is the chunk sums added in chunk
+ * order, times 1 / samples_per_pixel. A render cut into passes at chunk boundaries and
+ * accumulated in chunk order makes the same additions, so its final frame equals the one-shot
+ * frame of crt_render_async bit for bit. */
+
+/* Samples per chunk of a render with this many samples per pixel: max(4, ceil(spp / 192)).
+ * Pass boundaries are multiples of it. */
+uint32_t crt_sample_chunk_len(uint32_t samples_per_pixel);
+
+/* One pass: samples [first_sample, first_sample + num_samples) of every owned pixel, of a job of
+ * cam->samples_per_pixel samples in all (that total fixes the chunking and the seeds).
+ *   d_sum    DEVICE, the layout of crt_render_async's d_rgb (whole frame, or the owned rows packed
+ *            under CRT_TILING_PACKED): the pixels' running sums. first_sample == 0 overwrites it
+ *            (and d_noise); any other pass adds to it.
+ *   d_noise  DEVICE or NULL, 2 doubles per pixel at the same pixel addresses: t = sum of y and
+ *            q = sum of y * y over the full-length chunks so far, y = (r + g) + b of a chunk's sum
+ *            (the state crt_noise_estimate reads). A ragged last chunk is left out.
+ *   d_rgb    DEVICE or NULL, as crt_render_async's: the frame so far, sum * (1 / (double)(first_sample
+ *            + num_samples)); after the last pass, the one-shot frame.
+ * CRT_E_INVALID (the message names the rule) unless first_sample is a multiple of the chunk
+ * length, num_samples > 0, first_sample + num_samples <= samples_per_pixel, the end is a multiple
+ * of the chunk length or equals samples_per_pixel, and d_sum is not NULL.
+ * The call keeps no state: issuing each pass once, in increasing order, on one stream (or
+ * otherwise ordered) is the caller's job. In order, the final frame is bit-identical to the
+ * one-shot frame; passes after the first issued out of order still give a correct mean, equal
+ * within rounding (floating-point addition is not associative). Enqueued on `stream`. */
+int crt_render_pass_async(const crt_scene* scene, int device, const crt_camera* cam,
+                          const crt_tiling* tiling, uint32_t first_sample, uint32_t num_samples,
+                          double* d_sum, double* d_noise, double* d_rgb, void* stream);
+
+/* Noise of `pixels` d_noise records (device memory on `device`) after samples_done samples of a
+ * samples_per_pixel job. With L = the chunk length and K = samples_done / L full chunks, a pixel
+ * has m = t / (K L), the mean of r + g + b, and se = sqrt(max(0, q / L^2 - K m^2) / (K (K - 1))),
+ * the standard error of m. *sum_se and *sum_mean (HOST) receive the sums of se and of m over the
+ * pixels; sum_se / sum_mean is the frame's relative noise. Both are NaN while K < 2. The sums are
+ * taken in a fixed order: repeated calls give the same bits. Synchronous on `stream`. */
+int crt_noise_estimate(int device, const double* d_noise, size_t pixels, uint32_t samples_per_pixel,
+                       uint32_t samples_done, double* sum_se, double* sum_mean, void* stream);
+
+/* Progress callback of crt_render_progressive, called on the calling thread after every pass:
+ * noise is sum_se / sum_mean over the frame with CRT_PROGRESS_NOISE (NaN without it, or before two
+ * chunks are done); h_rgb is the caller's frame buffer holding the frame so far with
+ * CRT_PROGRESS_PREVIEW, else NULL. A non-zero return stops the render. */
+typedef int (*crt_progress_fn)(void* user, uint32_t samples_done, uint32_t samples_total,
+                               double noise, const double* h_rgb);
+#define CRT_PROGRESS_NOISE 1u
+#define CRT_PROGRESS_PREVIEW 2u
+
+/* Blocking whole-frame render over devices [0, num_devices) as crt_render's, in passes of
+ * samples_per_pass samples (rounded up to whole chunks; 0 = a tenth of the job, at least one
+ * chunk). fn may be NULL. h_rgb (HOST, image_w*image_h*3 doubles) is written after every pass with
+ * CRT_PROGRESS_PREVIEW, else once when the render ends. When it ends after all samples h_rgb is
+ * crt_render's frame bit for bit; when fn stops it, the mean of the *samples_done (may be NULL)
+ * samples rendered so far. */
+int crt_render_progressive(crt_scene* scene, const crt_camera* cam, int num_devices,
+                           uint32_t samples_per_pass, uint32_t flags, crt_progress_fn fn, void* user,
+                           double* h_rgb, uint32_t* samples_done);
+
 /* Instrumented pass: counts the work of the same render (never timed). */
 int crt_render_count(const crt_scene* scene, int device, const crt_camera* cam,
                      const crt_tiling* tiling, crt_render_stats* stats);
