@@ -18,13 +18,13 @@ import numpy as np
 from . import _capi
 from ._capi import (CRT_BOX, CRT_DIELECTRIC, CRT_DIFFUSE_LIGHT, CRT_LAMBERTIAN, CRT_METAL,
                     CRT_PARALLELOGRAM, CRT_SPHERE, HIT_DTYPE, MATERIAL_DTYPE, NODE_DTYPE,
-                    OBJECT_DTYPE, BVHParams, Camera, CameraSettings, CrtError, RenderStats,
+                    OBJECT_DTYPE, CRT_BLOCK_STOPPED, BVHParams, Camera, CameraSettings, CrtError, RenderStats,
                     SceneInfo, Tiling, check, lib)
 
 __all__ = [
     "SceneData", "GpuScene", "CameraSettings", "Camera", "Tiling", "RenderStats", "CrtError",
     "resolve_camera", "sample_seed", "rand_double", "device_count", "lib", "ppm_values", "write_ppm",
-    "sample_chunk_len", "noise_estimate",
+    "sample_chunk_len", "noise_estimate", "block_count", "adaptive_update", "CRT_BLOCK_STOPPED",
     "CRT_LAMBERTIAN", "CRT_METAL", "CRT_DIELECTRIC", "CRT_DIFFUSE_LIGHT",
     "CRT_SPHERE", "CRT_PARALLELOGRAM", "CRT_BOX",
 ]
@@ -59,6 +59,27 @@ def noise_estimate(device: int, noise_ptr: int, pixels: int, spp: int, samples_d
     check(lib().crt_noise_estimate(device, C.c_void_p(noise_ptr), pixels, spp, samples_done,
                                    C.byref(se), C.byref(mean), C.c_void_p(stream)), "crt_noise_estimate")
     return se.value, mean.value
+
+
+def block_count(image_w: int, owned_rows: int) -> int:
+    """Blocks (16 columns x 4 owned rows, the render kernel's tile) of owned_rows rows of an
+    image_w wide frame (crt_block_count): the words of an adaptive render's block state."""
+    return int(lib().crt_block_count(image_w, owned_rows))
+
+
+def adaptive_update(device: int, cam: Camera, noise_ptr: int, blocks_ptr: int, samples_done: int,
+                    threshold: float, min_samples: int = 0, stream: int = 0,
+                    tiling: Optional[Tiling] = None) -> int:
+    """The stopping rule of an adaptive render (crt_adaptive_update): every block at samples_done
+    whose summed standard error is at most threshold times its summed mean, and that has
+    min_samples samples and two chunks, gets CRT_BLOCK_STOPPED. Returns the number of blocks still
+    active. Waits for the stream."""
+    t = C.byref(tiling) if tiling is not None else None
+    n = C.c_uint32(0)
+    check(lib().crt_adaptive_update(device, C.byref(cam), t, C.c_void_p(noise_ptr), C.c_void_p(blocks_ptr),
+                                    samples_done, threshold, min_samples, C.byref(n), C.c_void_p(stream)),
+          "crt_adaptive_update")
+    return int(n.value)
 
 
 def device_count() -> int:
@@ -231,6 +252,53 @@ class GpuScene:
                                           C.c_void_p(sum_ptr), C.c_void_p(noise_ptr or None),
                                           C.c_void_p(out_ptr or None), C.c_void_p(stream)),
               "crt_render_pass_async")
+
+    def render_pass_masked(self, device: int, cam: Camera, first: int, count: int, sum_ptr: int,
+                           noise_ptr: int, out_ptr: int, blocks_ptr: int, active_hint: int = 0,
+                           stream: int = 0, tiling: Optional[Tiling] = None) -> None:
+        """render_pass for the blocks whose word at blocks_ptr equals `first` only
+        (crt_render_pass_masked_async); their words become first + count. active_hint: how many
+        blocks the caller expects to be rendered (0: unknown); it never changes the result."""
+        t = C.byref(tiling) if tiling is not None else None
+        check(lib().crt_render_pass_masked_async(self._h, device, C.byref(cam), t, first, count,
+                                                 C.c_void_p(sum_ptr), C.c_void_p(noise_ptr or None),
+                                                 C.c_void_p(out_ptr or None), C.c_void_p(blocks_ptr or None),
+                                                 min(active_hint, 0xFFFFFFFF), C.c_void_p(stream)),
+              "crt_render_pass_masked_async")
+
+    def render_adaptive(self, cam: Camera, threshold: float, min_samples: int = 0, samples_per_pass: int = 0,
+                        callback=None, num_devices: int = 1,
+                        preview: bool = False) -> tuple[np.ndarray, np.ndarray, int]:
+        """Blocking adaptive render (crt_render_adaptive): blocks of 16 x 4 pixels stop between
+        passes once their noise is at most `threshold`. callback(samples_done, samples_total,
+        active_blocks, total_blocks, frame) runs after every pass (frame as render_progressive's);
+        a true return stops the render. Returns (frame, the blocks' sample counts as a
+        (ceil(h / 4), ceil(w / 16)) uint32 array, the samples rendered over all pixels)."""
+        out = np.empty((cam.image_h, cam.image_w, 3), np.float64)
+        counts = np.zeros(((cam.image_h + 3) // 4, (cam.image_w + 15) // 16), np.uint32)
+        raised = []
+
+        def trampoline(_user, done, total, active, blocks, h_rgb):
+            try:
+                return 1 if callback(done, total, active, blocks, out if h_rgb else None) else 0
+            except BaseException as e:  # not through the C frames: stop, raise after the call
+                raised.append(e)
+                return 1
+
+        fn = _capi.ADAPTIVE_FN(trampoline) if callback is not None else _capi.ADAPTIVE_FN()
+        prm = _capi.AdaptiveParams(threshold, min_samples, samples_per_pass,
+                                   _capi.CRT_PROGRESS_PREVIEW if preview else 0, 0)
+        rendered = C.c_uint64(0)
+        rc = lib().crt_render_adaptive(self._h, C.byref(cam), num_devices, C.byref(prm), fn, None,
+                                       out.ctypes.data, counts.ctypes.data, C.byref(rendered))
+        if raised:
+            raise raised[0]
+        check(rc, "crt_render_adaptive")
+        return out, counts, int(rendered.value)
+
+    # the module functions, beside the passes they go with
+    adaptive_update = staticmethod(adaptive_update)
+    block_count = staticmethod(block_count)
 
     def render_progressive(self, cam: Camera, samples_per_pass: int = 0, callback=None, num_devices: int = 1,
                            preview: bool = False, noise: bool = False) -> tuple[np.ndarray, int]:

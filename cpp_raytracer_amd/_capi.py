@@ -87,6 +87,11 @@ class RenderStats(C.Structure):
                 ("candidate_tests", C.c_uint64), ("wave_iters_candidates", C.c_uint64)]
 
 
+class AdaptiveParams(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("min_samples", C.c_uint32), ("samples_per_pass", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # numpy views of the same records (for bulk scene I/O)
 MATERIAL_DTYPE = np.dtype([("kind", "<u4"), ("reserved", "<u4"), ("color", "<f8", 3), ("param", "<f8")])
 OBJECT_DTYPE = np.dtype([("kind", "<u4"), ("material", "<u4"), ("v", "<f8", 9)])
@@ -103,6 +108,9 @@ P = C.POINTER
 # crt_progress_fn(user, samples_done, samples_total, noise, h_rgb) -> non-zero stops the render
 CRT_PROGRESS_NOISE, CRT_PROGRESS_PREVIEW = 1, 2
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.c_void_p)
+# crt_adaptive_fn(user, samples_done, samples_total, active_blocks, total_blocks, h_rgb)
+ADAPTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p)
+CRT_BLOCK_W, CRT_BLOCK_H, CRT_BLOCK_STOPPED = 16, 4, 0x80000000
 EXPORTS = {
     "crt_abi_version": (C.c_int, []),
     "crt_last_error": (C.c_char_p, []),
@@ -129,6 +137,14 @@ EXPORTS = {
                                      P(C.c_double), P(C.c_double), C.c_void_p]),
     "crt_render_progressive": (C.c_int, [C.c_void_p, P(Camera), C.c_int, C.c_uint32, C.c_uint32, PROGRESS_FN,
                                          C.c_void_p, C.c_void_p, P(C.c_uint32)]),
+    "crt_block_count": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "crt_render_pass_masked_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Tiling), C.c_uint32, C.c_uint32,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                               C.c_void_p]),
+    "crt_adaptive_update": (C.c_int, [C.c_int, P(Camera), P(Tiling), C.c_void_p, C.c_void_p, C.c_uint32,
+                                      C.c_double, C.c_uint32, P(C.c_uint32), C.c_void_p]),
+    "crt_render_adaptive": (C.c_int, [C.c_void_p, P(Camera), C.c_int, P(AdaptiveParams), ADAPTIVE_FN, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, P(C.c_uint64)]),
     "crt_render_count": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Tiling), P(RenderStats)]),
     "crt_render": (C.c_int, [C.c_void_p, P(Camera), C.c_int, C.c_void_p, P(RenderStats)]),
     "crt_render_ppm": (C.c_int, [C.c_void_p, P(Camera), C.c_int, C.c_void_p, P(RenderStats)]),

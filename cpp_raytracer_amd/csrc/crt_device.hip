@@ -1805,10 +1805,14 @@ __device__ __forceinline__ void set_prio() {
 // only, no sphere paths)
 // W5: 5 waves per SIMD (96 VGPRs, ~40-48 of them spilled), launched for sphere-only and
 // flat-parallelogram LDS scenes whose LDS copy leaves room for five blocks per CU (dispatch_render)
-template <typename SE, bool GSTACK, bool LSCENE, bool COUNT, int PM, bool W5>
+// MASK: the masked pass of an adaptive render (crt_render_pass_masked_async). The queues run over
+// the band's active tiles only: active[0] = their number, active[1 + i] = the band tile of list
+// entry i, in tile-major order (active_list_kernel). A separate instance: the unmasked instances
+// keep their code.
+template <typename SE, bool GSTACK, bool LSCENE, bool COUNT, int PM, bool W5, bool MASK = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kManyWaves : LSCENE ? CRT_WAVES_PER_EU_LDS : CRT_WAVES_PER_EU, 8))) void render_kernel(
     SceneView Sg, CamView C, Work W, double* __restrict__ partial, SE* __restrict__ gstack,
-    Counters* __restrict__ counters) {
+    Counters* __restrict__ counters, const uint32_t* __restrict__ active) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // the instances with PM = 0 are launched for sphere-only scenes only, PM = 2 for scenes of
     // axis-aligned parallelograms only: the other primitive's paths are compiled out of them
@@ -1876,6 +1880,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kMa
     // the next units in lane order. A unit's sum goes to partial[chunk][pixel] whichever lane
     // traced it, so frames do not depend on the schedule.
     uint32_t item_pos = 0, item_units = 0;
+    // tiles in the queues: the band's, or (MASK) the true number of active ones, whatever the host
+    // sized the grid and the items for
+    const uint32_t q_tiles = MASK ? active[0] : W.tiles;
     uint32_t seg = blockIdx.x % W.segments, seg_tried = 0;  // the wave's queue (XCD-local first)
     uint32_t item_txy = 0, item_chunk = 0;
     // the lane's unit: tile (tx | ty << 16), chunk << 6 | tile pixel; and its current sample
@@ -1926,8 +1933,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kMa
                 item_pos = 0;
                 // this wave's segment first, then the others in turn; seg == segments: all dry
                 while (seg < W.segments) {
-                    const uint32_t t0 = static_cast<uint32_t>(static_cast<uint64_t>(W.tiles) * seg / W.segments);
-                    const uint32_t t1 = static_cast<uint32_t>(static_cast<uint64_t>(W.tiles) * (seg + 1) / W.segments);
+                    const uint32_t t0 = static_cast<uint32_t>(static_cast<uint64_t>(q_tiles) * seg / W.segments);
+                    const uint32_t t1 = static_cast<uint32_t>(static_cast<uint64_t>(q_tiles) * (seg + 1) / W.segments);
                     const uint32_t nt = t1 - t0, bulk = nt * W.groups;
                     uint32_t v = 0;
                     if (lane == leader) v = atomicAdd(W.queue + seg, 1u);
@@ -1945,6 +1952,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kMa
                             item_units = 64;
                         }
                         tile += t0;
+                        if (MASK) tile = active[1 + tile];  // wave-uniform: a scalar load
                         item_txy = (tile % W.tiles_x) | ((tile / W.tiles_x) << 16);
                         break;
                     }
@@ -2221,6 +2229,189 @@ __global__ __launch_bounds__(256) void scale_kernel(const double* __restrict__ s
                                                     uint64_t n, double inv_done) {
     const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (i < n) out[i] = sum[i] * inv_done;
+}
+
+// ---- adaptive sampling: block state, the active-tile list, the masked accumulate, the update ----
+// A block is a kTileW x kTileH tile of the owned rows; blocks[b], b = by * ceil(w / kTileW) + bx,
+// holds the samples accumulated in the block's pixels, and CRT_BLOCK_STOPPED.
+static_assert(kTileW == CRT_BLOCK_W && kTileH == CRT_BLOCK_H, "a block is the render kernel's tile");
+
+// The block of band tile `tile` (tile-major in the band): the band starts at a tile boundary.
+__device__ __forceinline__ uint32_t band_block(const Work& W, uint32_t tile, uint32_t frame_tiles_x) {
+    const uint32_t tx = tile % W.tiles_x, ty = tile / W.tiles_x;
+    return (W.k0 / kTileH + ty) * frame_tiles_x + W.col0 / kTileW + tx;
+}
+
+// The band's tiles whose block word equals `first`, in tile-major order: active[0] = their number,
+// active[1 + i] = the i-th one's band tile. One block of 1024 threads takes 1024 tiles a round:
+// every wave counts its tiles with a ballot, the waves' counts are prefix-summed through LDS, and
+// a lane writes at (round base + its wave's offset + the set bits below it): ordered compaction,
+// so adjacent list entries are adjacent tiles. It also zeroes the render kernel's queue counters.
+constexpr uint32_t kListThreads = 1024;
+__global__ __launch_bounds__(kListThreads) void active_list_kernel(const uint32_t* __restrict__ blocks, Work W,
+                                                                   uint32_t frame_tiles_x, uint32_t first,
+                                                                   uint32_t* __restrict__ active) {
+    __shared__ uint32_t wave_count[kListThreads / 64];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t base = 0;
+    for (uint32_t t0 = 0; t0 < W.tiles; t0 += kListThreads) {
+        const uint32_t tile = t0 + threadIdx.x;
+        const bool on = tile < W.tiles && blocks[band_block(W, tile, frame_tiles_x)] == first;
+        const uint64_t m = __ballot(on);
+        if (lane == 0) wave_count[wave] = static_cast<uint32_t>(__popcll(m));
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (uint32_t v = 0; v < kListThreads / 64; ++v) {
+            const uint32_t c = wave_count[v];
+            if (v < wave) before += c;
+            all += c;
+        }
+        if (on) {
+            const uint32_t below = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32),
+                                                             __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
+            active[1 + base + before + below] = tile;
+        }
+        base += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) active[0] = base;
+    if (threadIdx.x < 8) W.queue[threadIdx.x] = 0;  // the draw's queue counters, one per segment
+}
+
+// accumulate_kernel for a masked pass: one wave per band tile, lane = tile pixel. A tile whose
+// block word equals the pass's first sample was rendered: its pixels get accumulate_kernel's
+// additions, in its order, and the word becomes `end`. Any other tile was skipped: a pass from
+// sample 0 zeroes its pixels (sum, noise, out); a later one leaves sum and noise alone and writes
+// out = sum * (1 / (double)n), n = the block's own count (0 when n = 0). Only lane 0 touches the
+// block word. partial == nullptr (W.s0 = ~0u, which no word equals): the out of every tile only,
+// the frame of an adaptive render that ends between previews.
+__global__ __launch_bounds__(256) void accumulate_masked_kernel(const double* __restrict__ partial,
+                                                                double* __restrict__ sum, double* __restrict__ noise,
+                                                                double* __restrict__ out, uint32_t* __restrict__ blocks,
+                                                                Work W, uint32_t w, uint32_t frame_tiles_x,
+                                                                uint32_t full_chunks, uint32_t end, double inv_done) {
+    const uint32_t tile = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (tile >= W.tiles) return;  // wave-uniform
+    const uint32_t b = band_block(W, tile, frame_tiles_x);
+    uint32_t word = 0;
+    if (lane == 0) word = blocks[b];
+    word = __shfl(word, 0);
+    const uint32_t col_l = (tile % W.tiles_x) * kTileW + lane % kTileW, k_l = (tile / W.tiles_x) * kTileH + lane / kTileW;
+    const bool inside = col_l < W.bw && k_l < W.bh;
+    const uint32_t k = W.k0 + k_l, col = W.col0 + col_l;
+    const size_t pix = inside ? static_cast<size_t>(W.packed ? k : owned_row(W, k)) * w + col : 0;
+    if (word != W.s0) {  // skipped
+        if (!inside) return;
+        if (W.s0 == 0) {
+            sum[pix * 3 + 0] = 0;
+            sum[pix * 3 + 1] = 0;
+            sum[pix * 3 + 2] = 0;
+            if (noise) {
+                noise[pix * 2 + 0] = 0;
+                noise[pix * 2 + 1] = 0;
+            }
+            if (out) {
+                out[pix * 3 + 0] = 0;
+                out[pix * 3 + 1] = 0;
+                out[pix * 3 + 2] = 0;
+            }
+        } else if (out) {
+            const uint32_t n = word & ~CRT_BLOCK_STOPPED;
+            const double inv = 1 / static_cast<double>(n);
+            out[pix * 3 + 0] = n ? sum[pix * 3 + 0] * inv : 0.0;
+            out[pix * 3 + 1] = n ? sum[pix * 3 + 1] * inv : 0.0;
+            out[pix * 3 + 2] = n ? sum[pix * 3 + 2] * inv : 0.0;
+        }
+        return;
+    }
+    if (lane == 0) blocks[b] = end;
+    if (!inside) return;
+    const uint64_t i = static_cast<uint64_t>(k_l) * W.bw + col_l;
+    const size_t plane = static_cast<size_t>(W.bh) * W.bw * 3;
+    const bool fresh = W.s0 == 0;
+    double r, g, bl;
+    if (fresh) {
+        r = partial[i * 3 + 0];
+        g = partial[i * 3 + 1];
+        bl = partial[i * 3 + 2];
+    } else {
+        r = sum[pix * 3 + 0];
+        g = sum[pix * 3 + 1];
+        bl = sum[pix * 3 + 2];
+    }
+    double t = 0, q = 0;
+    if (noise && !fresh) {
+        t = noise[pix * 2 + 0];
+        q = noise[pix * 2 + 1];
+    }
+    for (uint32_t c = 0; c < W.chunks; ++c) {
+        const double pr = partial[c * plane + i * 3 + 0], pg = partial[c * plane + i * 3 + 1],
+                     pb = partial[c * plane + i * 3 + 2];
+        if (c > 0 || !fresh) {
+            r = r + pr;
+            g = g + pg;
+            bl = bl + pb;
+        }
+        if (c < full_chunks) {
+            const double y = (pr + pg) + pb;
+            t = t + y;
+            q = q + y * y;
+        }
+    }
+    sum[pix * 3 + 0] = r;
+    sum[pix * 3 + 1] = g;
+    sum[pix * 3 + 2] = bl;
+    if (noise) {
+        noise[pix * 2 + 0] = t;
+        noise[pix * 2 + 1] = q;
+    }
+    if (out) {
+        out[pix * 3 + 0] = r * inv_done;
+        out[pix * 3 + 1] = g * inv_done;
+        out[pix * 3 + 2] = bl * inv_done;
+    }
+}
+
+// crt_adaptive_update: one wave per block of the owned rows (W: owned_rows and the tiling; w: the
+// image width), lane = block pixel. A block whose word equals samples_done sums its pixels' se and
+// m (noise_stage1_kernel's formulas; a lane off the image adds 0) over a butterfly of the 64 lanes:
+// the order of the additions depends on the lane numbers only. may_stop = K >= 2 and the sample
+// floor is reached. The block stops when sum se <= threshold * sum m (no division: an all-black
+// block stops, a NaN never does); else it counts as active.
+__global__ __launch_bounds__(256) void adaptive_update_kernel(const double* __restrict__ noise,
+                                                              uint32_t* __restrict__ blocks, Work W, uint32_t w,
+                                                              uint32_t n_blocks, uint32_t samples_done, double K,
+                                                              double L, double threshold, uint32_t may_stop,
+                                                              uint32_t* __restrict__ n_active) {
+    const uint32_t b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (b >= n_blocks) return;  // wave-uniform
+    uint32_t word = 0;
+    if (lane == 0) word = blocks[b];
+    word = __shfl(word, 0);
+    if (word != samples_done) return;
+    bool stop = false;
+    if (may_stop) {
+        const uint32_t tiles_x = (w + kTileW - 1) / kTileW;
+        const uint32_t col = (b % tiles_x) * kTileW + lane % kTileW, k = (b / tiles_x) * kTileH + lane / kTileW;
+        double se = 0, mean = 0;
+        if (col < w && k < W.owned_rows) {
+            const size_t pix = static_cast<size_t>(W.packed ? k : owned_row(W, k)) * w + col;
+            const double t = noise[pix * 2 + 0], q = noise[pix * 2 + 1];
+            const double m = t / (K * L);
+            const double var = q / (L * L) - K * m * m;
+            se = sqrt(fmax(0.0, var) / (K * (K - 1)));
+            mean = m;
+        }
+        for (int d = 1; d < 64; d <<= 1) {
+            se = se + __shfl_xor(se, d);
+            mean = mean + __shfl_xor(mean, d);
+        }
+        stop = se <= threshold * mean;
+    }
+    if (lane == 0) {
+        if (stop) blocks[b] = word | CRT_BLOCK_STOPPED;
+        else atomicAdd(n_active, 1u);
+    }
 }
 
 // Noise figure of a progressive render (crt_noise_estimate). A pixel's K full chunk sums y_c (L
@@ -2685,6 +2876,47 @@ uint32_t sample_chunk_len(uint32_t spp) {
     return std::max<uint32_t>(CRT_CHUNK_MIN, (spp + 191) / 192);
 }
 
+// Scratch of pass renders (partial sums, queue, active list, the update's counter) comes from a
+// memory pool of the library's own, one per device, that never gives memory back: the process's
+// default pool is left alone. The default pool releases unused memory at every synchronization
+// (release threshold 0), and a render in passes synchronizes between passes, so every pass drew
+// its scratch from memory released and mapped again. In a C++ process on the ROCm 7.0 runtime (not
+// under PyTorch's bundled runtime) whole tiles of a later pass then came out as zeros:
+// crt_render_progressive in three passes of four samples lost one pass in most tiles from the
+// second render of a process on (tests/cpp/passes_e2e.cpp), with every kernel serialized too; why
+// was not found. With scratch that stays mapped no pass is lost, whatever the host does with the
+// default pool. The pool holds the largest scratch any pass needed (at most the partial-sum
+// budget) until the process ends. One-shot renders allocate as before. A pool that cannot be
+// created is an error: pass renders do not fall back to the default pool.
+static int pass_pool(int device, hipMemPool_t* out) {
+    static std::mutex mu;
+    static hipMemPool_t pools[kMaxDevices] = {};
+    std::lock_guard<std::mutex> lk(mu);
+    if (device < 0 || device >= kMaxDevices) return fail(CRT_E_NODEVICE, "pass scratch pool: device out of range");
+    if (!pools[device]) {
+        hipMemPoolProps props{};
+        props.allocType = hipMemAllocationTypePinned;
+        props.handleTypes = hipMemHandleTypeNone;
+        props.location.type = hipMemLocationTypeDevice;
+        props.location.id = device;
+        hipMemPool_t pool = nullptr;
+        uint64_t keep = UINT64_MAX;
+        hipError_t e = hipMemPoolCreate(&pool, &props);
+        if (e == hipSuccess) {
+            e = hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
+            if (e != hipSuccess) (void)hipMemPoolDestroy(pool);
+        }
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(CRT_E_HIP, std::string("pass scratch pool on device ") + std::to_string(device) + ": " +
+                                       hipGetErrorString(e));
+        }
+        pools[device] = pool;
+    }
+    *out = pools[device];
+    return CRT_OK;
+}
+
 template <typename SE, bool GSTACK, bool LSCENE, int PM, bool W5 = false>
 static int launch_render(const crt_scene* s, int device, const crt_camera* cam, const dev::Work& w0,
                          size_t lds, double* d_rgb, hipStream_t stream, crt_render_stats* count_stats,
@@ -2702,7 +2934,10 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
         lds = W.lds_inv64 + kInvBytes;
     }
     constexpr int kThreads = dev::kBlock;
-    const void* kfn = reinterpret_cast<const void*>(dev::render_kernel<SE, GSTACK, LSCENE, false, PM, W5>);
+    // a masked pass (adaptive sampling) launches the MASK instance over the active tiles' list
+    const bool masked = pass && pass->blocks;
+    const void* kfn = masked ? reinterpret_cast<const void*>(dev::render_kernel<SE, GSTACK, LSCENE, false, PM, W5, true>)
+                             : reinterpret_cast<const void*>(dev::render_kernel<SE, GSTACK, LSCENE, false, PM, W5>);
     const uint64_t pixels = static_cast<uint64_t>(W.owned_rows) * cam->image_w;
     // Sample chunks: a function of spp ONLY, so every pixel's sum is grouped identically whatever
     // the tiling / number of GPUs / lane schedule / band split (bit-identical frames for 1..N
@@ -2718,6 +2953,14 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
     // chunks that hold chunk_len samples (all but a job's ragged last one) feed the noise state.
     uint32_t full_chunks = 0;
     double inv_done = 0;
+    hipMemPool_t pool = nullptr;  // pass renders: the library's own pool (pass_pool)
+    if (pass) {
+        const int rc = pass_pool(device, &pool);
+        if (rc) return rc;
+    }
+    auto scratch = [&](void** p, size_t bytes) {
+        return pool ? hipMallocFromPoolAsync(p, bytes, pool, stream) : hipMallocAsync(p, bytes, stream);
+    };
     if (pass) {
         const uint32_t end = pass->first + pass->count;
         W.s0 = pass->first;
@@ -2759,18 +3002,21 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
     const uint64_t band_px = std::min<uint64_t>(static_cast<uint64_t>(bx) * dev::kTileW, cam->image_w) *
                              std::min<uint64_t>(static_cast<uint64_t>(by) * dev::kTileH, W.owned_rows);
     if (!count)
-        HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&partial), band_px * 3 * W.chunks * sizeof(double), stream));
+        HIP_TRY(scratch(reinterpret_cast<void**>(&partial), band_px * 3 * W.chunks * sizeof(double)));
     if (GSTACK) {
         size_t bytes = static_cast<size_t>(s->depth + 4) * resident * dev::kBlock * sizeof(SE);  // + 3 levels below
-        HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&gstack), bytes, stream));
+        HIP_TRY(scratch(reinterpret_cast<void**>(&gstack), bytes));
     }
     if (count) {
         HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&ctr), sizeof(dev::Counters), stream));
         HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(dev::Counters), stream));
     }
     uint32_t* queue = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&queue), 256, stream));
+    HIP_TRY(scratch(reinterpret_cast<void**>(&queue), 256));
     W.queue = queue;
+    uint32_t* active = nullptr;  // masked pass: a band's active tiles (active_list_kernel)
+    if (masked)
+        HIP_TRY(scratch(reinterpret_cast<void**>(&active), (static_cast<size_t>(bx) * by + 1) * sizeof(uint32_t)));
     dev::SceneView S = view_of(c);
     dev::CamView C = cam_view(cam);
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -2788,8 +3034,11 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
             W.tiles_x = (W.bw + dev::kTileW - 1) / dev::kTileW;
             W.tiles_y = (W.bh + dev::kTileH - 1) / dev::kTileH;
             W.tiles = W.tiles_x * W.tiles_y;
+            // the tiles the grid and the items are sized for: the band's, or what the caller of a
+            // masked pass expects to be active (the kernel bounds itself by the true number)
+            const uint64_t q_tiles = masked && pass->hint ? std::min<uint64_t>(pass->hint, W.tiles) : W.tiles;
             const uint64_t blocks = std::max<uint64_t>(
-                1, std::min<uint64_t>(resident, (static_cast<uint64_t>(W.tiles) * W.chunks + kWavesPerBlock - 1) / kWavesPerBlock));
+                1, std::min<uint64_t>(resident, (q_tiles * W.chunks + kWavesPerBlock - 1) / kWavesPerBlock));
             // Items: bulk items of K chunks for the first part of each tile's chunks, then the
             // rest in one-chunk items at the end of the queue (CRT_TAIL_CHUNKS), so the grid
             // drains on small items; a wave's lanes cross from item to item without waiting
@@ -2802,7 +3051,7 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
             // 36.9 -> 36.7 ms, N = 4 (p = 92) 19.7 -> 19.0, N = 8 (p = 46, K = 3 with an 81-chunk
             // tail) 10.34-10.49 -> 10.17-10.31 against the earlier K = p / 30 with a 1/9 tail;
             // N = 1 (7, 13 of 125 chunks) unchanged. (CRT_ITEM_CHUNKS, CRT_TAIL_CHUNKS override.)
-            const uint64_t per_lane = static_cast<uint64_t>(W.tiles) * W.chunks / (blocks * kWavesPerBlock);
+            const uint64_t per_lane = q_tiles * W.chunks / (blocks * kWavesPerBlock);
             const uint32_t k_auto = per_lane >= 60 ? static_cast<uint32_t>(std::min<uint64_t>(7, per_lane / 15)) : 3u;
             W.item_chunks = std::max<uint32_t>(1, knob("CRT_ITEM_CHUNKS", k_auto));
             const uint32_t tail_auto = static_cast<uint32_t>(std::max<uint64_t>(
@@ -2820,7 +3069,8 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
             // serves the rays of one region of the band (config 4: 163.5 vs 166.2 ms); LDS scenes
             // keep one queue (config 2: 88.5 vs 89.0 ms with eight). CRT_XCD_QUEUES=0/1 forces.
             W.segments = knob("CRT_XCD_QUEUES", LSCENE ? 0 : 1) ? 8u : 1u;
-            HIP_TRY(hipMemsetAsync(queue, 0, 8 * sizeof(uint32_t), stream));
+            // a masked pass has no memset: active_list_kernel zeroes W.queue[0..7] (W is set up to here)
+            if (!masked) HIP_TRY(hipMemsetAsync(queue, 0, 8 * sizeof(uint32_t), stream));
 #if CRT_WATCHDOG
             {
                 void* wd = nullptr;
@@ -2830,11 +3080,23 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
 #endif
             if (count) {
                 hipLaunchKernelGGL((dev::render_kernel<SE, GSTACK, LSCENE, true, PM, W5>), dim3(static_cast<uint32_t>(blocks)),
-                                   dim3(dev::kBlock), lds, stream, S, C, W, partial, gstack, ctr);
+                                   dim3(dev::kBlock), lds, stream, S, C, W, partial, gstack, ctr, nullptr);
+                HIP_TRY(hipGetLastError());
+            } else if (masked) {
+                const uint32_t ftx = static_cast<uint32_t>(tiles_x_all);
+                hipLaunchKernelGGL(dev::active_list_kernel, dim3(1), dim3(dev::kListThreads), 0, stream, pass->blocks, W, ftx,
+                                   pass->first, active);
+                HIP_TRY(hipGetLastError());
+                hipLaunchKernelGGL((dev::render_kernel<SE, GSTACK, LSCENE, false, PM, W5, true>), dim3(static_cast<uint32_t>(blocks)),
+                                   dim3(dev::kBlock), lds, stream, S, C, W, partial, gstack, ctr, active);
+                HIP_TRY(hipGetLastError());
+                hipLaunchKernelGGL(dev::accumulate_masked_kernel, dim3((W.tiles + 3) / 4), dim3(256), 0, stream, partial,
+                                   pass->sum, pass->noise, d_rgb, pass->blocks, W, cam->image_w, ftx, full_chunks,
+                                   pass->first + pass->count, inv_done);
                 HIP_TRY(hipGetLastError());
             } else {
                 hipLaunchKernelGGL((dev::render_kernel<SE, GSTACK, LSCENE, false, PM, W5>), dim3(static_cast<uint32_t>(blocks)),
-                                   dim3(dev::kBlock), lds, stream, S, C, W, partial, gstack, ctr);
+                                   dim3(dev::kBlock), lds, stream, S, C, W, partial, gstack, ctr, nullptr);
                 HIP_TRY(hipGetLastError());
                 const uint64_t rb = (static_cast<uint64_t>(W.bw) * W.bh + 255) / 256;
                 if (pass)
@@ -2850,6 +3112,7 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
     if (count) HIP_TRY(hipEventRecord(e1, stream));
     if (partial) HIP_TRY(hipFreeAsync(partial, stream));
     HIP_TRY(hipFreeAsync(queue, stream));
+    if (active) HIP_TRY(hipFreeAsync(active, stream));
     if (gstack) HIP_TRY(hipFreeAsync(gstack, stream));
     if (count) {
         dev::Counters h{};
@@ -3405,8 +3668,11 @@ int device_noise_estimate(int device, const double* d_noise, size_t pixels, uint
     if (K < 2 || pixels == 0) return CRT_OK;
     DeviceGuard g(device);
     hipStream_t st = static_cast<hipStream_t>(stream);
+    hipMemPool_t pool = nullptr;  // a pass render's companion: the same scratch pool (pass_pool)
+    rc = pass_pool(device, &pool);
+    if (rc) return rc;
     double* d_tmp = nullptr;  // kNoiseBlocks block results, then the two sums
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_tmp), (dev::kNoiseBlocks + 1) * 2 * sizeof(double), st));
+    HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&d_tmp), (dev::kNoiseBlocks + 1) * 2 * sizeof(double), pool, st));
     double h[2] = {0, 0};
     hipLaunchKernelGGL(dev::noise_stage1_kernel, dim3(dev::kNoiseBlocks), dim3(256), 0, st, d_noise,
                        static_cast<uint64_t>(pixels), static_cast<double>(K), static_cast<double>(L), d_tmp);
@@ -3571,6 +3837,247 @@ int render_progressive(crt_scene* s, const crt_camera* cam, int num_devices, uin
         (void)hipFree(frame);
     }
     if (samples_done) *samples_done = done;
+    return rc;
+}
+
+// ---- adaptive sampling (host side) ---------------------------------------------------------
+bool adaptive_tiling_ok(const crt_tiling* t) {
+    return !t || t->tile_count == 1 || (t->row_block != 0 && t->row_block % dev::kTileH == 0);
+}
+
+// the tiling part of a Work (owned_row, packed) for the kernels that address pixels by owned row
+static int tiling_work(const crt_camera* cam, const crt_tiling* t, dev::Work& W) {
+    crt_tiling tl{1, 1, 0, 0};
+    if (t) tl = *t;
+    if (tl.flags & ~CRT_TILING_PACKED) return fail(CRT_E_INVALID, "unknown tiling flags");
+    if (tl.row_block == 0 || tl.tile_count == 0 || tl.tile_index >= tl.tile_count)
+        return fail(CRT_E_INVALID, "bad tiling");
+    W = dev::Work{};
+    W.row_block = tl.row_block;
+    W.tile_count = tl.tile_count;
+    W.tile_index = tl.tile_index;
+    W.owned_rows = count_owned(cam->image_h, tl.row_block, tl.tile_count, tl.tile_index);
+    W.packed = (tl.flags & CRT_TILING_PACKED) ? 1u : 0u;
+    W.rb_shift = 32;
+    for (uint32_t sh = 0; sh < 31; ++sh)
+        if ((1u << sh) == W.row_block) W.rb_shift = sh;
+    return CRT_OK;
+}
+
+static uint32_t block_count(uint32_t w, uint32_t rows) {
+    return ((w + dev::kTileW - 1) / dev::kTileW) * ((rows + dev::kTileH - 1) / dev::kTileH);
+}
+
+int device_adaptive_update(int device, const crt_camera* cam, const crt_tiling* t, const double* d_noise,
+                           uint32_t* d_blocks, uint32_t samples_done, double threshold, uint32_t min_samples,
+                           uint32_t* active_blocks, void* stream) {
+    int rc = check_device(device);
+    if (rc) return rc;
+    dev::Work W;
+    rc = tiling_work(cam, t, W);
+    if (rc) return rc;
+    *active_blocks = 0;
+    const uint32_t nb = block_count(cam->image_w, W.owned_rows);
+    if (nb == 0) return CRT_OK;
+    const uint32_t N = cam->samples_per_pixel, L = sample_chunk_len(N), K = samples_done / L;
+    const uint32_t may_stop = (K >= 2 && samples_done >= min_samples && min_samples < N) ? 1u : 0u;
+    DeviceGuard g(device);
+    hipMemPool_t pool = nullptr;
+    rc = pass_pool(device, &pool);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    uint32_t* d_n = nullptr;
+    HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&d_n), sizeof(uint32_t), pool, st));
+    hipError_t e = hipMemsetAsync(d_n, 0, sizeof(uint32_t), st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(dev::adaptive_update_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, d_noise, d_blocks, W,
+                           cam->image_w, nb, samples_done, static_cast<double>(K), static_cast<double>(L), threshold,
+                           may_stop, d_n);
+        e = hipGetLastError();
+    }
+    uint32_t h = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, d_n, sizeof h, hipMemcpyDeviceToHost, st);
+    (void)hipFreeAsync(d_n, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(CRT_E_HIP, std::string("adaptive update: ") + hipGetErrorString(e));
+    *active_blocks = h;
+    return CRT_OK;
+}
+
+// crt_render_adaptive: render_progressive's layout (rows dealt in 4-row blocks, so a device's
+// blocks are blocks of the frame; packed running sums and noise state per device; the gather into
+// device 0; CRT_EMULATE_DEVICES) with a block state per device: every step is one masked pass and
+// one update on every device, and a device's last active count is its next pass's hint. The frame
+// is each block's sum times 1 / its own count: written by the masked passes with
+// CRT_PROGRESS_PREVIEW, else once at the end (accumulate_masked_kernel without partial sums).
+int render_adaptive(crt_scene* s, const crt_camera* cam, int num_devices, const crt_adaptive_params* prm,
+                    crt_adaptive_fn fn, void* user, double* h_rgb, uint32_t* h_block_samples,
+                    uint64_t* samples_rendered) {
+    int avail = 0;
+    if (hipGetDeviceCount(&avail) != hipSuccess || avail == 0)
+        return fail(CRT_E_NODEVICE, "no HIP device visible (the render path has no CPU fallback)");
+    if (num_devices <= 0) num_devices = avail;
+    num_devices = std::min(num_devices, std::min(avail, kMaxDevices));
+    bool emulate = false;
+    if (const char* e = std::getenv("CRT_EMULATE_DEVICES")) {
+        num_devices = std::max(1, std::min(std::atoi(e), 64));
+        emulate = true;
+    }
+    const int n = num_devices;
+    auto phys = [&](int d) { return emulate ? 0 : d; };
+    const size_t W = cam->image_w, H = cam->image_h;
+    const uint32_t N = cam->samples_per_pixel, L = sample_chunk_len(N);
+    const uint32_t rb = 4;
+    const bool want_preview = (prm->flags & CRT_PROGRESS_PREVIEW) != 0;
+    uint64_t per_pass = prm->samples_per_pass ? prm->samples_per_pass : std::max<uint32_t>(1, N / 10);
+    per_pass = (per_pass + L - 1) / L * L;
+    const int n_phys = emulate ? 1 : n;
+    for (int d = 0; d < n_phys; ++d) {
+        const int rc = device_upload(s, d);
+        if (rc) return rc;
+    }
+    const uint32_t tiles_x = static_cast<uint32_t>((W + dev::kTileW - 1) / dev::kTileW);
+    const uint32_t total_blocks = block_count(cam->image_w, cam->image_h);
+    std::vector<double*> sums(n, nullptr), noise(n, nullptr), bufs(n, nullptr);
+    std::vector<uint32_t*> blocks(n, nullptr);
+    std::vector<uint32_t> rows(n, 0), nblk(n, 0), hint(n, 0);
+    std::vector<hipStream_t> streams(n, nullptr);
+    std::vector<hipEvent_t> ev(n, nullptr);
+    double* frame = nullptr;
+    int rc = CRT_OK;
+    for (int d = 0; d < n && rc == CRT_OK; ++d) {
+        DeviceGuard g(phys(d));
+        rows[d] = count_owned(cam->image_h, rb, static_cast<uint32_t>(n), static_cast<uint32_t>(d));
+        nblk[d] = block_count(cam->image_w, rows[d]);
+        const size_t px = std::max<size_t>(1, static_cast<size_t>(rows[d]) * W);
+        const size_t bb = std::max<size_t>(1, nblk[d]) * sizeof(uint32_t);
+        if (hipStreamCreateWithFlags(&streams[d], hipStreamNonBlocking) != hipSuccess ||
+            hipMalloc(&sums[d], px * 3 * sizeof(double)) != hipSuccess ||
+            hipMalloc(&bufs[d], px * 3 * sizeof(double)) != hipSuccess ||
+            hipMalloc(&noise[d], px * 2 * sizeof(double)) != hipSuccess || hipMalloc(&blocks[d], bb) != hipSuccess ||
+            hipMemsetAsync(blocks[d], 0, bb, streams[d]) != hipSuccess || hipEventCreate(&ev[d]) != hipSuccess) {
+            (void)hipGetLastError();
+            rc = fail(CRT_E_HIP, "adaptive render: per-device setup failed on device " + std::to_string(phys(d)));
+        }
+    }
+    if (rc == CRT_OK) {
+        DeviceGuard g(0);
+        if (hipMalloc(&frame, std::max<size_t>(1, H * W) * 3 * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            rc = fail(CRT_E_HIP, "adaptive render: frame buffer");
+        }
+    }
+    auto gather = [&]() -> int {
+        DeviceGuard g(0);
+        for (int d = 0; d < n; ++d) {
+            if (!emulate && d > 0) enable_peer_once(0, d);
+            {
+                DeviceGuard gd(phys(d));
+                if (hipEventRecord(ev[d], streams[d]) != hipSuccess) return fail(CRT_E_HIP, "adaptive render: event");
+            }
+            if (d > 0 && hipStreamWaitEvent(streams[0], ev[d], 0) != hipSuccess)
+                return fail(CRT_E_HIP, "adaptive render: gather wait failed");
+            const hipError_t e = gather_packed(reinterpret_cast<char*>(frame), reinterpret_cast<const char*>(bufs[d]), H, rb,
+                                               n, d, W * 3 * sizeof(double), streams[0]);
+            if (e != hipSuccess)
+                return fail(CRT_E_HIP, std::string("adaptive render: gather from device ") + std::to_string(d) + ": " +
+                                           hipGetErrorString(e));
+        }
+        hipError_t e = hipMemcpyAsync(h_rgb, frame, H * W * 3 * sizeof(double), hipMemcpyDeviceToHost, streams[0]);
+        if (e == hipSuccess) e = hipStreamSynchronize(streams[0]);
+        if (e != hipSuccess) return fail(CRT_E_HIP, std::string("adaptive render: ") + hipGetErrorString(e));
+        return CRT_OK;
+    };
+    uint32_t done = 0;
+    bool have_frame = false;
+    while (rc == CRT_OK && done < N) {
+        const uint32_t count = static_cast<uint32_t>(std::min<uint64_t>(per_pass, N - done));
+        have_frame = want_preview && fn;
+        for (int d = 0; d < n && rc == CRT_OK; ++d) {
+            if (!rows[d]) continue;
+            crt_tiling t{rb, static_cast<uint32_t>(n), static_cast<uint32_t>(d), CRT_TILING_PACKED};
+            const RenderPass pass{done, count, sums[d], noise[d], blocks[d], hint[d]};
+            rc = device_render(s, phys(d), cam, &t, have_frame ? bufs[d] : nullptr, streams[d], nullptr, &pass);
+        }
+        if (rc != CRT_OK) break;
+        done += count;
+        uint32_t active = 0;
+        for (int d = 0; d < n && rc == CRT_OK; ++d) {  // synchronizes the device's stream
+            if (!rows[d]) continue;
+            crt_tiling t{rb, static_cast<uint32_t>(n), static_cast<uint32_t>(d), CRT_TILING_PACKED};
+            uint32_t a = 0;
+            rc = device_adaptive_update(phys(d), cam, &t, noise[d], blocks[d], done, prm->threshold, prm->min_samples, &a,
+                                        streams[d]);
+            hint[d] = std::max(1u, a);
+            active += a;
+        }
+        if (rc != CRT_OK) break;
+        if (have_frame) rc = gather();
+        if (rc != CRT_OK) break;
+        if (fn && fn(user, done, N, active, total_blocks, want_preview ? h_rgb : nullptr) != 0) break;
+        if (active == 0) break;
+    }
+    // ended between previews: every block's sum times 1 / its own count
+    if (rc == CRT_OK && !have_frame) {
+        for (int d = 0; d < n && rc == CRT_OK; ++d) {
+            if (!rows[d]) continue;
+            DeviceGuard g(phys(d));
+            crt_tiling t{rb, static_cast<uint32_t>(n), static_cast<uint32_t>(d), CRT_TILING_PACKED};
+            dev::Work Wk;
+            rc = tiling_work(cam, &t, Wk);
+            if (rc) break;
+            Wk.bw = cam->image_w;
+            Wk.bh = rows[d];
+            Wk.tiles_x = tiles_x;
+            Wk.tiles_y = (rows[d] + dev::kTileH - 1) / dev::kTileH;
+            Wk.tiles = nblk[d];
+            Wk.s0 = ~0u;  // no block word equals it: every tile takes the skipped branch
+            hipLaunchKernelGGL(dev::accumulate_masked_kernel, dim3((nblk[d] + 3) / 4), dim3(256), 0, streams[d], nullptr,
+                               sums[d], nullptr, bufs[d], blocks[d], Wk, cam->image_w, tiles_x, 0u, 0u, 0.0);
+            if (hipGetLastError() != hipSuccess) rc = fail(CRT_E_HIP, "adaptive render: frame kernel launch");
+        }
+        if (rc == CRT_OK) rc = gather();
+    }
+    // the frame's block counts: device d's block row j is block row (j / (rb / 4) * n + d) * (rb / 4)
+    // + j % (rb / 4) of the frame (rb = 4: one block row per row block)
+    uint64_t rendered = 0;
+    if (rc == CRT_OK) {
+        std::vector<uint32_t> hb;
+        for (int d = 0; d < n && rc == CRT_OK; ++d) {
+            if (!nblk[d]) continue;
+            DeviceGuard g(phys(d));
+            hb.resize(nblk[d]);
+            if (hipMemcpy(hb.data(), blocks[d], nblk[d] * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) {
+                (void)hipGetLastError();
+                rc = fail(CRT_E_HIP, "adaptive render: block state copy");
+                break;
+            }
+            for (uint32_t j = 0; j * dev::kTileH < rows[d]; ++j) {
+                const uint32_t fy = j * static_cast<uint32_t>(n) + static_cast<uint32_t>(d);
+                const uint64_t bh = std::min<uint64_t>(dev::kTileH, rows[d] - j * dev::kTileH);
+                for (uint32_t bx = 0; bx < tiles_x; ++bx) {
+                    const uint32_t cnt = hb[j * tiles_x + bx] & ~CRT_BLOCK_STOPPED;
+                    if (h_block_samples) h_block_samples[static_cast<size_t>(fy) * tiles_x + bx] = cnt;
+                    rendered += cnt * bh * std::min<uint64_t>(dev::kTileW, W - static_cast<uint64_t>(bx) * dev::kTileW);
+                }
+            }
+        }
+    }
+    for (int d = 0; d < n; ++d) {
+        DeviceGuard g(phys(d));
+        if (streams[d]) (void)hipStreamSynchronize(streams[d]);
+        if (sums[d]) (void)hipFree(sums[d]);
+        if (noise[d]) (void)hipFree(noise[d]);
+        if (bufs[d]) (void)hipFree(bufs[d]);
+        if (blocks[d]) (void)hipFree(blocks[d]);
+        if (streams[d]) (void)hipStreamDestroy(streams[d]);
+        if (ev[d]) (void)hipEventDestroy(ev[d]);
+    }
+    if (frame) {
+        DeviceGuard g(0);
+        (void)hipFree(frame);
+    }
+    if (samples_rendered) *samples_rendered = rendered;
     return rc;
 }
 

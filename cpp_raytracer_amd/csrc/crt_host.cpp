@@ -1200,27 +1200,98 @@ int crt_render_async(const crt_scene* s, int device, const crt_camera* cam,
 
 uint32_t crt_sample_chunk_len(uint32_t samples_per_pixel) { return sample_chunk_len(samples_per_pixel); }
 
+// the rules of a pass (crt_render_pass_async, crt_render_pass_masked_async): CRT_OK, or the
+// failure naming the broken rule
+static int check_pass(const char* fn, const crt_scene* s, const crt_camera* cam, uint32_t first_sample,
+                      uint32_t num_samples, const double* d_sum) {
+    const std::string who = std::string(fn) + ": ";
+    if (!s || !cam) return fail(CRT_E_INVALID, who + "null argument");
+    if (!d_sum) return fail(CRT_E_INVALID, who + "d_sum is null (the running sums are required)");
+    const uint32_t N = cam->samples_per_pixel, L = sample_chunk_len(N);
+    const std::string len = " (chunk length " + std::to_string(L) + " at " + std::to_string(N) + " spp)";
+    if (num_samples == 0) return fail(CRT_E_INVALID, who + "num_samples is 0");
+    if (first_sample % L != 0)
+        return fail(CRT_E_INVALID, who + "first_sample " + std::to_string(first_sample) +
+                                       " is not a multiple of the chunk length" + len);
+    const uint64_t end = static_cast<uint64_t>(first_sample) + num_samples;
+    if (end > N)
+        return fail(CRT_E_INVALID, who + "first_sample + num_samples = " + std::to_string(end) +
+                                       " exceeds samples_per_pixel = " + std::to_string(N));
+    if (end != N && end % L != 0)
+        return fail(CRT_E_INVALID, who + "the pass ends at sample " + std::to_string(end) +
+                                       ", neither a multiple of the chunk length nor samples_per_pixel" + len);
+    return CRT_OK;
+}
+
 int crt_render_pass_async(const crt_scene* s, int device, const crt_camera* cam, const crt_tiling* tiling,
                           uint32_t first_sample, uint32_t num_samples, double* d_sum, double* d_noise,
                           double* d_rgb, void* stream) {
     clear_error();
-    if (!s || !cam) return fail(CRT_E_INVALID, "crt_render_pass_async: null argument");
-    if (!d_sum) return fail(CRT_E_INVALID, "crt_render_pass_async: d_sum is null (the running sums are required)");
-    const uint32_t N = cam->samples_per_pixel, L = sample_chunk_len(N);
-    const std::string len = " (chunk length " + std::to_string(L) + " at " + std::to_string(N) + " spp)";
-    if (num_samples == 0) return fail(CRT_E_INVALID, "crt_render_pass_async: num_samples is 0");
-    if (first_sample % L != 0)
-        return fail(CRT_E_INVALID, "crt_render_pass_async: first_sample " + std::to_string(first_sample) +
-                                       " is not a multiple of the chunk length" + len);
-    const uint64_t end = static_cast<uint64_t>(first_sample) + num_samples;
-    if (end > N)
-        return fail(CRT_E_INVALID, "crt_render_pass_async: first_sample + num_samples = " + std::to_string(end) +
-                                       " exceeds samples_per_pixel = " + std::to_string(N));
-    if (end != N && end % L != 0)
-        return fail(CRT_E_INVALID, "crt_render_pass_async: the pass ends at sample " + std::to_string(end) +
-                                       ", neither a multiple of the chunk length nor samples_per_pixel" + len);
+    const int rc = check_pass("crt_render_pass_async", s, cam, first_sample, num_samples, d_sum);
+    if (rc) return rc;
     const RenderPass pass{first_sample, num_samples, d_sum, d_noise};
     return device_render(s, device, cam, tiling, d_rgb, stream, nullptr, &pass);
+}
+
+size_t crt_block_count(uint32_t image_w, uint32_t owned_rows) {
+    return (static_cast<size_t>(image_w) + CRT_BLOCK_W - 1) / CRT_BLOCK_W *
+           ((static_cast<size_t>(owned_rows) + CRT_BLOCK_H - 1) / CRT_BLOCK_H);
+}
+
+static int check_adaptive_tiling(const char* fn, const crt_tiling* tiling) {
+    if (adaptive_tiling_ok(tiling)) return CRT_OK;
+    return fail(CRT_E_INVALID, std::string(fn) + ": adaptive sampling needs a tiling with tile_count == 1 or row_block a "
+                                                 "multiple of 4 (a rank's blocks must be blocks of the frame)");
+}
+
+int crt_render_pass_masked_async(const crt_scene* s, int device, const crt_camera* cam, const crt_tiling* tiling,
+                                 uint32_t first_sample, uint32_t num_samples, double* d_sum, double* d_noise,
+                                 double* d_rgb, uint32_t* d_blocks, uint32_t active_hint, void* stream) {
+    clear_error();
+    int rc = check_pass("crt_render_pass_masked_async", s, cam, first_sample, num_samples, d_sum);
+    if (rc) return rc;
+    if (!d_blocks) return fail(CRT_E_INVALID, "crt_render_pass_masked_async: d_blocks is null (the block state is required)");
+    if (first_sample + num_samples >= CRT_BLOCK_STOPPED)
+        return fail(CRT_E_INVALID, "crt_render_pass_masked_async: sample counts must stay below 2^31");
+    rc = check_adaptive_tiling("crt_render_pass_masked_async", tiling);
+    if (rc) return rc;
+    const RenderPass pass{first_sample, num_samples, d_sum, d_noise, d_blocks, active_hint};
+    return device_render(s, device, cam, tiling, d_rgb, stream, nullptr, &pass);
+}
+
+int crt_adaptive_update(int device, const crt_camera* cam, const crt_tiling* tiling, const double* d_noise,
+                        uint32_t* d_blocks, uint32_t samples_done, double threshold, uint32_t min_samples,
+                        uint32_t* active_blocks, void* stream) {
+    clear_error();
+    if (!cam || !d_noise || !d_blocks || !active_blocks) return fail(CRT_E_INVALID, "crt_adaptive_update: null argument");
+    if (!(threshold >= 0) || !std::isfinite(threshold))
+        return fail(CRT_E_INVALID, "crt_adaptive_update: threshold must be finite and >= 0");
+    if (samples_done > cam->samples_per_pixel)
+        return fail(CRT_E_INVALID, "crt_adaptive_update: samples_done exceeds samples_per_pixel");
+    if (samples_done != cam->samples_per_pixel && samples_done % sample_chunk_len(cam->samples_per_pixel) != 0)
+        return fail(CRT_E_INVALID, "crt_adaptive_update: samples_done = " + std::to_string(samples_done) +
+                                       " is not a pass boundary (a multiple of the chunk length, or samples_per_pixel)");
+    const int rc = check_adaptive_tiling("crt_adaptive_update", tiling);
+    if (rc) return rc;
+    return device_adaptive_update(device, cam, tiling, d_noise, d_blocks, samples_done, threshold, min_samples,
+                                  active_blocks, stream);
+}
+
+int crt_render_adaptive(crt_scene* s, const crt_camera* cam, int num_devices, const crt_adaptive_params* params,
+                        crt_adaptive_fn fn, void* user, double* h_rgb, uint32_t* h_block_samples,
+                        uint64_t* samples_rendered) {
+    clear_error();
+    if (samples_rendered) *samples_rendered = 0;
+    if (!s || !cam || !params || !h_rgb) return fail(CRT_E_INVALID, "crt_render_adaptive: null argument");
+    if (params->flags & ~CRT_PROGRESS_PREVIEW) return fail(CRT_E_INVALID, "crt_render_adaptive: unknown flags");
+    if (params->reserved != 0) return fail(CRT_E_INVALID, "crt_render_adaptive: params->reserved must be 0");
+    if (!(params->threshold >= 0) || !std::isfinite(params->threshold))
+        return fail(CRT_E_INVALID, "crt_render_adaptive: threshold must be finite and >= 0");
+    if (cam->samples_per_pixel == 0) return fail(CRT_E_INVALID, "crt_render_adaptive: samples_per_pixel is 0");
+    if (cam->samples_per_pixel >= CRT_BLOCK_STOPPED)
+        return fail(CRT_E_INVALID, "crt_render_adaptive: sample counts must stay below 2^31");
+    if (cam->image_w == 0 || cam->image_h == 0) return fail(CRT_E_INVALID, "empty image");
+    return render_adaptive(s, cam, num_devices, params, fn, user, h_rgb, h_block_samples, samples_rendered);
 }
 
 int crt_noise_estimate(int device, const double* d_noise, size_t pixels, uint32_t samples_per_pixel,

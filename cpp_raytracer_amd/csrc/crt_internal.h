@@ -375,10 +375,14 @@ void device_release(crt_scene* s);
 // One pass of a progressive render (crt_render_pass_async, which checks the alignment rules):
 // samples [first, first + count) of every owned pixel go into the running sums `sum` and the noise
 // state `noise` (may be null), and d_rgb (may be null) gets the frame so far.
+// blocks != null makes it a masked pass (crt_render_pass_masked_async): only the blocks whose word
+// equals `first` are rendered, about `hint` of them (0: unknown, all assumed).
 struct RenderPass {
     uint32_t first, count;
     double* sum;
     double* noise;
+    uint32_t* blocks = nullptr;
+    uint32_t hint = 0;
 };
 uint32_t sample_chunk_len(uint32_t spp);
 int device_render(const crt_scene* s, int device, const crt_camera* cam, const crt_tiling* t,
@@ -386,6 +390,14 @@ int device_render(const crt_scene* s, int device, const crt_camera* cam, const c
                   const RenderPass* pass = nullptr);
 int device_noise_estimate(int device, const double* d_noise, size_t pixels, uint32_t spp,
                           uint32_t samples_done, double* sum_se, double* sum_mean, void* stream);
+// adaptive sampling (crt_adaptive_update, crt_render_adaptive); the callers check the arguments
+bool adaptive_tiling_ok(const crt_tiling* t);
+int device_adaptive_update(int device, const crt_camera* cam, const crt_tiling* t, const double* d_noise,
+                           uint32_t* d_blocks, uint32_t samples_done, double threshold, uint32_t min_samples,
+                           uint32_t* active_blocks, void* stream);
+int render_adaptive(crt_scene* s, const crt_camera* cam, int num_devices, const crt_adaptive_params* prm,
+                    crt_adaptive_fn fn, void* user, double* h_rgb, uint32_t* h_block_samples,
+                    uint64_t* samples_rendered);
 int render_progressive(crt_scene* s, const crt_camera* cam, int num_devices, uint32_t samples_per_pass,
                        uint32_t flags, crt_progress_fn fn, void* user, double* h_rgb,
                        uint32_t* samples_done);

@@ -201,7 +201,81 @@ class Camera {
         return img;
     }
 
+    // render_scene_progressive with adaptive sampling (crt_render_adaptive): blocks of 16 x 4
+    // pixels stop once their noise is at most `threshold`
+    struct AdaptiveCtx {
+        ProgressBar<>* bar;
+        const std::function<bool(size_t, size_t, size_t, size_t)>* on_pass;
+    };
+    static int adaptive_pass(void* user, uint32_t done, uint32_t total, uint32_t active, uint32_t blocks,
+                             const double*) {
+        auto* ctx = static_cast<AdaptiveCtx*>(user);
+        ctx->bar->complete_iteration();
+        return (*ctx->on_pass && !(*ctx->on_pass)(done, total, active, blocks)) ? 1 : 0;
+    }
+
+    Image render_scene_adaptive(const crt_api::GpuScene& g, double threshold, size_t min_samples,
+                                size_t samples_per_pass,
+                                const std::function<bool(size_t, size_t, size_t, size_t)>& on_pass) {
+        crt_scene* scene = g.get();
+        init();
+        if (const char* dump = std::getenv("CRT_DUMP_SCENE")) dump_and_exit(g, dump);
+        resolved.base_seed = SeedSeqGenerator::get_instance().next_seed();
+        int devices = 0;
+        if (crt_device_count(&devices) || devices == 0) crt_api::die("Camera::render_adaptive");
+        if (const char* e = std::getenv("CRT_NUM_DEVICES")) devices = std::max(1, std::min(devices, std::atoi(e)));
+        if (samples_per_pass > UINT32_MAX) samples_per_pass = UINT32_MAX;
+        const size_t chunk = crt_sample_chunk_len(resolved.samples_per_pixel);
+        size_t per_pass = samples_per_pass ? samples_per_pass : std::max<size_t>(1, samples_per_pixel / 10);
+        per_pass = (per_pass + chunk - 1) / chunk * chunk;
+        if (min_samples == 0) min_samples = 2 * per_pass;  // two passes' worth
+        if (min_samples > UINT32_MAX) min_samples = UINT32_MAX;
+        ProgressBar<> bar((samples_per_pixel + per_pass - 1) / per_pass,
+                          "Rendering " + std::to_string(image_w) + " x " + std::to_string(image_h) + " image (up to " +
+                              std::to_string(samples_per_pixel) + " spp, adaptive) on " + std::to_string(devices) +
+                              " GPU" + (devices > 1 ? "s" : ""));
+        std::vector<double> rgb(image_w * image_h * 3);
+        AdaptiveCtx ctx{&bar, &on_pass};
+        crt_adaptive_params prm{};
+        prm.threshold = threshold;
+        prm.min_samples = static_cast<uint32_t>(min_samples);
+        prm.samples_per_pass = static_cast<uint32_t>(samples_per_pass);
+        uint64_t rendered = 0;
+        if (crt_render_adaptive(scene, &resolved, devices, &prm, adaptive_pass, &ctx, rgb.data(), nullptr, &rendered))
+            crt_api::die("Camera::render_adaptive");
+        std::cout << "Rendered " << static_cast<double>(rendered) / static_cast<double>(image_w * image_h)
+                  << " spp on average (of " << samples_per_pixel << ")\n" << std::endl;
+        auto img = Image::with_dimensions(image_w, image_h);
+        for (size_t r = 0; r < image_h; ++r)
+            for (size_t c = 0; c < image_w; ++c) {
+                const double* p = &rgb[(r * image_w + c) * 3];
+                img[r][c] = RGB::from_mag(p[0], p[1], p[2]);
+            }
+        return img;
+    }
+
 public:
+    // Extension (not in the reference): render_progressive with adaptive sampling. Blocks of
+    // 16 x 4 pixels stop between passes once the sum of their pixels' standard errors is at most
+    // `threshold` times the sum of their means, not before min_samples samples (0 = two passes'
+    // worth); later passes trace the other blocks only. Ticks a ProgressBar once a pass and prints
+    // the mean samples per pixel rendered. on_pass(samples done, samples in all, active blocks,
+    // blocks in all) returning false stops the render. When no block stops (min_samples >=
+    // samples_per_pixel never stops one) the image is render()'s bit for bit.
+    template <typename T>
+    requires std::is_base_of_v<Hittable, T>
+    Image render_adaptive(const T& world, double threshold, size_t min_samples = 0, size_t samples_per_pass = 0,
+                          std::function<bool(size_t done, size_t total, size_t active, size_t blocks)> on_pass = {}) {
+        if constexpr (std::is_same_v<T, BVH>) {
+            return render_scene_adaptive(world.gpu_scene(), threshold, min_samples, samples_per_pass, on_pass);
+        } else if constexpr (std::is_same_v<T, Scene>) {
+            return render_adaptive(BVH(world), threshold, min_samples, samples_per_pass, on_pass);
+        } else {
+            crt_api::GpuScene s(world, 32, 12, true);
+            return render_scene_adaptive(s, threshold, min_samples, samples_per_pass, on_pass);
+        }
+    }
+
     // Extension (not in the reference): render in passes of samples_per_pass samples per pixel
     // (0 = a tenth of them; rounded up to whole sample chunks), ticking a ProgressBar once a pass.
     // on_pass(samples done, samples in all, relative noise of the frame so far) returning false

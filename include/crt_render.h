@@ -263,6 +263,11 @@ uint32_t crt_sample_chunk_len(uint32_t samples_per_pixel);
  * CRT_E_INVALID (the message names the rule) unless first_sample is a multiple of the chunk
  * length, num_samples > 0, first_sample + num_samples <= samples_per_pixel, the end is a multiple
  * of the chunk length or equals samples_per_pixel, and d_sum is not NULL.
+ * Scratch of pass renders (this call, crt_render_pass_masked_async, crt_noise_estimate,
+ * crt_adaptive_update and the blocking drivers over them) comes from a stream-ordered memory pool
+ * the library creates per device and never trims: it holds the largest scratch a pass needed (the
+ * pass's partial sums, at most 4 GiB or CRT_PARTIAL_MB) until the process ends. The process's
+ * default pool is not used or changed by them. CRT_E_HIP if the pool cannot be created.
  * The call keeps no state: issuing each pass once, in increasing order, on one stream (or
  * otherwise ordered) is the caller's job. In order, the final frame is bit-identical to the
  * one-shot frame; passes after the first issued out of order still give a correct mean, equal
@@ -298,6 +303,74 @@ typedef int (*crt_progress_fn)(void* user, uint32_t samples_done, uint32_t sampl
 int crt_render_progressive(crt_scene* scene, const crt_camera* cam, int num_devices,
                            uint32_t samples_per_pass, uint32_t flags, crt_progress_fn fn, void* user,
                            double* h_rgb, uint32_t* samples_done);
+
+/* ---- adaptive sampling --------------------------------------------------------------------
+ * A block is the render kernel's tile: CRT_BLOCK_W columns x CRT_BLOCK_H owned rows. Block
+ * (bx, by) covers columns [16 bx, 16 bx + 16) and owned rows [4 by, 4 by + 4) (edge blocks are
+ * smaller) and has the number by * ceil(image_w / 16) + bx. Block state, d_blocks, is one uint32_t
+ * per block in device memory: the samples accumulated in each of the block's pixels, plus the bit
+ * CRT_BLOCK_STOPPED. Between passes crt_adaptive_update stops the blocks whose noise is below a
+ * threshold; a masked pass renders the others. A block that stops after n samples holds, bit for
+ * bit, what crt_render_pass_async's passes hold after n samples.
+ * The adaptive calls take a tiling only with tile_count == 1 or row_block % 4 == 0 (else
+ * CRT_E_INVALID): a rank's blocks are then blocks of the frame, whatever the number of ranks. */
+#define CRT_BLOCK_W 16
+#define CRT_BLOCK_H 4
+#define CRT_BLOCK_STOPPED 0x80000000u
+
+/* Blocks of owned_rows rows of an image_w wide frame: ceil(image_w / 16) * ceil(owned_rows / 4). */
+size_t crt_block_count(uint32_t image_w, uint32_t owned_rows);
+
+/* crt_render_pass_async (its rules, checked before any device work) for the blocks with
+ * d_blocks[b] == first_sample only; a stopped block never matches. A rendered block gets exactly
+ * crt_render_pass_async's additions, in its order, into d_sum and d_noise, and its word becomes
+ * first_sample + num_samples. A skipped block: with first_sample > 0, d_sum and d_noise are left
+ * alone and d_rgb (if given) gets sum * (1 / (double)n), n = the block's own count (0 when n = 0);
+ * with first_sample == 0 its pixels' d_sum, d_noise and d_rgb are written 0, so a caller may
+ * pre-set CRT_BLOCK_STOPPED on blocks to render a region only. The caller zeroes d_blocks
+ * (crt_block_count words, DEVICE) before the first pass.
+ * active_hint: the number of blocks the caller expects to be rendered (0 = unknown: all of them).
+ * It sizes the grid and the work items only: any value gives the same bits. */
+int crt_render_pass_masked_async(const crt_scene* scene, int device, const crt_camera* cam,
+                                 const crt_tiling* tiling, uint32_t first_sample, uint32_t num_samples,
+                                 double* d_sum, double* d_noise, double* d_rgb, uint32_t* d_blocks,
+                                 uint32_t active_hint, void* stream);
+
+/* The stopping rule, for every block with d_blocks[b] == samples_done. With L = the chunk length
+ * and K = samples_done / L, sum_se and sum_m are the sums over the block's pixels of
+ * crt_noise_estimate's se and m (in a fixed order that depends on the block's shape only). The
+ * block gets CRT_BLOCK_STOPPED iff K >= 2, samples_done >= min_samples and
+ * sum_se <= threshold * sum_m: no division, so an all-black block (0 <= 0) stops, and a NaN
+ * (compares false) never does. min_samples >= samples_per_pixel: never stop. threshold must be
+ * finite and >= 0; samples_done a multiple of the chunk length, or samples_per_pixel.
+ * *active_blocks (HOST) receives the number of blocks still at samples_done and
+ * not stopped. Synchronous on `stream`. */
+int crt_adaptive_update(int device, const crt_camera* cam, const crt_tiling* tiling, const double* d_noise,
+                        uint32_t* d_blocks, uint32_t samples_done, double threshold, uint32_t min_samples,
+                        uint32_t* active_blocks, void* stream);
+
+typedef struct crt_adaptive_params {
+    double threshold;          /* a block stops at sum_se <= threshold * sum_m                    */
+    uint32_t min_samples;      /* ... and not before this many samples                           */
+    uint32_t samples_per_pass; /* as crt_render_progressive's (0 = a tenth of the job)           */
+    uint32_t flags;            /* CRT_PROGRESS_PREVIEW                                           */
+    uint32_t reserved;         /* must be 0 (CRT_E_INVALID otherwise)                            */
+} crt_adaptive_params;
+
+/* Called on the calling thread after every pass and update; h_rgb as crt_progress_fn's. A non-zero
+ * return stops the render. */
+typedef int (*crt_adaptive_fn)(void* user, uint32_t samples_done, uint32_t samples_total,
+                               uint32_t active_blocks, uint32_t total_blocks, const double* h_rgb);
+
+/* Blocking adaptive render over devices [0, num_devices), rows dealt as crt_render_progressive's:
+ * one masked pass and one update per step on every device, until no block is active, all samples
+ * are done, or fn stops it. h_rgb: every pixel's mean over its block's own samples.
+ * h_block_samples (HOST, crt_block_count(image_w, image_h) words, or NULL): the frame's block
+ * counts in frame block order, the stopped bit cleared. *samples_rendered (or NULL): the sum over
+ * the pixels of their counts. */
+int crt_render_adaptive(crt_scene* scene, const crt_camera* cam, int num_devices,
+                        const crt_adaptive_params* params, crt_adaptive_fn fn, void* user, double* h_rgb,
+                        uint32_t* h_block_samples, uint64_t* samples_rendered);
 
 /* Instrumented pass: counts the work of the same render (never timed). */
 int crt_render_count(const crt_scene* scene, int device, const crt_camera* cam,
