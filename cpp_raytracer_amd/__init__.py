@@ -18,13 +18,14 @@ import numpy as np
 from . import _capi
 from ._capi import (CRT_BOX, CRT_DIELECTRIC, CRT_DIFFUSE_LIGHT, CRT_LAMBERTIAN, CRT_METAL,
                     CRT_PARALLELOGRAM, CRT_SPHERE, HIT_DTYPE, MATERIAL_DTYPE, NODE_DTYPE,
-                    OBJECT_DTYPE, CRT_BLOCK_STOPPED, BVHParams, Camera, CameraSettings, CrtError, RenderStats,
-                    SceneInfo, Tiling, check, lib)
+                    OBJECT_DTYPE, CRT_BLOCK_STOPPED, FEATURE_DTYPE, BVHParams, Camera, CameraSettings, CrtError,
+                    DenoiseParams, RenderStats, SceneInfo, Tiling, check, lib)
 
 __all__ = [
     "SceneData", "GpuScene", "CameraSettings", "Camera", "Tiling", "RenderStats", "CrtError",
     "resolve_camera", "sample_seed", "rand_double", "device_count", "lib", "ppm_values", "write_ppm",
     "sample_chunk_len", "noise_estimate", "block_count", "adaptive_update", "CRT_BLOCK_STOPPED",
+    "DenoiseParams", "FEATURE_DTYPE", "denoise_params", "pixel_variance", "denoise",
     "CRT_LAMBERTIAN", "CRT_METAL", "CRT_DIELECTRIC", "CRT_DIFFUSE_LIGHT",
     "CRT_SPHERE", "CRT_PARALLELOGRAM", "CRT_BOX",
 ]
@@ -80,6 +81,36 @@ def adaptive_update(device: int, cam: Camera, noise_ptr: int, blocks_ptr: int, s
                                     samples_done, threshold, min_samples, C.byref(n), C.c_void_p(stream)),
           "crt_adaptive_update")
     return int(n.value)
+
+
+def denoise_params(iterations: int = 5, normal_squarings: int = 7, sigma_l: float = 1.0,
+                   sigma_p: float = 0.05) -> DenoiseParams:
+    """crt_denoise_params: a-trous iterations (steps 1, 2, 4, ...), the normal weight's exponent
+    2^normal_squarings, the colour tolerance in standard errors and the plane-distance tolerance as
+    a fraction of the hit distance. The defaults are DESIGN section 6c's."""
+    return DenoiseParams(iterations, normal_squarings, sigma_l, sigma_p, 0, 0)
+
+
+def pixel_variance(device: int, cam: Camera, noise_ptr: int, var_ptr: int, samples_done: int,
+                   blocks_ptr: int = 0, stream: int = 0, tiling: Optional[Tiling] = None) -> None:
+    """Enqueue the per-pixel variance of the mean (crt_pixel_variance_async) from the noise state
+    at noise_ptr into var_ptr (1 double a pixel). Every pixel has samples_done samples, or with
+    blocks_ptr (an adaptive render's block state) its block's own count."""
+    t = C.byref(tiling) if tiling is not None else None
+    check(lib().crt_pixel_variance_async(device, C.byref(cam), t, C.c_void_p(noise_ptr or None),
+                                         C.c_void_p(blocks_ptr or None), samples_done, C.c_void_p(var_ptr or None),
+                                         C.c_void_p(stream)), "crt_pixel_variance_async")
+
+
+def denoise(device: int, width: int, height: int, rgb_ptr: int, var_ptr: int, feat_ptr: int,
+            params: DenoiseParams, out_ptr: int, var_out_ptr: int = 0, stream: int = 0) -> None:
+    """Enqueue the feature-guided a-trous filter (crt_denoise_async) of the whole frame at rgb_ptr
+    (h*w*3 doubles) with its variance map and feature records into out_ptr (and the filtered
+    variance into var_out_ptr, 0 = not wanted). The outputs may not overlap the inputs."""
+    check(lib().crt_denoise_async(device, width, height, C.c_void_p(rgb_ptr or None), C.c_void_p(var_ptr or None),
+                                  C.c_void_p(feat_ptr or None), C.byref(params) if params is not None else None,
+                                  C.c_void_p(out_ptr or None), C.c_void_p(var_out_ptr or None), C.c_void_p(stream)),
+          "crt_denoise_async")
 
 
 def device_count() -> int:
@@ -299,6 +330,33 @@ class GpuScene:
     # the module functions, beside the passes they go with
     adaptive_update = staticmethod(adaptive_update)
     block_count = staticmethod(block_count)
+    pixel_variance = staticmethod(pixel_variance)
+    denoise = staticmethod(denoise)
+
+    def render_features(self, device: int, cam: Camera, feat_ptr: int, stream: int = 0,
+                        tiling: Optional[Tiling] = None) -> None:
+        """Enqueue the first-hit features of the owned pixels (crt_render_features_async) into the
+        device buffer at feat_ptr: one 88-byte crt_feature (FEATURE_DTYPE) per pixel, at
+        render_async's pixel addresses."""
+        t = C.byref(tiling) if tiling is not None else None
+        check(lib().crt_render_features_async(self._h, device, C.byref(cam), t, C.c_void_p(feat_ptr or None),
+                                              C.c_void_p(stream)), "crt_render_features_async")
+
+    def render_denoised(self, cam: Camera, params: Optional[DenoiseParams] = None, threshold: Optional[float] = None,
+                        min_samples: int = 0, samples_per_pass: int = 0, device: int = 0,
+                        noisy: bool = False):
+        """Blocking denoised render on one device (crt_render_denoised): every sample, or with
+        `threshold` an adaptive render (render_adaptive's rule), then features, variance and the
+        filter. Returns (denoised frame, unfiltered frame or None, samples rendered over all pixels)."""
+        out = np.empty((cam.image_h, cam.image_w, 3), np.float64)
+        raw = np.empty_like(out) if noisy else None
+        prm = params if params is not None else denoise_params()
+        ad = _capi.AdaptiveParams(threshold, min_samples, samples_per_pass, 0, 0) if threshold is not None else None
+        rendered = C.c_uint64(0)
+        check(lib().crt_render_denoised(self._h, device, C.byref(cam), C.byref(ad) if ad is not None else None,
+                                        C.byref(prm), raw.ctypes.data if noisy else None, out.ctypes.data,
+                                        C.byref(rendered)), "crt_render_denoised")
+        return out, raw, int(rendered.value)
 
     def render_progressive(self, cam: Camera, samples_per_pass: int = 0, callback=None, num_devices: int = 1,
                            preview: bool = False, noise: bool = False) -> tuple[np.ndarray, int]:

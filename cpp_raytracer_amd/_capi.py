@@ -92,6 +92,16 @@ class AdaptiveParams(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class Feature(C.Structure):
+    _fields_ = [("albedo", D3), ("normal", D3), ("point", D3), ("t", C.c_double), ("prim", C.c_int32),
+                ("material", C.c_uint32)]
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("normal_squarings", C.c_uint32), ("sigma_l", C.c_double),
+                ("sigma_p", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # numpy views of the same records (for bulk scene I/O)
 MATERIAL_DTYPE = np.dtype([("kind", "<u4"), ("reserved", "<u4"), ("color", "<f8", 3), ("param", "<f8")])
 OBJECT_DTYPE = np.dtype([("kind", "<u4"), ("material", "<u4"), ("v", "<f8", 9)])
@@ -103,6 +113,9 @@ assert MATERIAL_DTYPE.itemsize == C.sizeof(Material) == 40
 assert OBJECT_DTYPE.itemsize == C.sizeof(Object) == 80
 assert NODE_DTYPE.itemsize == C.sizeof(BVHNode) == 64
 assert HIT_DTYPE.itemsize == C.sizeof(Hit)
+FEATURE_DTYPE = np.dtype([("albedo", "<f8", 3), ("normal", "<f8", 3), ("point", "<f8", 3), ("t", "<f8"),
+                          ("prim", "<i4"), ("material", "<u4")])
+assert FEATURE_DTYPE.itemsize == C.sizeof(Feature) == 88
 
 P = C.POINTER
 # crt_progress_fn(user, samples_done, samples_total, noise, h_rgb) -> non-zero stops the render
@@ -144,6 +157,13 @@ EXPORTS = {
     "crt_adaptive_update": (C.c_int, [C.c_int, P(Camera), P(Tiling), C.c_void_p, C.c_void_p, C.c_uint32,
                                       C.c_double, C.c_uint32, P(C.c_uint32), C.c_void_p]),
     "crt_render_adaptive": (C.c_int, [C.c_void_p, P(Camera), C.c_int, P(AdaptiveParams), ADAPTIVE_FN, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, P(C.c_uint64)]),
+    "crt_render_features_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Tiling), C.c_void_p, C.c_void_p]),
+    "crt_pixel_variance_async": (C.c_int, [C.c_int, P(Camera), P(Tiling), C.c_void_p, C.c_void_p, C.c_uint32,
+                                           C.c_void_p, C.c_void_p]),
+    "crt_denoise_async": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    P(DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "crt_render_denoised": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(AdaptiveParams), P(DenoiseParams),
                                       C.c_void_p, C.c_void_p, P(C.c_uint64)]),
     "crt_render_count": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Tiling), P(RenderStats)]),
     "crt_render": (C.c_int, [C.c_void_p, P(Camera), C.c_int, C.c_void_p, P(RenderStats)]),

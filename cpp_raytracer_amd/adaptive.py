@@ -87,6 +87,10 @@ class AdaptiveRender(ProgressiveRender):
         sample_map)."""
         raise CrtError("AdaptiveRender.noise: blocks hold different sample counts; see active_blocks / sample_map")
 
+    def _blocks_ptr(self) -> int:
+        """denoised() (ProgressiveRender's) takes every pixel's sample count from its block word."""
+        return self._blocks.data_ptr()
+
     def block_words(self) -> np.ndarray:
         """The block state: (block rows, block columns) uint32, counts with CRT_BLOCK_STOPPED."""
         bx = (self.cam.image_w + BLOCK_W - 1) // BLOCK_W

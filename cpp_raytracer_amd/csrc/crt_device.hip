@@ -2573,6 +2573,84 @@ __global__ __launch_bounds__(kBlock) void hits_kernel(SceneView S, const double*
     out[i] = h;
 }
 
+// crt_render_features_async: hits_kernel's query for the centre ray of every owned pixel (thread
+// i = owned row i / w, column i % w), start_path's expressions with the random terms left out.
+__global__ __launch_bounds__(kBlock) void features_kernel(SceneView S, CamView C, Work W, uint32_t n,
+                                                          const uint32_t* __restrict__ ref_prim,
+                                                          uint32_t num_spheres,
+                                                          crt_feature* __restrict__ out,
+                                                          uint32_t* __restrict__ gstack) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    Stack<uint32_t> st;
+    st.base = gstack + i;
+    st.stride = gridDim.x * kBlock;
+    const uint32_t k = i / C.w, col = i % C.w, row = owned_row(W, k);
+    const double fr = static_cast<double>(row), fc = static_cast<double>(col);
+    double o[3], d[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double center = (C.p00[j] + C.pdy[j] * fr) + C.pdx[j] * fc;
+        o[j] = C.o[j];
+        d[j] = center - o[j];
+    }
+    double tmax = std::numeric_limits<double>::infinity();
+    uint32_t ref = 0;
+    LaneCounters ctr{};
+    crt_feature f{};
+    f.prim = -1;
+    if (trace<uint32_t, false>(S, st, o, d, C.t_min, tmax, ref, ctr)) {
+        double p[3], nrm[3];
+        bool front;
+        f.material = hit_record<false>(S, ref, o, d, tmax, p, nrm, front);
+        f.t = tmax;
+        const DevMaterial& m = S.mats[f.material];
+        const bool glass = m.kind == CRT_DIELECTRIC;
+        for (int j = 0; j < 3; ++j) {
+            f.point[j] = p[j];
+            f.normal[j] = nrm[j];
+            f.albedo[j] = glass ? 1.0 : m.color[j];
+        }
+        const uint32_t r = (ref & kRefQuad) ? num_spheres + (ref & ~kRefQuad) : ref;
+        f.prim = static_cast<int32_t>(ref_prim[r]);
+    } else {
+        for (int j = 0; j < 3; ++j) f.albedo[j] = C.bg[j];
+    }
+    out[static_cast<size_t>(W.packed ? k : row) * C.w + col] = f;
+}
+
+// crt_pixel_variance_async: thread i = owned row i / w, column i % w. n = samples_done, or the
+// pixel's block word (adaptive_update_kernel's block numbering) without the stopped bit;
+// noise_stage1_kernel's expressions for m and the variance of the mean, without its sqrt.
+__global__ __launch_bounds__(256) void pixel_variance_kernel(const double* __restrict__ noise,
+                                                             const uint32_t* __restrict__ blocks, Work W, uint32_t w,
+                                                             uint32_t n_pixels, uint32_t samples_done, uint32_t L_,
+                                                             double* __restrict__ var_out) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_pixels) return;
+    const uint32_t k = i / w, col = i % w;
+    const size_t pix = static_cast<size_t>(W.packed ? k : owned_row(W, k)) * w + col;
+    uint32_t n = samples_done;
+    if (blocks) {
+        const uint32_t tiles_x = (w + kTileW - 1) / kTileW;
+        n = blocks[(k / kTileH) * tiles_x + col / kTileW] & ~CRT_BLOCK_STOPPED;
+    }
+    const uint32_t Ki = n / L_;
+    const double K = static_cast<double>(Ki), L = static_cast<double>(L_);
+    double v = 0;
+    if (Ki >= 1) {
+        const double t = noise[pix * 2 + 0], q = noise[pix * 2 + 1];
+        const double m = t / (K * L);
+        if (Ki == 1) {
+            v = m * m;
+        } else {
+            const double var = q / (L * L) - K * m * m;
+            v = (var > 0 ? var : 0.0) / (K * (K - 1));
+        }
+    }
+    var_out[pix] = v;
+}
+
 }  // namespace dev
 
 // =============================================================================================
@@ -2816,6 +2894,7 @@ void device_release(crt_scene* s) {
         if (!c.valid) continue;
         DeviceGuard g(d);
         (void)hipFree(c.base);
+        if (c.ref_prim) (void)hipFree(c.ref_prim);
         c = DeviceCopy{};
     }
 }
@@ -3901,6 +3980,103 @@ int device_adaptive_update(int device, const crt_camera* cam, const crt_tiling* 
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(CRT_E_HIP, std::string("adaptive update: ") + hipGetErrorString(e));
     *active_blocks = h;
+    return CRT_OK;
+}
+
+// ---- denoising inputs (host side): first-hit features and the per-pixel variance -------------
+int device_check(int device) { return check_device(device); }
+
+int device_pass_pool(int device, void** pool) {
+    hipMemPool_t p = nullptr;
+    const int rc = pass_pool(device, &p);
+    *pool = p;
+    return rc;
+}
+
+// the scene's ref -> primitive number table on `device` (hits_kernel's ref_prim), built and
+// uploaded once per device copy, blocking; the scene's device lock orders the first callers
+static int ref_prim_table(const crt_scene* cs, int device, const uint32_t** out) {
+    crt_scene* s = const_cast<crt_scene*>(cs);  // the table is a cache beside the device copy
+    std::lock_guard<std::mutex> lk(s->dev_mu[device]);
+    DeviceCopy& c = s->dev[device];
+    if (!c.ref_prim) {
+        const size_t nsp = s->num_spheres, nq = s->num_quads;
+        std::vector<uint32_t> ref_prim(std::max<size_t>(1, nsp + nq));
+        std::vector<uint32_t> dev_refs;  // a scene set up on the device has no host refs
+        const uint32_t* refs = s->refs.data();
+        if (s->refs.size() != s->num_prims) {
+            dev_refs.resize(s->num_prims);
+            HIP_TRY(hipMemcpy(dev_refs.data(), c.refs, s->num_prims * 4, hipMemcpyDeviceToHost));
+            refs = dev_refs.data();
+        }
+        for (size_t slot = 0; slot < s->num_prims; ++slot) {
+            const uint32_t r = refs[slot];
+            ref_prim[(r & kRefQuad) ? nsp + (r & ~kRefQuad) : r] = s->order[slot];
+        }
+        uint32_t* d = nullptr;
+        HIP_TRY(hipMalloc(&d, ref_prim.size() * 4));
+        const hipError_t e = hipMemcpy(d, ref_prim.data(), ref_prim.size() * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            return fail(CRT_E_HIP, std::string("feature pass: primitive table upload: ") + hipGetErrorString(e));
+        }
+        c.ref_prim = d;
+    }
+    *out = c.ref_prim;
+    return CRT_OK;
+}
+
+int device_render_features(const crt_scene* s, int device, const crt_camera* cam, const crt_tiling* t,
+                           crt_feature* d_feat, void* stream) {
+    int rc = check_device(device);
+    if (rc) return rc;
+    if (!s->dev[device].valid)
+        return fail(CRT_E_NOT_UPLOADED, "scene not uploaded to device " + std::to_string(device));
+    if (static_cast<uint64_t>(cam->image_w) * cam->image_h >= 0x7fffffffull)
+        return fail(CRT_E_INVALID, "crt_render_features_async: image has more than 2^31-2 pixels");
+    dev::Work W;
+    rc = tiling_work(cam, t, W);
+    if (rc) return rc;
+    const uint64_t n = static_cast<uint64_t>(W.owned_rows) * cam->image_w;
+    if (n == 0) return CRT_OK;
+    DeviceGuard g(device);
+    const uint32_t* d_ref_prim = nullptr;
+    rc = ref_prim_table(s, device, &d_ref_prim);
+    if (rc) return rc;
+    hipMemPool_t pool = nullptr;
+    rc = pass_pool(device, &pool);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint32_t blocks = static_cast<uint32_t>((n + dev::kBlock - 1) / dev::kBlock);
+    uint32_t* d_stack = nullptr;  // trace()'s stacks, [level][thread], as device_closest_hits sizes them
+    HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&d_stack),
+                                   static_cast<size_t>(s->depth + 1) * blocks * dev::kBlock * 4, pool, st));
+    hipLaunchKernelGGL(dev::features_kernel, dim3(blocks), dim3(dev::kBlock), 0, st, view_of(s->dev[device]),
+                       cam_view(cam), W, static_cast<uint32_t>(n), d_ref_prim, static_cast<uint32_t>(s->num_spheres),
+                       d_feat, d_stack);
+    const hipError_t e = hipGetLastError();
+    (void)hipFreeAsync(d_stack, st);
+    if (e != hipSuccess) return fail(CRT_E_HIP, std::string("features_kernel launch: ") + hipGetErrorString(e));
+    return CRT_OK;
+}
+
+int device_pixel_variance(int device, const crt_camera* cam, const crt_tiling* t, const double* d_noise,
+                          const uint32_t* d_blocks, uint32_t samples_done, double* d_var, void* stream) {
+    int rc = check_device(device);
+    if (rc) return rc;
+    if (static_cast<uint64_t>(cam->image_w) * cam->image_h >= 0xffffffffull)
+        return fail(CRT_E_INVALID, "crt_pixel_variance_async: image has more than 2^32-1 pixels");
+    dev::Work W;
+    rc = tiling_work(cam, t, W);
+    if (rc) return rc;
+    const uint64_t n = static_cast<uint64_t>(W.owned_rows) * cam->image_w;
+    if (n == 0) return CRT_OK;
+    DeviceGuard g(device);
+    hipLaunchKernelGGL(dev::pixel_variance_kernel, dim3(static_cast<uint32_t>((n + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), d_noise, d_blocks, W, cam->image_w, static_cast<uint32_t>(n),
+                       samples_done, sample_chunk_len(cam->samples_per_pixel), d_var);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(CRT_E_HIP, std::string("pixel_variance_kernel launch: ") + hipGetErrorString(e));
     return CRT_OK;
 }
 

@@ -1294,6 +1294,96 @@ int crt_render_adaptive(crt_scene* s, const crt_camera* cam, int num_devices, co
     return render_adaptive(s, cam, num_devices, params, fn, user, h_rgb, h_block_samples, samples_rendered);
 }
 
+// ---- denoising: every rule is checked here, before any device work ---------------------------
+int crt_render_features_async(const crt_scene* s, int device, const crt_camera* cam, const crt_tiling* tiling,
+                              crt_feature* d_feat, void* stream) {
+    clear_error();
+    if (!s || !cam) return fail(CRT_E_INVALID, "crt_render_features_async: null argument");
+    if (!d_feat) return fail(CRT_E_INVALID, "crt_render_features_async: d_feat is null (the output is required)");
+    return device_render_features(s, device, cam, tiling, d_feat, stream);
+}
+
+int crt_pixel_variance_async(int device, const crt_camera* cam, const crt_tiling* tiling, const double* d_noise,
+                             const uint32_t* d_blocks, uint32_t samples_done, double* d_var, void* stream) {
+    clear_error();
+    if (!cam || !d_noise) return fail(CRT_E_INVALID, "crt_pixel_variance_async: null argument");
+    if (!d_var) return fail(CRT_E_INVALID, "crt_pixel_variance_async: d_var is null (the output is required)");
+    if (samples_done > cam->samples_per_pixel)
+        return fail(CRT_E_INVALID, "crt_pixel_variance_async: samples_done exceeds samples_per_pixel");
+    if (samples_done != cam->samples_per_pixel && samples_done % sample_chunk_len(cam->samples_per_pixel) != 0)
+        return fail(CRT_E_INVALID, "crt_pixel_variance_async: samples_done = " + std::to_string(samples_done) +
+                                       " is not a pass boundary (a multiple of the chunk length, or samples_per_pixel)");
+    if (d_blocks) {
+        const int rc = check_adaptive_tiling("crt_pixel_variance_async", tiling);
+        if (rc) return rc;
+    }
+    return device_pixel_variance(device, cam, tiling, d_noise, d_blocks, samples_done, d_var, stream);
+}
+
+// the rules of crt_denoise_params: CRT_OK, or the failure naming the broken rule
+static int check_denoise_params(const char* fn, const crt_denoise_params* p) {
+    const std::string who = std::string(fn) + ": ";
+    if (!p) return fail(CRT_E_INVALID, who + "the denoise parameters are null");
+    if (p->iterations < 1 || p->iterations > 8)
+        return fail(CRT_E_INVALID, who + "iterations = " + std::to_string(p->iterations) + " is outside 1..8");
+    if (p->normal_squarings > 10)
+        return fail(CRT_E_INVALID, who + "normal_squarings = " + std::to_string(p->normal_squarings) + " is outside 0..10");
+    if (!(p->sigma_l > 0) || !std::isfinite(p->sigma_l)) return fail(CRT_E_INVALID, who + "sigma_l must be finite and > 0");
+    if (!(p->sigma_p > 0) || !std::isfinite(p->sigma_p)) return fail(CRT_E_INVALID, who + "sigma_p must be finite and > 0");
+    if (p->flags != 0) return fail(CRT_E_INVALID, who + "denoise flags must be 0");
+    if (p->reserved != 0) return fail(CRT_E_INVALID, who + "denoise reserved must be 0");
+    return CRT_OK;
+}
+
+static bool ranges_overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+    if (!a || !b || a_bytes == 0 || b_bytes == 0) return false;
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + b_bytes && y < x + a_bytes;
+}
+
+int crt_denoise_async(int device, uint32_t w, uint32_t h, const double* d_rgb, const double* d_var,
+                      const crt_feature* d_feat, const crt_denoise_params* params, double* d_out, double* d_var_out,
+                      void* stream) {
+    clear_error();
+    const int rc = check_denoise_params("crt_denoise_async", params);
+    if (rc) return rc;
+    if (!d_rgb || !d_var || !d_feat) return fail(CRT_E_INVALID, "crt_denoise_async: null input (d_rgb, d_var and d_feat are required)");
+    if (!d_out) return fail(CRT_E_INVALID, "crt_denoise_async: d_out is null (the output is required)");
+    const uint64_t n = static_cast<uint64_t>(w) * h;
+    const struct { const void* p; uint64_t bytes; const char* name; } in[3] = {
+        {d_rgb, n * 24, "d_rgb"}, {d_var, n * 8, "d_var"}, {d_feat, n * sizeof(crt_feature), "d_feat"}};
+    for (const auto& i : in) {
+        if (ranges_overlap(d_out, n * 24, i.p, i.bytes))
+            return fail(CRT_E_INVALID, std::string("crt_denoise_async: d_out aliases ") + i.name);
+        if (ranges_overlap(d_var_out, n * 8, i.p, i.bytes))
+            return fail(CRT_E_INVALID, std::string("crt_denoise_async: d_var_out aliases ") + i.name);
+    }
+    if (ranges_overlap(d_out, n * 24, d_var_out, n * 8))
+        return fail(CRT_E_INVALID, "crt_denoise_async: d_var_out aliases d_out");
+    return device_denoise(device, w, h, d_rgb, d_var, d_feat, params, d_out, d_var_out, stream);
+}
+
+int crt_render_denoised(crt_scene* s, int device, const crt_camera* cam, const crt_adaptive_params* adaptive,
+                        const crt_denoise_params* denoise, double* h_noisy, double* h_rgb, uint64_t* samples_rendered) {
+    clear_error();
+    if (samples_rendered) *samples_rendered = 0;
+    if (!s || !cam) return fail(CRT_E_INVALID, "crt_render_denoised: null argument");
+    if (!h_rgb) return fail(CRT_E_INVALID, "crt_render_denoised: h_rgb is null (the output is required)");
+    const int rc = check_denoise_params("crt_render_denoised", denoise);
+    if (rc) return rc;
+    if (adaptive) {
+        if (adaptive->flags != 0) return fail(CRT_E_INVALID, "crt_render_denoised: adaptive flags must be 0");
+        if (adaptive->reserved != 0) return fail(CRT_E_INVALID, "crt_render_denoised: adaptive reserved must be 0");
+        if (!(adaptive->threshold >= 0) || !std::isfinite(adaptive->threshold))
+            return fail(CRT_E_INVALID, "crt_render_denoised: threshold must be finite and >= 0");
+    }
+    if (cam->samples_per_pixel == 0) return fail(CRT_E_INVALID, "crt_render_denoised: samples_per_pixel is 0");
+    if (cam->samples_per_pixel >= CRT_BLOCK_STOPPED)
+        return fail(CRT_E_INVALID, "crt_render_denoised: sample counts must stay below 2^31");
+    if (cam->image_w == 0 || cam->image_h == 0) return fail(CRT_E_INVALID, "empty image");
+    return render_denoised(s, device, cam, adaptive, denoise, h_noisy, h_rgb, samples_rendered);
+}
+
 int crt_noise_estimate(int device, const double* d_noise, size_t pixels, uint32_t samples_per_pixel,
                        uint32_t samples_done, double* sum_se, double* sum_mean, void* stream) {
     clear_error();

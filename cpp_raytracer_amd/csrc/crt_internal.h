@@ -294,6 +294,9 @@ struct DeviceCopy {
     // parity guard words (zeroed at upload): [0] Dielectric reflect-or-refract decisions that a
     // 1-ulp difference of pow(1 - cos, 5) could have flipped (shade(), crt_render_guard)
     unsigned long long* guard = nullptr;
+    // ref -> primitive number (spheres, then parallelograms), an allocation of its own made by the
+    // first crt_render_features_async on this device (device_render_features)
+    uint32_t* ref_prim = nullptr;
 };
 
 // A flattened primitive (Scene::get_primitive_components order) with the derived data the
@@ -403,6 +406,21 @@ int render_progressive(crt_scene* s, const crt_camera* cam, int num_devices, uin
                        uint32_t* samples_done);
 int device_closest_hits(crt_scene* s, int device, const double* rays, size_t n, double t_min,
                         double t_max, crt_hit* out);
+// denoising: first-hit features and the per-pixel variance (crt_device.hip), the filter and the
+// blocking driver (crt_denoise.hip); the callers check the arguments
+int device_render_features(const crt_scene* s, int device, const crt_camera* cam, const crt_tiling* t,
+                           crt_feature* d_feat, void* stream);
+int device_pixel_variance(int device, const crt_camera* cam, const crt_tiling* t, const double* d_noise,
+                          const uint32_t* d_blocks, uint32_t samples_done, double* d_var, void* stream);
+int device_denoise(int device, uint32_t w, uint32_t h, const double* d_rgb, const double* d_var,
+                   const crt_feature* d_feat, const crt_denoise_params* prm, double* d_out, double* d_var_out,
+                   void* stream);
+int render_denoised(crt_scene* s, int device, const crt_camera* cam, const crt_adaptive_params* adaptive,
+                    const crt_denoise_params* denoise, double* h_noisy, double* h_rgb, uint64_t* samples_rendered);
+// CRT_OK when `device` is a visible device the library can use, else the CRT_E_NODEVICE failure
+int device_check(int device);
+// the stream-ordered scratch pool of pass renders on `device` (a hipMemPool_t)
+int device_pass_pool(int device, void** pool);
 int device_count(int* n);
 const char* device_build_info();
 int device_guard(crt_scene* s, int device, uint64_t* schlick_undecided, bool reset);

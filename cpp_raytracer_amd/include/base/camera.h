@@ -28,6 +28,14 @@
 #include "util/image.h"
 #include "util/progressbar.h"
 
+// Extension (not in the reference): the knobs of Camera::render_denoised (crt_denoise_params).
+struct DenoiseOptions {
+    unsigned iterations = 5;        // a-trous iterations: steps 1, 2, 4, ... (1..8)
+    unsigned normal_squarings = 7;  // normal weight = max(0, n_p . n_q)^(2^this) (0..10)
+    double sigma_l = 1;             // colour tolerance in standard errors
+    double sigma_p = 0.05;          // plane-distance tolerance as a fraction of the hit distance
+};
+
 class Camera {
     size_t image_w = 1280, image_h = 720;
     double viewport_w = 0, viewport_h = 0;
@@ -254,7 +262,67 @@ class Camera {
         return img;
     }
 
+    // render_scene followed by the denoiser (crt_render_denoised) on GPU 0: every sample, or with
+    // adaptive_threshold >= 0 an adaptive render at that threshold
+    Image render_scene_denoised(const crt_api::GpuScene& g, const DenoiseOptions& opt, double adaptive_threshold) {
+        crt_scene* scene = g.get();
+        init();
+        if (const char* dump = std::getenv("CRT_DUMP_SCENE")) dump_and_exit(g, dump);
+        resolved.base_seed = SeedSeqGenerator::get_instance().next_seed();
+        int devices = 0;
+        if (crt_device_count(&devices) || devices == 0) crt_api::die("Camera::render_denoised");
+        const bool adaptive = adaptive_threshold >= 0;
+        std::cout << "Rendering " << image_w << " x " << image_h << " image (" << (adaptive ? "up to " : "")
+                  << samples_per_pixel << " spp" << (adaptive ? ", adaptive" : "") << ", denoised) on 1 GPU" << std::endl;
+        std::vector<double> rgb(image_w * image_h * 3);
+        crt_denoise_params dp{};
+        dp.iterations = opt.iterations;
+        dp.normal_squarings = opt.normal_squarings;
+        dp.sigma_l = opt.sigma_l;
+        dp.sigma_p = opt.sigma_p;
+        crt_adaptive_params ap{};
+        ap.threshold = adaptive_threshold;
+        {  // render_adaptive's defaults: passes of a tenth of the samples, a floor of two passes
+            const size_t chunk = crt_sample_chunk_len(resolved.samples_per_pixel);
+            const size_t per_pass = (std::max<size_t>(1, samples_per_pixel / 10) + chunk - 1) / chunk * chunk;
+            ap.min_samples = static_cast<uint32_t>(std::min<size_t>(2 * per_pass, UINT32_MAX));
+        }
+        uint64_t rendered = 0;
+        auto t0 = std::chrono::steady_clock::now();
+        if (crt_render_denoised(scene, 0, &resolved, adaptive ? &ap : nullptr, &dp, nullptr, rgb.data(), &rendered))
+            crt_api::die("Camera::render_denoised");
+        auto ms = ms_diff(t0, std::chrono::steady_clock::now());
+        std::cout << "Rendered " << static_cast<double>(rendered) / static_cast<double>(image_w * image_h)
+                  << " spp on average (of " << samples_per_pixel << "), denoised: Finished in " << ms << "ms\n"
+                  << std::endl;
+        auto img = Image::with_dimensions(image_w, image_h);
+        for (size_t r = 0; r < image_h; ++r)
+            for (size_t c = 0; c < image_w; ++c) {
+                const double* p = &rgb[(r * image_w + c) * 3];
+                img[r][c] = RGB::from_mag(p[0], p[1], p[2]);
+            }
+        return img;
+    }
+
 public:
+    // Extension (not in the reference): render (adaptive_threshold < 0: every sample) or
+    // render_adaptive (blocks stop at that threshold, default pass length and sample floor), then
+    // the feature-guided a-trous denoiser of crt_denoise_async over the frame, on one GPU. Guided
+    // by first-hit normals, positions and the per-pixel variance; what is seen through glass or in
+    // mirrors is filtered by colour and variance alone, and albedo is not divided out.
+    template <typename T>
+    requires std::is_base_of_v<Hittable, T>
+    Image render_denoised(const T& world, DenoiseOptions options = {}, double adaptive_threshold = -1) {
+        if constexpr (std::is_same_v<T, BVH>) {
+            return render_scene_denoised(world.gpu_scene(), options, adaptive_threshold);
+        } else if constexpr (std::is_same_v<T, Scene>) {
+            return render_denoised(BVH(world), options, adaptive_threshold);
+        } else {
+            crt_api::GpuScene s(world, 32, 12, true);
+            return render_scene_denoised(s, options, adaptive_threshold);
+        }
+    }
+
     // Extension (not in the reference): render_progressive with adaptive sampling. Blocks of
     // 16 x 4 pixels stop between passes once the sum of their pixels' standard errors is at most
     // `threshold` times the sum of their means, not before min_samples samples (0 = two passes'

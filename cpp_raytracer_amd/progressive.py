@@ -11,7 +11,8 @@ from typing import Optional
 
 import numpy as np
 
-from . import Camera, CrtError, GpuScene, Tiling, noise_estimate, sample_chunk_len
+from . import (FEATURE_DTYPE, Camera, CrtError, GpuScene, Tiling, denoise, denoise_params, noise_estimate,
+               pixel_variance, sample_chunk_len)
 
 
 def _owned_rows(height: int, tiling: Optional[Tiling]) -> int:
@@ -80,6 +81,49 @@ class ProgressiveRender:
         se, mean = noise_estimate(self.device, self._noise.data_ptr(), self._noise.shape[0] * self._noise.shape[1],
                                   self.samples_total, self.samples_done, st)
         return se / mean if mean == mean and mean != 0 else float("nan")
+
+    def _blocks_ptr(self) -> int:
+        """The block state whose counts denoised() takes the pixels' sample counts from (0: every
+        pixel has samples_done samples)."""
+        return 0
+
+    def features(self):
+        """The first-hit features of the frame (crt_render_features_async), computed once per
+        render object: a device tensor of h * w 88-byte records (FEATURE_DTYPE) as uint8."""
+        import torch
+        if self.tiling is not None and self.tiling.tile_count != 1:
+            raise CrtError("ProgressiveRender.features: needs a render of the whole frame (one tile)")
+        if getattr(self, "_feat", None) is None:
+            dev = torch.device("cuda", self.device)
+            feat = torch.zeros(self.cam.image_h * self.cam.image_w, FEATURE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            with torch.cuda.device(self.device):
+                st = torch.cuda.current_stream().cuda_stream
+            self.scene.render_features(self.device, self.cam, feat.data_ptr(), st)
+            self._feat = feat
+        return self._feat
+
+    def denoised(self, params=None):
+        """The denoised frame of the state so far (the preview between passes): the frame of the
+        last step() filtered by crt_denoise_async with the variance crt_pixel_variance_async takes
+        from the noise state. Returns a device tensor (h, w, 3) float64, the same one every call,
+        valid once the current stream reaches this point. params: denoise_params(...)."""
+        import torch
+        if self._noise is None:
+            raise CrtError("ProgressiveRender.denoised: built with noise=False (the variance comes from the noise state)")
+        if self.samples_done == 0:
+            raise CrtError("ProgressiveRender.denoised: no pass rendered yet")
+        feat = self.features()
+        if getattr(self, "_var", None) is None:
+            dev = torch.device("cuda", self.device)
+            self._var = torch.zeros(self.cam.image_h, self.cam.image_w, dtype=torch.float64, device=dev)
+            self._den = torch.zeros(self.cam.image_h, self.cam.image_w, 3, dtype=torch.float64, device=dev)
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream().cuda_stream
+        pixel_variance(self.device, self.cam, self._noise.data_ptr(), self._var.data_ptr(), self.samples_done,
+                       self._blocks_ptr(), st, self.tiling)
+        denoise(self.device, self.cam.image_w, self.cam.image_h, self._out.data_ptr(), self._var.data_ptr(),
+                feat.data_ptr(), params if params is not None else denoise_params(), self._den.data_ptr(), 0, st)
+        return self._den
 
     def state(self) -> dict:
         """A checkpoint: the running sums (and noise state) as numpy arrays, and what identifies

@@ -372,6 +372,107 @@ int crt_render_adaptive(crt_scene* scene, const crt_camera* cam, int num_devices
                         const crt_adaptive_params* params, crt_adaptive_fn fn, void* user, double* h_rgb,
                         uint32_t* h_block_samples, uint64_t* samples_rendered);
 
+/* ---- denoising ----------------------------------------------------------------------------
+ * A frame that stopped early (progressive passes, adaptive sampling) is noisy. The calls below
+ * filter it with an edge-stopping a-trous wavelet filter guided by first-hit features and by the
+ * per-pixel variance the noise state already holds. Everything here is specified as IEEE f64
+ * expressions of + - * / in a fixed order (host and device build with -ffp-contract=off), so a
+ * restatement on the CPU gives the same bits (tests/denoise_model.py is one).
+ * Limits: the features are those of the first hit only, so detail seen through glass or in
+ * mirrors is guided by colour and variance alone; albedo is reported but not divided out before
+ * filtering (no albedo demodulation): textures would blur, the reference's materials have none.
+ * One device per call: a multi-GPU render would have to gather its noise state first (not built).
+ * Below, max0(x) = x > 0 ? x : 0 (so -0 and NaN give +0), y(c) = (c0 + c1) + c2 and
+ * dot(a, b) = (a0 * b0 + a1 * b1) + a2 * b2. */
+
+/* First-hit features of one pixel. */
+typedef struct crt_feature {
+    double albedo[3];  /* Lambertian, Metal, DiffuseLight: material colour; Dielectric: 1,1,1; miss: cam->background */
+    double normal[3];  /* faces the ray, as crt_hit.normal; miss: 0,0,0 */
+    double point[3];   /* as crt_hit.point; miss: 0,0,0 */
+    double t;          /* as crt_hit.t; miss: 0 */
+    int32_t prim;      /* as crt_hit.prim; -1 = miss */
+    uint32_t material; /* as crt_hit.material; miss: 0 */
+} crt_feature;         /* 88 bytes */
+
+/* Features of the owned pixels into d_feat (DEVICE, one record per pixel at crt_render_async's
+ * pixel addresses: whole frame, or the owned rows packed under CRT_TILING_PACKED; rows not owned
+ * are left untouched). One ray per pixel (row, col) from cam->origin through the pixel's centre,
+ * no defocus offset and no jitter: per component k
+ *   center = (pixel00[k] + pixel_delta_y[k] * row) + pixel_delta_x[k] * col,  d[k] = center - origin[k]
+ * (random_ray_through_pixel's order with the random terms left out), over the interval
+ * (cam->t_min, +inf), traced as crt_closest_hits traces it. The parity guard count is not touched.
+ * The first call for a scene and device builds a table of primitive numbers and uploads it,
+ * blocking; after that the call only enqueues on `stream`. Scratch comes from the pass pool. */
+int crt_render_features_async(const crt_scene* scene, int device, const crt_camera* cam,
+                              const crt_tiling* tiling, crt_feature* d_feat, void* stream);
+
+/* Per-pixel variance of the mean from the noise state d_noise (t, q per pixel), into d_var
+ * (DEVICE, 1 double per pixel at d_noise's pixel addresses; owned rows only).
+ * n = samples_done when d_blocks is NULL, else the pixel's block word with CRT_BLOCK_STOPPED
+ * cleared (block = crt_block_count's numbering over the owned rows). L = the chunk length of
+ * cam->samples_per_pixel, K = n / L (integer division), both then taken as doubles:
+ *   m = t / (K * L)
+ *   v = max0(q / (L * L) - (K * m) * m) / (K * (K - 1))            for K >= 2,
+ * the square of crt_noise_estimate's se (its operations in its order, without the final sqrt, and
+ * with max0 where it calls fmax: the two differ for -0 and NaN only);
+ *   v = m * m for K == 1 (a finite 100 %-error stand-in), v = 0 for K == 0.
+ * CRT_E_INVALID (the message names the rule) unless samples_done <= samples_per_pixel and it is a
+ * multiple of the chunk length or equals samples_per_pixel; with d_blocks the tiling must have
+ * tile_count == 1 or row_block % 4 == 0, as for crt_adaptive_update. Enqueued on `stream`. */
+int crt_pixel_variance_async(int device, const crt_camera* cam, const crt_tiling* tiling, const double* d_noise,
+                             const uint32_t* d_blocks, uint32_t samples_done, double* d_var, void* stream);
+
+typedef struct crt_denoise_params {
+    uint32_t iterations;        /* 1..8; step of iteration i (from 0) is 2^i                     */
+    uint32_t normal_squarings;  /* 0..10: normal weight = max0(n_p . n_q)^(2^this)               */
+    double sigma_l;             /* colour tolerance in standard errors, finite, > 0              */
+    double sigma_p;             /* plane-distance tolerance as a fraction of t_p, finite, > 0    */
+    uint32_t flags, reserved;   /* must be 0                                                     */
+} crt_denoise_params;
+
+/* The filter. d_rgb (w*h*3), d_var (w*h), d_feat (w*h records): whole-frame, unpacked DEVICE
+ * buffers on `device`; d_out (w*h*3) receives the filtered frame and d_var_out (w*h, or NULL) its
+ * variance. Neither output may overlap an input or the other output (CRT_E_INVALID). Ping-pong
+ * scratch comes from the pass pool. Enqueued on `stream`.
+ * Iteration i = 0 .. iterations - 1 maps the current (c, v) (the inputs at i = 0) to (c', v') with
+ * step = 2^i; for pixel p = (x, y), features n (normal), P (point), t, prim:
+ *   Variance pre-filter: vbar = 0.0; for dy = -1..1 (outer), dx = -1..1 (inner):
+ *       vbar = vbar + (g[dy] * g[dx]) * v(q),  q = (clamp(x + dx, 0, w - 1), clamp(y + dy, 0, h - 1)),
+ *       g = {1/4, 1/2, 1/4}.
+ *   Colour tolerance: D = (sigma_l * sigma_l) * vbar + (1e-6 * (y_p * y_p) + DBL_MIN), y_p = y(c_p).
+ *   Taps: W = 0.0, C[j] = 0.0, V = 0.0; for dy = -2..2 (outer), dx = -2..2 (inner),
+ *       q = (x + step * dx, y + step * dy), k = h[dy] * h[dx], h = {1/16, 1/4, 3/8, 1/4, 1/16}:
+ *     the tap is skipped when q is outside the frame, or when any of c_q's channels or v_q is not
+ *     finite, or when exactly one of prim_p, prim_q is < 0;
+ *     both prims < 0:  N = 1, b = 0;
+ *     otherwise:       N = max0(dot(n_p, n_q)), then N = N * N normal_squarings times,
+ *                      e = dot(P_q - P_p, n_p)  (the differences per component first),
+ *                      b = (e * e) / ((sigma_p * sigma_p) * (t_p * t_p));
+ *     d = y(c_q) - y_p,  a = (d * d) / D,
+ *     w = (k * N) / ((1 + a) * (1 + b))                              (one division)
+ *     W = W + w;  C[j] = C[j] + w * c_q[j] (j = 0, 1, 2);  V = V + (w * w) * v_q.
+ *   Result: c'[j] = C[j] / W, v' = V / (W * W); if any channel of c_p or v_p is not finite, or W
+ *   is not > 0 (a NaN included), the pixel is copied through: c' = c_p, v' = v_p.
+ * The kernels take small steps from an LDS tile and large steps as gathers; both evaluate these
+ * expressions in this order, so the result does not depend on the route. */
+int crt_denoise_async(int device, uint32_t w, uint32_t h, const double* d_rgb, const double* d_var,
+                      const crt_feature* d_feat, const crt_denoise_params* params, double* d_out,
+                      double* d_var_out, void* stream);
+
+/* Blocking denoised render on one device: the passes of crt_render_progressive (adaptive == NULL:
+ * all samples) or the masked passes and updates of crt_render_adaptive (its rules for *adaptive;
+ * flags must be 0), then crt_render_features_async, crt_pixel_variance_async and
+ * crt_denoise_async on the same stream. h_rgb (HOST, image_w*image_h*3) receives the denoised
+ * frame; h_noisy (HOST, same size, or NULL) the unfiltered one, bit for bit the frame of
+ * crt_render_progressive / crt_render_adaptive on one device; *samples_rendered (or NULL) the sum
+ * over the pixels of their sample counts. Multi-GPU denoising is out of scope: the filter reads
+ * neighbours across row blocks, so the devices' frames and noise states would have to be gathered
+ * first. */
+int crt_render_denoised(crt_scene* scene, int device, const crt_camera* cam, const crt_adaptive_params* adaptive,
+                        const crt_denoise_params* denoise, double* h_noisy, double* h_rgb,
+                        uint64_t* samples_rendered);
+
 /* Instrumented pass: counts the work of the same render (never timed). */
 int crt_render_count(const crt_scene* scene, int device, const crt_camera* cam,
                      const crt_tiling* tiling, crt_render_stats* stats);
