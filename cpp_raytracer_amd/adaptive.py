@@ -14,7 +14,7 @@ from typing import Optional
 import numpy as np
 
 from . import CRT_BLOCK_STOPPED, Camera, CrtError, GpuScene, Tiling, adaptive_update, block_count, sample_chunk_len
-from .progressive import ProgressiveRender, _owned_rows
+from .progressive import ProgressiveRender, _resume_job
 
 BLOCK_W, BLOCK_H = 16, 4
 
@@ -29,7 +29,10 @@ def _check_tiling(tiling: Optional[Tiling]) -> None:
 
 
 def _rank_rows(height: int, tiling: Optional[Tiling]) -> int:
-    """The rows the tiling owns (the buffers hold the whole frame unless it is packed)."""
+    """The rows the block state covers (one word per 16 x 4 block of them) and sample_map() lists:
+    the rows the tiling owns, packed or not, the whole frame with no tiling."""
+    # not progressive._owned_rows: an unpacked tiling's pixel buffers hold the whole frame, while
+    # its blocks are numbered over the owned rows only; the two agree for None and packed tilings
     if tiling is None:
         return height
     return sum(1 for r in range(height) if (r // tiling.row_block) % tiling.tile_count == tiling.tile_index)
@@ -122,24 +125,9 @@ class AdaptiveRender(ProgressiveRender):
     def resume(cls, scene: GpuScene, cam: Camera, state: dict, device: int = 0) -> "AdaptiveRender":
         """Continue the render of a state() checkpoint of this job (ProgressiveRender.resume's
         rules, and block words that fit the frame and the checkpoint's samples_done)."""
-        for key, want in (("spp", cam.samples_per_pixel), ("base_seed", cam.base_seed),
-                          ("width", cam.image_w), ("height", cam.image_h)):
-            got = int(state[key])
-            if got != int(want):
-                raise CrtError(f"AdaptiveRender.resume: the state's {key} is {got}, the camera's {int(want)}")
-        done = int(state["samples_done"])
+        done, tiling, rows, total = _resume_job("AdaptiveRender", cam, state, _check_tiling)
         L = sample_chunk_len(cam.samples_per_pixel)
-        if done < 0 or done > cam.samples_per_pixel or (done % L and done != cam.samples_per_pixel):
-            raise CrtError(f"AdaptiveRender.resume: samples_done = {done} is not a pass boundary")
-        tl = [int(v) for v in np.asarray(state["tiling"]).reshape(-1)]
-        tiling = None if tl == [1, 1, 0, 0] else Tiling(*tl)
-        _check_tiling(tiling)
-        rows = _owned_rows(cam.image_h, tiling)
-        total = np.asarray(state["sum"])
         noise = np.asarray(state["noise"]) if "noise" in state else None
-        if total.shape != (rows, cam.image_w, 3) or total.dtype != np.float64:
-            raise CrtError(f"AdaptiveRender.resume: the state's sums have shape {total.shape}, "
-                           f"the job's {(rows, int(cam.image_w), 3)}")
         if noise is None or noise.shape != (rows, cam.image_w, 2):
             raise CrtError("AdaptiveRender.resume: the state has no noise state of the job's shape")
         if "blocks" not in state or "threshold" not in state or "min_samples" not in state:

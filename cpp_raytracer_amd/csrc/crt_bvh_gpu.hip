@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "crt_internal.h"
+#include "crt_hip_util.h"
 
 namespace crt {
 namespace bvhgpu {
@@ -998,9 +999,7 @@ int device_build_bvh(crt_scene* s, uint32_t num_buckets, uint32_t max_leaf, int 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
         return fail(CRT_E_NODEVICE, "GPU BVH build: device " + std::to_string(device) + " not visible");
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(device);
+    DeviceGuard g(device);
     const size_t n = s->prims.size();
     int rc = CRT_OK;
     double* d_pb = nullptr;
@@ -1020,7 +1019,6 @@ int device_build_bvh(crt_scene* s, uint32_t num_buckets, uint32_t max_leaf, int 
 done:
     (void)hipFree(d_pb);
     device_tree_free(t);
-    (void)hipSetDevice(prev);
     return rc;
 }
 

@@ -1,7 +1,7 @@
 // gfx950 denoiser: the edge-stopping a-trous filter of crt_denoise_async (include/crt_render.h
 // states every expression and its order; this file evaluates exactly those, in IEEE f64 with
-// -ffp-contract=off, so tests/denoise_model.py's numpy restatement gives the same bits) and the
-// blocking driver crt_render_denoised.
+// -ffp-contract=off, so tests/denoise_model.py's numpy restatement gives the same bits). The
+// blocking driver crt_render_denoised is in crt_drivers.hip.
 //
 // One iteration is one launch of filter_kernel over 32 x 8 pixel tiles, one thread per pixel.
 // Before the first, pack_kernel packs the inputs into the two records the taps read: the state
@@ -26,17 +26,11 @@
 #include <vector>
 
 #include "crt_internal.h"
+#include "crt_hip_util.h"
 
 #pragma clang fp contract(off)
 
 namespace crt {
-
-#define HIP_TRY(expr)                                                                     \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess)                                                             \
-            return fail(CRT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
-    } while (0)
 
 namespace dn {
 
@@ -266,13 +260,7 @@ int device_denoise(int device, uint32_t w, uint32_t h, const double* d_rgb, cons
     if (n64 >= 0x7fffffffull || w > 0x3fffffffu || h > 0x3fffffffu)
         return fail(CRT_E_INVALID, "crt_denoise_async: frame has more than 2^31-2 pixels");
     const uint32_t n = static_cast<uint32_t>(n64);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    HIP_TRY(hipSetDevice(device));
-    struct Restore {
-        int d;
-        ~Restore() { (void)hipSetDevice(d); }
-    } restore{prev};
+    DeviceGuard g(device);
     void* pool_v = nullptr;
     rc = device_pass_pool(device, &pool_v);
     if (rc) return rc;
@@ -304,95 +292,6 @@ int device_denoise(int device, uint32_t w, uint32_t h, const double* d_rgb, cons
     (void)hipFreeAsync(scratch, st);
     if (e != hipSuccess) return fail(CRT_E_HIP, std::string("denoise kernels: ") + hipGetErrorString(e));
     return CRT_OK;
-}
-
-// crt_render_denoised: one device, one stream. The passes (one plain pass of all samples, or
-// render_adaptive's masked pass and update per step, the frame written by every masked pass), then
-// features, variance and filter behind them on the same stream, and the two frames copied back.
-int render_denoised(crt_scene* s, int device, const crt_camera* cam, const crt_adaptive_params* adaptive,
-                    const crt_denoise_params* denoise, double* h_noisy, double* h_rgb, uint64_t* samples_rendered) {
-    int rc = device_upload(s, device);
-    if (rc) return rc;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    HIP_TRY(hipSetDevice(device));
-    struct Restore {
-        int d;
-        ~Restore() { (void)hipSetDevice(d); }
-    } restore{prev};
-    const size_t W = cam->image_w, H = cam->image_h, px = W * H;
-    const uint32_t N = cam->samples_per_pixel, L = sample_chunk_len(N);
-    const size_t nblk = crt_block_count(cam->image_w, cam->image_h);
-    hipStream_t st = nullptr;
-    double *sum = nullptr, *noise = nullptr, *rgb = nullptr, *var = nullptr, *out = nullptr;
-    crt_feature* feat = nullptr;
-    uint32_t* blocks = nullptr;
-    auto release = [&]() {
-        if (st) (void)hipStreamSynchronize(st);
-        for (void* p : {static_cast<void*>(sum), static_cast<void*>(noise), static_cast<void*>(rgb),
-                        static_cast<void*>(var), static_cast<void*>(out), static_cast<void*>(feat),
-                        static_cast<void*>(blocks)})
-            if (p) (void)hipFree(p);
-        if (st) (void)hipStreamDestroy(st);
-    };
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&sum, px * 3 * sizeof(double)) != hipSuccess || hipMalloc(&noise, px * 2 * sizeof(double)) != hipSuccess ||
-        hipMalloc(&rgb, px * 3 * sizeof(double)) != hipSuccess || hipMalloc(&var, px * sizeof(double)) != hipSuccess ||
-        hipMalloc(&out, px * 3 * sizeof(double)) != hipSuccess || hipMalloc(&feat, px * sizeof(crt_feature)) != hipSuccess ||
-        hipMalloc(&blocks, nblk * sizeof(uint32_t)) != hipSuccess ||
-        hipMemsetAsync(blocks, 0, nblk * sizeof(uint32_t), st) != hipSuccess) {
-        (void)hipGetLastError();
-        release();
-        return fail(CRT_E_HIP, "denoised render: setup failed on device " + std::to_string(device));
-    }
-    uint32_t done = 0;
-    if (!adaptive) {
-        const RenderPass pass{0, N, sum, noise};
-        rc = device_render(s, device, cam, nullptr, rgb, st, nullptr, &pass);
-        done = N;
-    } else {
-        uint64_t per_pass = adaptive->samples_per_pass ? adaptive->samples_per_pass : std::max<uint32_t>(1, N / 10);
-        per_pass = (per_pass + L - 1) / L * L;
-        uint32_t hint = 0;
-        while (rc == CRT_OK && done < N) {
-            const uint32_t count = static_cast<uint32_t>(std::min<uint64_t>(per_pass, N - done));
-            const RenderPass pass{done, count, sum, noise, blocks, hint};
-            rc = device_render(s, device, cam, nullptr, rgb, st, nullptr, &pass);
-            if (rc != CRT_OK) break;
-            done += count;
-            uint32_t active = 0;  // synchronizes the stream
-            rc = device_adaptive_update(device, cam, nullptr, noise, blocks, done, adaptive->threshold,
-                                        adaptive->min_samples, &active, st);
-            hint = std::max(1u, active);
-            if (active == 0) break;
-        }
-    }
-    if (rc == CRT_OK) rc = device_render_features(s, device, cam, nullptr, feat, st);
-    if (rc == CRT_OK) rc = device_pixel_variance(device, cam, nullptr, noise, adaptive ? blocks : nullptr, done, var, st);
-    if (rc == CRT_OK) rc = device_denoise(device, cam->image_w, cam->image_h, rgb, var, feat, denoise, out, nullptr, st);
-    uint64_t rendered = 0;
-    if (rc == CRT_OK) {
-        std::vector<uint32_t> hb(adaptive ? nblk : 0);
-        hipError_t e = hipMemcpyAsync(h_rgb, out, px * 3 * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && h_noisy) e = hipMemcpyAsync(h_noisy, rgb, px * 3 * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && adaptive)
-            e = hipMemcpyAsync(hb.data(), blocks, nblk * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(CRT_E_HIP, std::string("denoised render: ") + hipGetErrorString(e));
-        if (!adaptive) {
-            rendered = static_cast<uint64_t>(done) * px;
-        } else {
-            const size_t tiles_x = (W + CRT_BLOCK_W - 1) / CRT_BLOCK_W;
-            for (size_t b = 0; b < nblk; ++b) {
-                const uint64_t bw = std::min<uint64_t>(CRT_BLOCK_W, W - (b % tiles_x) * CRT_BLOCK_W);
-                const uint64_t bh = std::min<uint64_t>(CRT_BLOCK_H, H - (b / tiles_x) * CRT_BLOCK_H);
-                rendered += (hb[b] & ~CRT_BLOCK_STOPPED) * bw * bh;
-            }
-        }
-    }
-    release();
-    if (samples_rendered) *samples_rendered = rendered;
-    return rc;
 }
 
 }  // namespace crt

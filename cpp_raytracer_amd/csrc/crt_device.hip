@@ -24,18 +24,13 @@
 #include <vector>
 
 #include "crt_internal.h"
+#include "crt_hip_util.h"
+#include "crt_rows.h"
 #include "crt_schlick.h"
 
 #pragma clang fp contract(off)
 
 namespace crt {
-
-#define HIP_TRY(expr)                                                                     \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess)                                                             \
-            return fail(CRT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
-    } while (0)
 
 namespace dev {
 
@@ -2682,12 +2677,6 @@ static int check_device(int device) {
     return CRT_OK;
 }
 
-struct DeviceGuard {
-    int prev = 0;
-    explicit DeviceGuard(int d) { (void)hipGetDevice(&prev); (void)hipSetDevice(d); }
-    ~DeviceGuard() { (void)hipSetDevice(prev); }
-};
-
 static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 // The device image of a scene: every array of device_layout() at its offset in one host buffer,
@@ -2825,7 +2814,7 @@ void device_bind_copy(crt_scene* s, int device, void* base, size_t total) {
 }
 
 // Copy the scene into HBM of `device`: the staged image in one transfer. Uploads to different
-// devices run concurrently (render_multi uploads from one thread per device); the image is
+// devices run concurrently (crt_drivers.hip upload_all: one thread per device); the image is
 // staged once, under the scene's lock. A scene set up on a device (crt_stage_gpu.hip) is copied
 // from that device's HBM instead (its copy there is already in place).
 int device_upload(crt_scene* s, int device) {
@@ -2919,13 +2908,6 @@ static dev::CamView cam_view(const crt_camera* cam) {
     v.max_depth = cam->max_depth;
     v.base_seed = cam->base_seed;
     return v;
-}
-
-static uint32_t count_owned(uint32_t h, uint32_t rb, uint32_t tc, uint32_t ti) {
-    uint32_t n = 0;
-    for (uint32_t r = 0; r < h; ++r)
-        if ((r / rb) % tc == ti) ++n;
-    return n;
 }
 
 static size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
@@ -3047,9 +3029,6 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
         full_chunks = end / W.chunk_len - pass->first / W.chunk_len;
         inv_done = 1 / static_cast<double>(end);
     }
-    W.rb_shift = 32;
-    for (uint32_t sh = 0; sh < 31; ++sh)
-        if ((1u << sh) == W.row_block) W.rb_shift = sh;
     // Bands: rectangles of bx x by tiles over the owned rows x width, each one launch (render +
     // resolve). bx, by <= 65535 (a unit packs its tile as tx | ty << 16), and a band's partial
     // sums (64 pixels x 3 x chunks doubles per tile) fit the budget. A pixel's chunks are summed
@@ -3325,6 +3304,26 @@ static int dispatch_render(const crt_scene* s, int device, const crt_camera* cam
     return launch_render<SE, true, false, 1>(s, device, cam, W, W.ntop, d_rgb, st, count_stats, pass);
 }
 
+// The tiling checked (null: the whole frame as one tile) and W cleared but for its tiling part:
+// which rows the tile owns, how the buffers hold them (packed), the row block's shift.
+static int tiling_work(const crt_camera* cam, const crt_tiling* t, dev::Work& W) {
+    crt_tiling tl{1, 1, 0, 0};
+    if (t) tl = *t;
+    if (tl.flags & ~CRT_TILING_PACKED) return fail(CRT_E_INVALID, "unknown tiling flags");
+    if (tl.row_block == 0 || tl.tile_count == 0 || tl.tile_index >= tl.tile_count)
+        return fail(CRT_E_INVALID, "bad tiling");
+    W = dev::Work{};
+    W.row_block = tl.row_block;
+    W.tile_count = tl.tile_count;
+    W.tile_index = tl.tile_index;
+    W.owned_rows = count_owned(cam->image_h, tl.row_block, tl.tile_count, tl.tile_index);
+    W.packed = (tl.flags & CRT_TILING_PACKED) ? 1u : 0u;
+    W.rb_shift = 32;
+    for (uint32_t sh = 0; sh < 31; ++sh)
+        if ((1u << sh) == W.row_block) W.rb_shift = sh;
+    return CRT_OK;
+}
+
 int device_render(const crt_scene* s, int device, const crt_camera* cam, const crt_tiling* t,
                   double* d_rgb, void* stream, crt_render_stats* count_stats, const RenderPass* pass) {
     int rc = check_device(device);
@@ -3334,18 +3333,10 @@ int device_render(const crt_scene* s, int device, const crt_camera* cam, const c
     if (cam->image_w == 0 || cam->image_h == 0) return fail(CRT_E_INVALID, "empty image");
     if (static_cast<uint64_t>(cam->image_w) * cam->image_h >= 0xffffffffull)
         return fail(CRT_E_INVALID, "image has more than 2^32-1 pixels");
-    crt_tiling tl{1, 1, 0, 0};
-    if (t) tl = *t;
-    if (tl.flags & ~CRT_TILING_PACKED) return fail(CRT_E_INVALID, "unknown tiling flags");
-    if (tl.row_block == 0 || tl.tile_count == 0 || tl.tile_index >= tl.tile_count)
-        return fail(CRT_E_INVALID, "bad tiling");
+    dev::Work W;
+    rc = tiling_work(cam, t, W);
+    if (rc) return rc;
     DeviceGuard g(device);
-    dev::Work W{};
-    W.row_block = tl.row_block;
-    W.tile_count = tl.tile_count;
-    W.tile_index = tl.tile_index;
-    W.owned_rows = count_owned(cam->image_h, tl.row_block, tl.tile_count, tl.tile_index);
-    W.packed = (tl.flags & CRT_TILING_PACKED) ? 1u : 0u;
     if (W.owned_rows == 0 || cam->samples_per_pixel == 0) {
         if (count_stats) *count_stats = crt_render_stats{};
         if (cam->samples_per_pixel == 0 && d_rgb && W.owned_rows) {
@@ -3353,9 +3344,8 @@ int device_render(const crt_scene* s, int device, const crt_camera* cam, const c
             std::vector<double> nanrow(static_cast<size_t>(cam->image_w) * 3,
                                        std::numeric_limits<double>::quiet_NaN());
             for (uint32_t k = 0; k < W.owned_rows; ++k) {
-                uint32_t blk = k / W.row_block, in = k % W.row_block;
-                uint32_t row = (tl.flags & CRT_TILING_PACKED) ? k : (blk * W.tile_count + W.tile_index) * W.row_block + in;
-                HIP_TRY(hipMemcpyAsync(d_rgb + static_cast<size_t>(row) * cam->image_w * 3, nanrow.data(),
+                const size_t row = owned_to_frame_row(k, W.row_block, W.tile_count, W.tile_index, W.packed != 0);
+                HIP_TRY(hipMemcpyAsync(d_rgb + row * cam->image_w * 3, nanrow.data(),
                                        nanrow.size() * 8, hipMemcpyHostToDevice,
                                        static_cast<hipStream_t>(stream)));
             }
@@ -3482,257 +3472,22 @@ int device_ppm_values(int device, const double* d_rgb, size_t n, int32_t* h_valu
     return CRT_OK;
 }
 
-// Peer access from device `to` to device `from`'s memory, enabled once per pair per process
-// (hipDeviceEnablePeerAccess fails with AlreadyEnabled on a repeat call; HIP keeps such an error as
-// the thread's last error, so it is read off here, not left for a later hipGetLastError).
-static void enable_peer_once(int to, int from) {
-    static std::mutex mu;
-    static bool done[kMaxDevices][kMaxDevices] = {};
-    std::lock_guard<std::mutex> lk(mu);
-    if (done[to][from]) return;
-    done[to][from] = true;
-    int can = 0;
-    if (hipDeviceCanAccessPeer(&can, to, from) != hipSuccess || !can) {
-        (void)hipGetLastError();
-        return;  // the copies still work, staged by the runtime
-    }
-    DeviceGuard g(to);
-    if (hipDeviceEnablePeerAccess(from, 0) != hipSuccess) (void)hipGetLastError();
+// ---- launchers of the kernels the blocking drivers (crt_drivers.hip) run themselves: one launch
+// on `stream` of the current device each; false when the launch failed
+bool device_ppm8(const double* d_rgb, uint64_t px, uint8_t* d_out, uint32_t* d_redo, uint32_t redo_cap, void* stream) {
+    hipLaunchKernelGGL(dev::ppm8_kernel, dim3(static_cast<uint32_t>((px + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), d_rgb, px, d_out, d_redo, redo_cap);
+    return hipGetLastError() == hipSuccess;
 }
-
-// Device d's owned rows (crt_tiling{rb, n, d}) are packed in its buffer; copy them to their frame
-// rows in `dst` (on device 0): full rb-row blocks with one strided copy (rb rows apart in the
-// source, n x rb rows apart in the frame), a short last block on its own. bytes_per_row: one row.
-static hipError_t gather_packed(char* dst, const char* src, size_t H, size_t rb, int n, int d,
-                                size_t bytes_per_row, hipStream_t st) {
-    const size_t first = static_cast<size_t>(d) * rb, step = static_cast<size_t>(n) * rb;
-    if (first >= H) return hipSuccess;
-    const size_t blocks = (H - first + step - 1) / step;     // blocks of device d
-    const size_t last = first + (blocks - 1) * step;         // frame row of its last block
-    const size_t full = last + rb <= H ? blocks : blocks - 1; // blocks with all rb rows
-    hipError_t e = hipSuccess;
-    if (full)
-        e = hipMemcpy2DAsync(dst + first * bytes_per_row, step * bytes_per_row, src, rb * bytes_per_row,
-                             rb * bytes_per_row, full, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && full < blocks)
-        e = hipMemcpyAsync(dst + last * bytes_per_row, src + full * rb * bytes_per_row, (H - last) * bytes_per_row,
-                           hipMemcpyDeviceToDevice, st);
-    return e;
+bool device_redo_gather(const double* d_rgb, const uint32_t* d_list, uint32_t n, double* d_out, void* stream) {
+    hipLaunchKernelGGL(dev::redo_gather_kernel, dim3(static_cast<uint32_t>((static_cast<uint64_t>(n) + 255) / 256)),
+                       dim3(256), 0, static_cast<hipStream_t>(stream), d_rgb, d_list, n, d_out);
+    return hipGetLastError() == hipSuccess;
 }
-
-// crt_render / crt_render_ppm: the whole frame over devices [0, n). Rows are dealt in 4-row
-// blocks (row r on device (r / 4) % n, crt_tiling{4, n, d}); the scene is uploaded to every device
-// concurrently (one host thread per device, one copy of the staged image each); each device renders
-// its own rows only, packed (CRT_TILING_PACKED: a device holds its share of the frame, 1/n of it)
-// on its own stream; device 0's stream then waits for each device and pulls that device's row
-// blocks into the frame with ONE strided peer copy (hipMemcpy2DAsync over xGMI), and the assembled
-// frame crosses PCIe once. Frames are bit-identical for any n (per-sample RNG, spp-only sample
-// chunks).
-//   h_rgb (f64 frame, crt_render): 24 B a pixel cross xGMI and PCIe; device 0 renders straight
-//     into the frame.
-//   h_ppm (int32 PPM values, crt_render_ppm; image.h:38-56, rgb.h:90-115): every device converts
-//     its rows to 8-bit PPM values before the gather (ppm8_kernel), so 3 B a pixel cross xGMI and
-//     PCIe; the few pixels the kernel leaves to the host (NaN, out of range, or within 2 ulps of
-//     an integer step) are recomputed from their f64 values with std::pow (ppm_pixel_host).
-// CRT_EMULATE_DEVICES=k (tests): k logical devices all on device 0, through the same tiling and
-// gather code.
-static int render_multi_impl(crt_scene* s, const crt_camera* cam, int num_devices, double* h_rgb,
-                             int32_t* h_ppm, crt_render_stats* stats) {
-    int avail = 0;
-    if (hipGetDeviceCount(&avail) != hipSuccess || avail == 0)
-        return fail(CRT_E_NODEVICE, "no HIP device visible (the render path has no CPU fallback)");
-    if (num_devices <= 0) num_devices = avail;
-    num_devices = std::min(num_devices, std::min(avail, kMaxDevices));
-    bool emulate = false;
-    if (const char* e = std::getenv("CRT_EMULATE_DEVICES")) {
-        num_devices = std::max(1, std::min(std::atoi(e), 64));
-        emulate = true;
-    }
-    const int n = num_devices;
-    const bool ppm = h_ppm != nullptr;
-    auto phys = [&](int d) { return emulate ? 0 : d; };
-    const size_t W = cam->image_w, H = cam->image_h;
-    const uint32_t rb = 4;  // 4-row blocks: 800 rows split exactly over 1, 2, 4, 8 devices
-    // 1. concurrent uploads, one thread per physical device; a worker's error message is taken
-    // from its own thread (crt_last_error is per thread) and raised again on this one
-    const int n_phys = emulate ? 1 : n;
-    std::vector<int> urc(n_phys, CRT_OK);
-    std::vector<std::string> umsg(n_phys);
-    {
-        std::vector<std::thread> th;
-        for (int d = 0; d < n_phys; ++d)
-            th.emplace_back([&, d] {
-                urc[d] = device_upload(s, d);
-                if (urc[d]) umsg[d] = crt_last_error();
-            });
-        for (auto& t : th) t.join();
-    }
-    for (int d = 0; d < n_phys; ++d)
-        if (urc[d]) return fail(urc[d], "device " + std::to_string(d) + ": " + umsg[d]);
-    // 2. render: each logical device its own rows on its own stream (f64 mode: device 0 into the
-    // whole frame, the others packed; ppm mode: every device packed, then to 8-bit values)
-    std::vector<double*> bufs(n, nullptr);
-    std::vector<uint8_t*> b8(n, nullptr);
-    std::vector<uint32_t*> redo(n, nullptr);  // [count, indices...] per device (ppm mode)
-    std::vector<size_t> rows(n, 0);
-    std::vector<hipStream_t> streams(n, nullptr);
-    std::vector<hipEvent_t> ev0(n, nullptr), ev1(n, nullptr);
-    constexpr uint32_t kRedoCap = 1u << 16;
-    int rc = CRT_OK;
-    for (int d = 0; d < n && rc == CRT_OK; ++d) {
-        DeviceGuard g(phys(d));
-        rows[d] = count_owned(cam->image_h, rb, static_cast<uint32_t>(n), static_cast<uint32_t>(d));
-        const bool packed = ppm || d > 0;
-        const size_t px = (packed ? rows[d] : H) * W;
-        if (hipStreamCreateWithFlags(&streams[d], hipStreamNonBlocking) != hipSuccess ||
-            hipMalloc(&bufs[d], std::max<size_t>(1, px) * 3 * sizeof(double)) != hipSuccess ||
-            (ppm && hipMalloc(&b8[d], std::max<size_t>(1, px) * 3) != hipSuccess) ||
-            (ppm && hipMalloc(&redo[d], (1 + kRedoCap) * sizeof(uint32_t)) != hipSuccess) ||
-            hipEventCreate(&ev0[d]) != hipSuccess || hipEventCreate(&ev1[d]) != hipSuccess) {
-            (void)hipGetLastError();
-            rc = fail(CRT_E_HIP, "render: per-device setup failed on device " + std::to_string(phys(d)));
-            break;
-        }
-        crt_tiling t{rb, static_cast<uint32_t>(n), static_cast<uint32_t>(d), packed ? CRT_TILING_PACKED : 0u};
-        (void)hipEventRecord(ev0[d], streams[d]);
-        rc = device_render(s, phys(d), cam, &t, bufs[d], streams[d], nullptr);
-        if (rc == CRT_OK && ppm && px) {
-            if (hipMemsetAsync(redo[d], 0, sizeof(uint32_t), streams[d]) != hipSuccess) {
-                rc = fail(CRT_E_HIP, "render: redo counter");
-                break;
-            }
-            hipLaunchKernelGGL(dev::ppm8_kernel, dim3(static_cast<uint32_t>((px + 255) / 256)), dim3(256), 0, streams[d],
-                               bufs[d], static_cast<uint64_t>(px), b8[d], redo[d], kRedoCap);
-            if (hipGetLastError() != hipSuccess) rc = fail(CRT_E_HIP, "render: ppm8_kernel launch");
-        }
-        (void)hipEventRecord(ev1[d], streams[d]);
-    }
-    // 3. gather into device 0: one strided copy per device, then one device-to-host copy
-    uint8_t* frame8 = nullptr;
-    std::vector<uint8_t> h8;
-    if (rc == CRT_OK) {
-        DeviceGuard g(0);
-        if (ppm && hipMalloc(&frame8, std::max<size_t>(1, H * W * 3)) != hipSuccess) {
-            (void)hipGetLastError();
-            rc = fail(CRT_E_HIP, "render: frame buffer");
-        }
-        const size_t row_bytes = W * 3 * (ppm ? 1 : sizeof(double));
-        for (int d = ppm ? 0 : 1; d < n && rc == CRT_OK; ++d) {
-            if (!emulate && d > 0) enable_peer_once(0, d);
-            if (hipStreamWaitEvent(streams[0], ev1[d], 0) != hipSuccess) {
-                rc = fail(CRT_E_HIP, "render: gather wait failed");
-                break;
-            }
-            const hipError_t e = ppm ? gather_packed(reinterpret_cast<char*>(frame8), reinterpret_cast<const char*>(b8[d]),
-                                                     H, rb, n, d, row_bytes, streams[0])
-                                     : gather_packed(reinterpret_cast<char*>(bufs[0]), reinterpret_cast<const char*>(bufs[d]),
-                                                     H, rb, n, d, row_bytes, streams[0]);
-            if (e != hipSuccess) rc = fail(CRT_E_HIP, std::string("render: gather from device ") +
-                                                         std::to_string(d) + ": " + hipGetErrorString(e));
-        }
-        if (rc == CRT_OK) {
-            hipError_t e;
-            if (ppm) {
-                h8.resize(H * W * 3);
-                e = hipMemcpyAsync(h8.data(), frame8, h8.size(), hipMemcpyDeviceToHost, streams[0]);
-            } else {
-                e = hipMemcpyAsync(h_rgb, bufs[0], H * W * 3 * sizeof(double), hipMemcpyDeviceToHost, streams[0]);
-            }
-            if (e == hipSuccess) e = hipStreamSynchronize(streams[0]);
-            if (e != hipSuccess) rc = fail(CRT_E_HIP, std::string("render: ") + hipGetErrorString(e));
-        }
-    }
-    float max_ms = 0;
-    for (int d = 0; d < n; ++d) {
-        if (!streams[d]) continue;
-        DeviceGuard g(phys(d));
-        hipError_t e = hipStreamSynchronize(streams[d]);
-        if (e != hipSuccess && rc == CRT_OK)
-            rc = fail(CRT_E_HIP, std::string("render on device ") + std::to_string(phys(d)) + ": " + hipGetErrorString(e));
-        float ms = 0;
-        if (rc == CRT_OK && hipEventElapsedTime(&ms, ev0[d], ev1[d]) == hipSuccess) max_ms = std::max(max_ms, ms);
-    }
-    // 4. ppm mode: 8-bit values to int32, and the pixels each device left to the host
-    if (rc == CRT_OK && ppm) {
-        for (size_t i = 0; i < H * W * 3; ++i) h_ppm[i] = h8[i];
-        for (int d = 0; d < n && rc == CRT_OK; ++d) {
-            if (!rows[d]) continue;
-            DeviceGuard g(phys(d));
-            uint32_t cnt = 0;
-            if (hipMemcpy(&cnt, redo[d], sizeof cnt, hipMemcpyDeviceToHost) != hipSuccess) {
-                rc = fail(CRT_E_HIP, "render: redo count");
-                break;
-            }
-            if (!cnt) continue;
-            const size_t px = rows[d] * W;
-            std::vector<uint32_t> idx;
-            if (cnt <= kRedoCap) {  // the listed pixels
-                idx.resize(cnt);
-                if (hipMemcpy(idx.data(), redo[d] + 1, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) {
-                    rc = fail(CRT_E_HIP, "render: redo list");
-                    break;
-                }
-            }
-            std::vector<double> rgb(cnt <= kRedoCap ? 3 * idx.size() : 3 * px);
-            const bool whole = cnt > kRedoCap;  // more than the list holds: every pixel of the device
-            if (whole) {
-                if (hipMemcpy(rgb.data(), bufs[d], 3 * px * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = CRT_E_HIP;
-            } else {
-                // the listed pixels gathered on the device, then one copy (not one per pixel)
-                double* packed = nullptr;
-                if (hipMalloc(&packed, 3 * idx.size() * sizeof(double)) != hipSuccess) {
-                    rc = CRT_E_HIP;
-                } else {
-                    hipLaunchKernelGGL(dev::redo_gather_kernel, dim3(static_cast<uint32_t>((idx.size() + 255) / 256)), dim3(256),
-                                       0, nullptr, bufs[d], redo[d] + 1, static_cast<uint32_t>(idx.size()), packed);
-                    if (hipGetLastError() != hipSuccess ||
-                        hipMemcpy(rgb.data(), packed, 3 * idx.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-                        rc = CRT_E_HIP;
-                    (void)hipFree(packed);
-                }
-            }
-            if (rc != CRT_OK) {
-                rc = fail(CRT_E_HIP, "render: redo pixels");
-                break;
-            }
-            const size_t m = whole ? px : idx.size();
-            for (size_t j = 0; j < m; ++j) {
-                const size_t k = whole ? j : idx[j];  // packed pixel index on device d
-                const size_t kr = k / W, col = k % W;
-                const size_t row = (kr / rb * static_cast<size_t>(n) + static_cast<size_t>(d)) * rb + kr % rb;
-                ppm_pixel_host(rgb.data() + 3 * j, h_ppm + 3 * (row * W + col));
-            }
-        }
-    }
-    for (int d = 0; d < n; ++d) {
-        DeviceGuard g(phys(d));
-        if (bufs[d]) (void)hipFree(bufs[d]);
-        if (b8[d]) (void)hipFree(b8[d]);
-        if (redo[d]) (void)hipFree(redo[d]);
-        if (streams[d]) (void)hipStreamDestroy(streams[d]);
-        if (ev0[d]) (void)hipEventDestroy(ev0[d]);
-        if (ev1[d]) (void)hipEventDestroy(ev1[d]);
-    }
-    if (frame8) {
-        DeviceGuard g(0);
-        (void)hipFree(frame8);
-    }
-    if (stats && rc == CRT_OK) {
-        *stats = crt_render_stats{};
-        stats->samples = static_cast<uint64_t>(cam->image_w) * cam->image_h * cam->samples_per_pixel;
-        stats->kernel_ms = max_ms;
-    }
-    return rc;
-}
-
-int render_multi(crt_scene* s, const crt_camera* cam, int num_devices, double* h_rgb,
-                 crt_render_stats* stats) {
-    return render_multi_impl(s, cam, num_devices, h_rgb, nullptr, stats);
-}
-
-int render_multi_ppm(crt_scene* s, const crt_camera* cam, int num_devices, int32_t* h_values,
-                     crt_render_stats* stats) {
-    return render_multi_impl(s, cam, num_devices, nullptr, h_values, stats);
+bool device_scale(const double* d_sum, double* d_out, uint64_t count, double factor, void* stream) {
+    hipLaunchKernelGGL(dev::scale_kernel, dim3(static_cast<uint32_t>((count + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), d_sum, d_out, count, factor);
+    return hipGetLastError() == hipSuccess;
 }
 
 // crt_noise_estimate: sum se and sum m over `pixels` noise records (noise_stage1_kernel). K = the
@@ -3769,178 +3524,9 @@ int device_noise_estimate(int device, const double* d_noise, size_t pixels, uint
     return CRT_OK;
 }
 
-// crt_render_progressive: render_multi_impl's layout (rows dealt in 4-row blocks, one stream per
-// logical device, the gather into device 0, CRT_EMULATE_DEVICES) with the samples cut into passes.
-// Every device keeps its packed running sums (and noise state) for the whole job and renders each
-// pass into them (device_render with a RenderPass); a frame is resolved and gathered only when
-// somebody looks at it: after every pass with CRT_PROGRESS_PREVIEW, else once at the end or when
-// the callback stops the job. A pixel's samples stay on one device, in order, so the final frame
-// is crt_render's bit for bit.
-int render_progressive(crt_scene* s, const crt_camera* cam, int num_devices, uint32_t samples_per_pass,
-                       uint32_t flags, crt_progress_fn fn, void* user, double* h_rgb, uint32_t* samples_done) {
-    int avail = 0;
-    if (hipGetDeviceCount(&avail) != hipSuccess || avail == 0)
-        return fail(CRT_E_NODEVICE, "no HIP device visible (the render path has no CPU fallback)");
-    if (num_devices <= 0) num_devices = avail;
-    num_devices = std::min(num_devices, std::min(avail, kMaxDevices));
-    bool emulate = false;
-    if (const char* e = std::getenv("CRT_EMULATE_DEVICES")) {
-        num_devices = std::max(1, std::min(std::atoi(e), 64));
-        emulate = true;
-    }
-    const int n = num_devices;
-    auto phys = [&](int d) { return emulate ? 0 : d; };
-    const size_t W = cam->image_w, H = cam->image_h;
-    const uint32_t N = cam->samples_per_pixel, L = sample_chunk_len(N);
-    const uint32_t rb = 4;
-    const bool want_noise = (flags & CRT_PROGRESS_NOISE) != 0, want_preview = (flags & CRT_PROGRESS_PREVIEW) != 0;
-    // samples per pass: whole chunks; 0 = a tenth of the job
-    uint64_t per_pass = samples_per_pass ? samples_per_pass : std::max<uint32_t>(1, N / 10);
-    per_pass = (per_pass + L - 1) / L * L;
-    const int n_phys = emulate ? 1 : n;
-    for (int d = 0; d < n_phys; ++d) {
-        const int rc = device_upload(s, d);
-        if (rc) return rc;
-    }
-    std::vector<double*> sums(n, nullptr), noise(n, nullptr), bufs(n, nullptr);
-    std::vector<size_t> px(n, 0);
-    std::vector<hipStream_t> streams(n, nullptr);
-    std::vector<hipEvent_t> ev(n, nullptr);
-    double* frame = nullptr;
-    int rc = CRT_OK;
-    for (int d = 0; d < n && rc == CRT_OK; ++d) {
-        DeviceGuard g(phys(d));
-        px[d] = static_cast<size_t>(count_owned(cam->image_h, rb, static_cast<uint32_t>(n), static_cast<uint32_t>(d))) * W;
-        const size_t bytes = std::max<size_t>(1, px[d]) * 3 * sizeof(double);
-        if (hipStreamCreateWithFlags(&streams[d], hipStreamNonBlocking) != hipSuccess ||
-            hipMalloc(&sums[d], bytes) != hipSuccess || hipMalloc(&bufs[d], bytes) != hipSuccess ||
-            (want_noise && hipMalloc(&noise[d], std::max<size_t>(1, px[d]) * 2 * sizeof(double)) != hipSuccess) ||
-            hipEventCreate(&ev[d]) != hipSuccess) {
-            (void)hipGetLastError();
-            rc = fail(CRT_E_HIP, "progressive render: per-device setup failed on device " + std::to_string(phys(d)));
-        }
-    }
-    if (rc == CRT_OK) {
-        DeviceGuard g(0);
-        if (hipMalloc(&frame, std::max<size_t>(1, H * W) * 3 * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            rc = fail(CRT_E_HIP, "progressive render: frame buffer");
-        }
-    }
-    // every device's resolved rows (bufs) into the frame on device 0, then to h_rgb; blocking
-    auto gather = [&]() -> int {
-        DeviceGuard g(0);
-        for (int d = 0; d < n; ++d) {
-            if (!emulate && d > 0) enable_peer_once(0, d);
-            {
-                DeviceGuard gd(phys(d));
-                if (hipEventRecord(ev[d], streams[d]) != hipSuccess) return fail(CRT_E_HIP, "progressive render: event");
-            }
-            if (d > 0 && hipStreamWaitEvent(streams[0], ev[d], 0) != hipSuccess)
-                return fail(CRT_E_HIP, "progressive render: gather wait failed");
-            const hipError_t e = gather_packed(reinterpret_cast<char*>(frame), reinterpret_cast<const char*>(bufs[d]), H, rb,
-                                               n, d, W * 3 * sizeof(double), streams[0]);
-            if (e != hipSuccess)
-                return fail(CRT_E_HIP, std::string("progressive render: gather from device ") + std::to_string(d) + ": " +
-                                           hipGetErrorString(e));
-        }
-        hipError_t e = hipMemcpyAsync(h_rgb, frame, H * W * 3 * sizeof(double), hipMemcpyDeviceToHost, streams[0]);
-        if (e == hipSuccess) e = hipStreamSynchronize(streams[0]);
-        if (e != hipSuccess) return fail(CRT_E_HIP, std::string("progressive render: ") + hipGetErrorString(e));
-        return CRT_OK;
-    };
-    uint32_t done = 0;
-    bool have_frame = false;
-    while (rc == CRT_OK && done < N) {
-        const uint32_t count = static_cast<uint32_t>(std::min<uint64_t>(per_pass, N - done));
-        const bool last = done + count == N;
-        have_frame = last || (want_preview && fn);
-        for (int d = 0; d < n && rc == CRT_OK; ++d) {
-            crt_tiling t{rb, static_cast<uint32_t>(n), static_cast<uint32_t>(d), CRT_TILING_PACKED};
-            const RenderPass pass{done, count, sums[d], noise[d]};
-            rc = device_render(s, phys(d), cam, &t, have_frame ? bufs[d] : nullptr, streams[d], nullptr, &pass);
-        }
-        if (rc != CRT_OK) break;
-        done += count;
-        double figure = std::numeric_limits<double>::quiet_NaN();
-        if (want_noise && fn) {  // sum se / sum m over the devices' pixels, in device order
-            double se = 0, mean = 0;
-            bool any = false;
-            for (int d = 0; d < n && rc == CRT_OK; ++d) {
-                if (!px[d]) continue;
-                double a = 0, b = 0;
-                rc = device_noise_estimate(phys(d), noise[d], px[d], N, done, &a, &b, streams[d]);
-                se += a;
-                mean += b;
-                any = true;
-            }
-            if (rc != CRT_OK) break;
-            if (any) figure = se / mean;
-        }
-        if (have_frame) {
-            rc = gather();
-        } else {
-            for (int d = 0; d < n && rc == CRT_OK; ++d) {
-                DeviceGuard g(phys(d));
-                const hipError_t e = hipStreamSynchronize(streams[d]);
-                if (e != hipSuccess)
-                    rc = fail(CRT_E_HIP, std::string("render on device ") + std::to_string(phys(d)) + ": " + hipGetErrorString(e));
-            }
-        }
-        if (rc != CRT_OK) break;
-        if (fn && fn(user, done, N, figure, want_preview ? h_rgb : nullptr) != 0) break;
-    }
-    // stopped between previews: the mean of the samples so far from the running sums
-    if (rc == CRT_OK && !have_frame && done > 0) {
-        for (int d = 0; d < n && rc == CRT_OK; ++d) {
-            if (!px[d]) continue;
-            DeviceGuard g(phys(d));
-            const uint64_t cnt = static_cast<uint64_t>(px[d]) * 3;
-            hipLaunchKernelGGL(dev::scale_kernel, dim3(static_cast<uint32_t>((cnt + 255) / 256)), dim3(256), 0, streams[d],
-                               sums[d], bufs[d], cnt, 1 / static_cast<double>(done));
-            if (hipGetLastError() != hipSuccess) rc = fail(CRT_E_HIP, "progressive render: scale_kernel launch");
-        }
-        if (rc == CRT_OK) rc = gather();
-    }
-    for (int d = 0; d < n; ++d) {
-        DeviceGuard g(phys(d));
-        if (streams[d]) (void)hipStreamSynchronize(streams[d]);
-        if (sums[d]) (void)hipFree(sums[d]);
-        if (noise[d]) (void)hipFree(noise[d]);
-        if (bufs[d]) (void)hipFree(bufs[d]);
-        if (streams[d]) (void)hipStreamDestroy(streams[d]);
-        if (ev[d]) (void)hipEventDestroy(ev[d]);
-    }
-    if (frame) {
-        DeviceGuard g(0);
-        (void)hipFree(frame);
-    }
-    if (samples_done) *samples_done = done;
-    return rc;
-}
-
 // ---- adaptive sampling (host side) ---------------------------------------------------------
 bool adaptive_tiling_ok(const crt_tiling* t) {
     return !t || t->tile_count == 1 || (t->row_block != 0 && t->row_block % dev::kTileH == 0);
-}
-
-// the tiling part of a Work (owned_row, packed) for the kernels that address pixels by owned row
-static int tiling_work(const crt_camera* cam, const crt_tiling* t, dev::Work& W) {
-    crt_tiling tl{1, 1, 0, 0};
-    if (t) tl = *t;
-    if (tl.flags & ~CRT_TILING_PACKED) return fail(CRT_E_INVALID, "unknown tiling flags");
-    if (tl.row_block == 0 || tl.tile_count == 0 || tl.tile_index >= tl.tile_count)
-        return fail(CRT_E_INVALID, "bad tiling");
-    W = dev::Work{};
-    W.row_block = tl.row_block;
-    W.tile_count = tl.tile_count;
-    W.tile_index = tl.tile_index;
-    W.owned_rows = count_owned(cam->image_h, tl.row_block, tl.tile_count, tl.tile_index);
-    W.packed = (tl.flags & CRT_TILING_PACKED) ? 1u : 0u;
-    W.rb_shift = 32;
-    for (uint32_t sh = 0; sh < 31; ++sh)
-        if ((1u << sh) == W.row_block) W.rb_shift = sh;
-    return CRT_OK;
 }
 
 static uint32_t block_count(uint32_t w, uint32_t rows) {
@@ -3980,6 +3566,27 @@ int device_adaptive_update(int device, const crt_camera* cam, const crt_tiling* 
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(CRT_E_HIP, std::string("adaptive update: ") + hipGetErrorString(e));
     *active_blocks = h;
+    return CRT_OK;
+}
+
+// The frame of an adaptive render from its running sums, on `stream` of the current device: every
+// block's sum times 1 / its own count (accumulate_masked_kernel without partial sums).
+int device_frame_from_sums(const crt_camera* cam, const crt_tiling* t, double* d_sum, uint32_t* d_blocks,
+                           double* d_rgb, void* stream) {
+    dev::Work W;
+    const int rc = tiling_work(cam, t, W);
+    if (rc) return rc;
+    const uint32_t tiles_x = (cam->image_w + dev::kTileW - 1) / dev::kTileW;
+    W.bw = cam->image_w;
+    W.bh = W.owned_rows;
+    W.tiles_x = tiles_x;
+    W.tiles_y = (W.owned_rows + dev::kTileH - 1) / dev::kTileH;
+    W.tiles = block_count(cam->image_w, W.owned_rows);
+    W.s0 = ~0u;  // no block word equals it: every tile takes the skipped branch
+    hipLaunchKernelGGL(dev::accumulate_masked_kernel, dim3((W.tiles + 3) / 4), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), nullptr, d_sum, nullptr, d_rgb, d_blocks, W, cam->image_w,
+                       tiles_x, 0u, 0u, 0.0);
+    if (hipGetLastError() != hipSuccess) return fail(CRT_E_HIP, "adaptive render: frame kernel launch");
     return CRT_OK;
 }
 
@@ -4078,183 +3685,6 @@ int device_pixel_variance(int device, const crt_camera* cam, const crt_tiling* t
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(CRT_E_HIP, std::string("pixel_variance_kernel launch: ") + hipGetErrorString(e));
     return CRT_OK;
-}
-
-// crt_render_adaptive: render_progressive's layout (rows dealt in 4-row blocks, so a device's
-// blocks are blocks of the frame; packed running sums and noise state per device; the gather into
-// device 0; CRT_EMULATE_DEVICES) with a block state per device: every step is one masked pass and
-// one update on every device, and a device's last active count is its next pass's hint. The frame
-// is each block's sum times 1 / its own count: written by the masked passes with
-// CRT_PROGRESS_PREVIEW, else once at the end (accumulate_masked_kernel without partial sums).
-int render_adaptive(crt_scene* s, const crt_camera* cam, int num_devices, const crt_adaptive_params* prm,
-                    crt_adaptive_fn fn, void* user, double* h_rgb, uint32_t* h_block_samples,
-                    uint64_t* samples_rendered) {
-    int avail = 0;
-    if (hipGetDeviceCount(&avail) != hipSuccess || avail == 0)
-        return fail(CRT_E_NODEVICE, "no HIP device visible (the render path has no CPU fallback)");
-    if (num_devices <= 0) num_devices = avail;
-    num_devices = std::min(num_devices, std::min(avail, kMaxDevices));
-    bool emulate = false;
-    if (const char* e = std::getenv("CRT_EMULATE_DEVICES")) {
-        num_devices = std::max(1, std::min(std::atoi(e), 64));
-        emulate = true;
-    }
-    const int n = num_devices;
-    auto phys = [&](int d) { return emulate ? 0 : d; };
-    const size_t W = cam->image_w, H = cam->image_h;
-    const uint32_t N = cam->samples_per_pixel, L = sample_chunk_len(N);
-    const uint32_t rb = 4;
-    const bool want_preview = (prm->flags & CRT_PROGRESS_PREVIEW) != 0;
-    uint64_t per_pass = prm->samples_per_pass ? prm->samples_per_pass : std::max<uint32_t>(1, N / 10);
-    per_pass = (per_pass + L - 1) / L * L;
-    const int n_phys = emulate ? 1 : n;
-    for (int d = 0; d < n_phys; ++d) {
-        const int rc = device_upload(s, d);
-        if (rc) return rc;
-    }
-    const uint32_t tiles_x = static_cast<uint32_t>((W + dev::kTileW - 1) / dev::kTileW);
-    const uint32_t total_blocks = block_count(cam->image_w, cam->image_h);
-    std::vector<double*> sums(n, nullptr), noise(n, nullptr), bufs(n, nullptr);
-    std::vector<uint32_t*> blocks(n, nullptr);
-    std::vector<uint32_t> rows(n, 0), nblk(n, 0), hint(n, 0);
-    std::vector<hipStream_t> streams(n, nullptr);
-    std::vector<hipEvent_t> ev(n, nullptr);
-    double* frame = nullptr;
-    int rc = CRT_OK;
-    for (int d = 0; d < n && rc == CRT_OK; ++d) {
-        DeviceGuard g(phys(d));
-        rows[d] = count_owned(cam->image_h, rb, static_cast<uint32_t>(n), static_cast<uint32_t>(d));
-        nblk[d] = block_count(cam->image_w, rows[d]);
-        const size_t px = std::max<size_t>(1, static_cast<size_t>(rows[d]) * W);
-        const size_t bb = std::max<size_t>(1, nblk[d]) * sizeof(uint32_t);
-        if (hipStreamCreateWithFlags(&streams[d], hipStreamNonBlocking) != hipSuccess ||
-            hipMalloc(&sums[d], px * 3 * sizeof(double)) != hipSuccess ||
-            hipMalloc(&bufs[d], px * 3 * sizeof(double)) != hipSuccess ||
-            hipMalloc(&noise[d], px * 2 * sizeof(double)) != hipSuccess || hipMalloc(&blocks[d], bb) != hipSuccess ||
-            hipMemsetAsync(blocks[d], 0, bb, streams[d]) != hipSuccess || hipEventCreate(&ev[d]) != hipSuccess) {
-            (void)hipGetLastError();
-            rc = fail(CRT_E_HIP, "adaptive render: per-device setup failed on device " + std::to_string(phys(d)));
-        }
-    }
-    if (rc == CRT_OK) {
-        DeviceGuard g(0);
-        if (hipMalloc(&frame, std::max<size_t>(1, H * W) * 3 * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            rc = fail(CRT_E_HIP, "adaptive render: frame buffer");
-        }
-    }
-    auto gather = [&]() -> int {
-        DeviceGuard g(0);
-        for (int d = 0; d < n; ++d) {
-            if (!emulate && d > 0) enable_peer_once(0, d);
-            {
-                DeviceGuard gd(phys(d));
-                if (hipEventRecord(ev[d], streams[d]) != hipSuccess) return fail(CRT_E_HIP, "adaptive render: event");
-            }
-            if (d > 0 && hipStreamWaitEvent(streams[0], ev[d], 0) != hipSuccess)
-                return fail(CRT_E_HIP, "adaptive render: gather wait failed");
-            const hipError_t e = gather_packed(reinterpret_cast<char*>(frame), reinterpret_cast<const char*>(bufs[d]), H, rb,
-                                               n, d, W * 3 * sizeof(double), streams[0]);
-            if (e != hipSuccess)
-                return fail(CRT_E_HIP, std::string("adaptive render: gather from device ") + std::to_string(d) + ": " +
-                                           hipGetErrorString(e));
-        }
-        hipError_t e = hipMemcpyAsync(h_rgb, frame, H * W * 3 * sizeof(double), hipMemcpyDeviceToHost, streams[0]);
-        if (e == hipSuccess) e = hipStreamSynchronize(streams[0]);
-        if (e != hipSuccess) return fail(CRT_E_HIP, std::string("adaptive render: ") + hipGetErrorString(e));
-        return CRT_OK;
-    };
-    uint32_t done = 0;
-    bool have_frame = false;
-    while (rc == CRT_OK && done < N) {
-        const uint32_t count = static_cast<uint32_t>(std::min<uint64_t>(per_pass, N - done));
-        have_frame = want_preview && fn;
-        for (int d = 0; d < n && rc == CRT_OK; ++d) {
-            if (!rows[d]) continue;
-            crt_tiling t{rb, static_cast<uint32_t>(n), static_cast<uint32_t>(d), CRT_TILING_PACKED};
-            const RenderPass pass{done, count, sums[d], noise[d], blocks[d], hint[d]};
-            rc = device_render(s, phys(d), cam, &t, have_frame ? bufs[d] : nullptr, streams[d], nullptr, &pass);
-        }
-        if (rc != CRT_OK) break;
-        done += count;
-        uint32_t active = 0;
-        for (int d = 0; d < n && rc == CRT_OK; ++d) {  // synchronizes the device's stream
-            if (!rows[d]) continue;
-            crt_tiling t{rb, static_cast<uint32_t>(n), static_cast<uint32_t>(d), CRT_TILING_PACKED};
-            uint32_t a = 0;
-            rc = device_adaptive_update(phys(d), cam, &t, noise[d], blocks[d], done, prm->threshold, prm->min_samples, &a,
-                                        streams[d]);
-            hint[d] = std::max(1u, a);
-            active += a;
-        }
-        if (rc != CRT_OK) break;
-        if (have_frame) rc = gather();
-        if (rc != CRT_OK) break;
-        if (fn && fn(user, done, N, active, total_blocks, want_preview ? h_rgb : nullptr) != 0) break;
-        if (active == 0) break;
-    }
-    // ended between previews: every block's sum times 1 / its own count
-    if (rc == CRT_OK && !have_frame) {
-        for (int d = 0; d < n && rc == CRT_OK; ++d) {
-            if (!rows[d]) continue;
-            DeviceGuard g(phys(d));
-            crt_tiling t{rb, static_cast<uint32_t>(n), static_cast<uint32_t>(d), CRT_TILING_PACKED};
-            dev::Work Wk;
-            rc = tiling_work(cam, &t, Wk);
-            if (rc) break;
-            Wk.bw = cam->image_w;
-            Wk.bh = rows[d];
-            Wk.tiles_x = tiles_x;
-            Wk.tiles_y = (rows[d] + dev::kTileH - 1) / dev::kTileH;
-            Wk.tiles = nblk[d];
-            Wk.s0 = ~0u;  // no block word equals it: every tile takes the skipped branch
-            hipLaunchKernelGGL(dev::accumulate_masked_kernel, dim3((nblk[d] + 3) / 4), dim3(256), 0, streams[d], nullptr,
-                               sums[d], nullptr, bufs[d], blocks[d], Wk, cam->image_w, tiles_x, 0u, 0u, 0.0);
-            if (hipGetLastError() != hipSuccess) rc = fail(CRT_E_HIP, "adaptive render: frame kernel launch");
-        }
-        if (rc == CRT_OK) rc = gather();
-    }
-    // the frame's block counts: device d's block row j is block row (j / (rb / 4) * n + d) * (rb / 4)
-    // + j % (rb / 4) of the frame (rb = 4: one block row per row block)
-    uint64_t rendered = 0;
-    if (rc == CRT_OK) {
-        std::vector<uint32_t> hb;
-        for (int d = 0; d < n && rc == CRT_OK; ++d) {
-            if (!nblk[d]) continue;
-            DeviceGuard g(phys(d));
-            hb.resize(nblk[d]);
-            if (hipMemcpy(hb.data(), blocks[d], nblk[d] * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) {
-                (void)hipGetLastError();
-                rc = fail(CRT_E_HIP, "adaptive render: block state copy");
-                break;
-            }
-            for (uint32_t j = 0; j * dev::kTileH < rows[d]; ++j) {
-                const uint32_t fy = j * static_cast<uint32_t>(n) + static_cast<uint32_t>(d);
-                const uint64_t bh = std::min<uint64_t>(dev::kTileH, rows[d] - j * dev::kTileH);
-                for (uint32_t bx = 0; bx < tiles_x; ++bx) {
-                    const uint32_t cnt = hb[j * tiles_x + bx] & ~CRT_BLOCK_STOPPED;
-                    if (h_block_samples) h_block_samples[static_cast<size_t>(fy) * tiles_x + bx] = cnt;
-                    rendered += cnt * bh * std::min<uint64_t>(dev::kTileW, W - static_cast<uint64_t>(bx) * dev::kTileW);
-                }
-            }
-        }
-    }
-    for (int d = 0; d < n; ++d) {
-        DeviceGuard g(phys(d));
-        if (streams[d]) (void)hipStreamSynchronize(streams[d]);
-        if (sums[d]) (void)hipFree(sums[d]);
-        if (noise[d]) (void)hipFree(noise[d]);
-        if (bufs[d]) (void)hipFree(bufs[d]);
-        if (blocks[d]) (void)hipFree(blocks[d]);
-        if (streams[d]) (void)hipStreamDestroy(streams[d]);
-        if (ev[d]) (void)hipEventDestroy(ev[d]);
-    }
-    if (frame) {
-        DeviceGuard g(0);
-        (void)hipFree(frame);
-    }
-    if (samples_rendered) *samples_rendered = rendered;
-    return rc;
 }
 
 // The compile-time switches this library was built with (bench.py hashes them with the kernel

@@ -398,16 +398,16 @@ bool adaptive_tiling_ok(const crt_tiling* t);
 int device_adaptive_update(int device, const crt_camera* cam, const crt_tiling* t, const double* d_noise,
                            uint32_t* d_blocks, uint32_t samples_done, double threshold, uint32_t min_samples,
                            uint32_t* active_blocks, void* stream);
-int render_adaptive(crt_scene* s, const crt_camera* cam, int num_devices, const crt_adaptive_params* prm,
-                    crt_adaptive_fn fn, void* user, double* h_rgb, uint32_t* h_block_samples,
-                    uint64_t* samples_rendered);
-int render_progressive(crt_scene* s, const crt_camera* cam, int num_devices, uint32_t samples_per_pass,
-                       uint32_t flags, crt_progress_fn fn, void* user, double* h_rgb,
-                       uint32_t* samples_done);
+int device_frame_from_sums(const crt_camera* cam, const crt_tiling* t, double* d_sum, uint32_t* d_blocks,
+                           double* d_rgb, void* stream);
+// the kernels the blocking drivers launch themselves, on `stream` of the current device (false: failed)
+bool device_ppm8(const double* d_rgb, uint64_t px, uint8_t* d_out, uint32_t* d_redo, uint32_t redo_cap, void* stream);
+bool device_redo_gather(const double* d_rgb, const uint32_t* d_list, uint32_t n, double* d_out, void* stream);
+bool device_scale(const double* d_sum, double* d_out, uint64_t count, double factor, void* stream);
 int device_closest_hits(crt_scene* s, int device, const double* rays, size_t n, double t_min,
                         double t_max, crt_hit* out);
-// denoising: first-hit features and the per-pixel variance (crt_device.hip), the filter and the
-// blocking driver (crt_denoise.hip); the callers check the arguments
+// denoising: first-hit features and the per-pixel variance (crt_device.hip), the filter
+// (crt_denoise.hip); the callers check the arguments
 int device_render_features(const crt_scene* s, int device, const crt_camera* cam, const crt_tiling* t,
                            crt_feature* d_feat, void* stream);
 int device_pixel_variance(int device, const crt_camera* cam, const crt_tiling* t, const double* d_noise,
@@ -415,8 +415,6 @@ int device_pixel_variance(int device, const crt_camera* cam, const crt_tiling* t
 int device_denoise(int device, uint32_t w, uint32_t h, const double* d_rgb, const double* d_var,
                    const crt_feature* d_feat, const crt_denoise_params* prm, double* d_out, double* d_var_out,
                    void* stream);
-int render_denoised(crt_scene* s, int device, const crt_camera* cam, const crt_adaptive_params* adaptive,
-                    const crt_denoise_params* denoise, double* h_noisy, double* h_rgb, uint64_t* samples_rendered);
 // CRT_OK when `device` is a visible device the library can use, else the CRT_E_NODEVICE failure
 int device_check(int device);
 // the stream-ordered scratch pool of pass renders on `device` (a hipMemPool_t)
@@ -450,8 +448,18 @@ int validate_scene(const crt_material* materials, size_t nm, const crt_object* o
 int device_ppm_values(int device, const double* d_rgb, size_t n, int32_t* h_values, void* stream);
 // host: RGB::as_string's three integers for one pixel (std::pow, x86 int conversion)
 void ppm_pixel_host(const double rgb[3], int32_t out[3]);
+
+// the blocking drivers (crt_drivers.hip); crt_host.cpp's entry points check the arguments
 int render_multi(crt_scene* s, const crt_camera* cam, int num_devices, double* h_rgb,
                  crt_render_stats* stats);
 int render_multi_ppm(crt_scene* s, const crt_camera* cam, int num_devices, int32_t* h_values,
                      crt_render_stats* stats);
+int render_progressive(crt_scene* s, const crt_camera* cam, int num_devices, uint32_t samples_per_pass,
+                       uint32_t flags, crt_progress_fn fn, void* user, double* h_rgb,
+                       uint32_t* samples_done);
+int render_adaptive(crt_scene* s, const crt_camera* cam, int num_devices, const crt_adaptive_params* prm,
+                    crt_adaptive_fn fn, void* user, double* h_rgb, uint32_t* h_block_samples,
+                    uint64_t* samples_rendered);
+int render_denoised(crt_scene* s, int device, const crt_camera* cam, const crt_adaptive_params* adaptive,
+                    const crt_denoise_params* denoise, double* h_noisy, double* h_rgb, uint64_t* samples_rendered);
 }  // namespace crt

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "crt_internal.h"
+#include "crt_hip_util.h"
 #include "crt_prims.h"
 
 #pragma clang fp contract(off)
@@ -412,9 +413,7 @@ int device_create_scene(crt_scene* s, const crt_material* materials, size_t num_
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev || device >= kMaxDevices)
         return fail(CRT_E_NODEVICE, "GPU BVH build: device " + std::to_string(device) + " not visible");
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(device);
+    DeviceGuard g(device);
     const bool dbg = std::getenv("CRT_DEBUG_BUILD") != nullptr;
     auto tp = std::chrono::steady_clock::now();
     auto phase = [&](const char* what) {  // CRT_DEBUG_BUILD: where the set-up's time goes
@@ -627,7 +626,6 @@ done:
     (void)hipFree(d_pb);
     (void)hipFree(base);
     device_tree_free(t);
-    (void)hipSetDevice(prev);
     return rc;
 }
 

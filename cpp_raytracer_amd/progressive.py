@@ -16,9 +16,37 @@ from . import (FEATURE_DTYPE, Camera, CrtError, GpuScene, Tiling, denoise, denoi
 
 
 def _owned_rows(height: int, tiling: Optional[Tiling]) -> int:
+    """The rows of the pixel buffers (running sums, noise state, frame): the whole frame with no
+    tiling and with an unpacked one (the owned rows stay at their frame rows), the owned rows only
+    with a packed one."""
     if tiling is None or not (tiling.flags & 1):  # CRT_TILING_PACKED
         return height
     return sum(1 for r in range(height) if (r // tiling.row_block) % tiling.tile_count == tiling.tile_index)
+
+
+def _resume_job(name: str, cam: Camera, state: dict, check_tiling=None):
+    """What every resume() checks of a state() checkpoint against `cam`: the job, samples_done at a
+    pass boundary, the tiling (check_tiling, if any, sees it before it is used) and the sums' shape.
+    name: the class, for the error texts. Returns (samples_done, tiling, buffer rows, sums)."""
+    for key, want in (("spp", cam.samples_per_pixel), ("base_seed", cam.base_seed),
+                      ("width", cam.image_w), ("height", cam.image_h)):
+        got = int(state[key])
+        if got != int(want):
+            raise CrtError(f"{name}.resume: the state's {key} is {got}, the camera's {int(want)}")
+    done = int(state["samples_done"])
+    L = sample_chunk_len(cam.samples_per_pixel)
+    if done < 0 or done > cam.samples_per_pixel or (done % L and done != cam.samples_per_pixel):
+        raise CrtError(f"{name}.resume: samples_done = {done} is not a pass boundary")
+    tl = [int(v) for v in np.asarray(state["tiling"]).reshape(-1)]
+    tiling = None if tl == [1, 1, 0, 0] else Tiling(*tl)
+    if check_tiling is not None:
+        check_tiling(tiling)
+    rows = _owned_rows(cam.image_h, tiling)
+    total = np.asarray(state["sum"])
+    if total.shape != (rows, cam.image_w, 3) or total.dtype != np.float64:
+        raise CrtError(f"{name}.resume: the state's sums have shape {total.shape}, "
+                       f"the job's {(rows, int(cam.image_w), 3)}")
+    return done, tiling, rows, total
 
 
 class ProgressiveRender:
@@ -147,22 +175,7 @@ class ProgressiveRender:
     def resume(cls, scene: GpuScene, cam: Camera, state: dict, device: int = 0) -> "ProgressiveRender":
         """Continue the render of a state() checkpoint. The state must be of this job: the same
         samples per pixel (they fix the chunking), base seed and frame size as `cam`."""
-        for key, want in (("spp", cam.samples_per_pixel), ("base_seed", cam.base_seed),
-                          ("width", cam.image_w), ("height", cam.image_h)):
-            got = int(state[key])
-            if got != int(want):
-                raise CrtError(f"ProgressiveRender.resume: the state's {key} is {got}, the camera's {int(want)}")
-        done = int(state["samples_done"])
-        L = sample_chunk_len(cam.samples_per_pixel)
-        if done < 0 or done > cam.samples_per_pixel or (done % L and done != cam.samples_per_pixel):
-            raise CrtError(f"ProgressiveRender.resume: samples_done = {done} is not a pass boundary")
-        tl = [int(v) for v in np.asarray(state["tiling"]).reshape(-1)]
-        tiling = None if tl == [1, 1, 0, 0] else Tiling(*tl)
-        rows = _owned_rows(cam.image_h, tiling)
-        total = np.asarray(state["sum"])
-        if total.shape != (rows, cam.image_w, 3) or total.dtype != np.float64:
-            raise CrtError(f"ProgressiveRender.resume: the state's sums have shape {total.shape}, "
-                           f"the job's {(rows, int(cam.image_w), 3)}")
+        done, tiling, _, total = _resume_job("ProgressiveRender", cam, state)
         import torch
         r = cls(scene, cam, device, tiling, noise="noise" in state)
         r._sum.copy_(torch.from_numpy(np.ascontiguousarray(total)))

@@ -326,7 +326,7 @@ def test_the_hint_changes_no_bit(crt, rtow64, rtow64_gpu):
         assert torch.equal(total, w_total) and torch.equal(nz, w_nz) and torch.equal(out, w_out), hint
 
 
-@pytest.mark.parametrize("emulate", [None, "3"])
+@pytest.mark.parametrize("emulate", [None, "3", "16"])
 def test_blocking_api(crt, monkeypatch, rtow64, rtow64_gpu, emulate):
     d, smp = rtow64
     s = crt.GpuScene(d)

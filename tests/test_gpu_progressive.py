@@ -164,7 +164,7 @@ def test_tiling_and_bands(crt, monkeypatch, mode):
     assert torch.equal(frame, want)
 
 
-@pytest.mark.parametrize("emulate", [None, "3"])
+@pytest.mark.parametrize("emulate", [None, "3", "16"])
 def test_blocking_api(crt, monkeypatch, rtow22, emulate):
     import torch
     d, _ = rtow22
