@@ -344,19 +344,58 @@ class GpuScene:
 
     def render_denoised(self, cam: Camera, params: Optional[DenoiseParams] = None, threshold: Optional[float] = None,
                         min_samples: int = 0, samples_per_pass: int = 0, device: int = 0,
-                        noisy: bool = False):
-        """Blocking denoised render on one device (crt_render_denoised): every sample, or with
-        `threshold` an adaptive render (render_adaptive's rule), then features, variance and the
-        filter. Returns (denoised frame, unfiltered frame or None, samples rendered over all pixels)."""
+                        noisy: bool = False, *, num_devices: int = 1, callback=None, preview: bool = False,
+                        counts: bool = False):
+        """Blocking denoised render: every sample, or with `threshold` an adaptive render
+        (render_adaptive's rule), then features, variance and the filter. Returns (denoised frame,
+        unfiltered frame or None, samples rendered over all pixels).
+        With the keyword arguments at their defaults: on `device` (crt_render_denoised). Otherwise
+        over devices [0, num_devices) with the filter on device 0 (crt_render_denoised_devices; 0 =
+        all visible devices; `device` must be 0): the same frames bit for bit.
+        callback(samples_done, samples_total, active_blocks, total_blocks, noisy, denoised) runs
+        after every pass; a true return stops the render. With preview=True (needs `threshold`;
+        min_samples >= the job's samples never stops a block) every call gets the denoised frame of
+        the state so far and, with noisy=True, the unfiltered one (views of the returned arrays:
+        copy them to keep them); else both are None. counts=True appends the blocks' sample counts
+        (render_adaptive's array) to the result."""
         out = np.empty((cam.image_h, cam.image_w, 3), np.float64)
         raw = np.empty_like(out) if noisy else None
         prm = params if params is not None else denoise_params()
-        ad = _capi.AdaptiveParams(threshold, min_samples, samples_per_pass, 0, 0) if threshold is not None else None
         rendered = C.c_uint64(0)
-        check(lib().crt_render_denoised(self._h, device, C.byref(cam), C.byref(ad) if ad is not None else None,
-                                        C.byref(prm), raw.ctypes.data if noisy else None, out.ctypes.data,
-                                        C.byref(rendered)), "crt_render_denoised")
-        return out, raw, int(rendered.value)
+        if num_devices == 1 and callback is None and not preview and not counts:
+            ad = _capi.AdaptiveParams(threshold, min_samples, samples_per_pass, 0, 0) if threshold is not None else None
+            check(lib().crt_render_denoised(self._h, device, C.byref(cam), C.byref(ad) if ad is not None else None,
+                                            C.byref(prm), raw.ctypes.data if noisy else None, out.ctypes.data,
+                                            C.byref(rendered)), "crt_render_denoised")
+            return out, raw, int(rendered.value)
+        if device != 0:
+            raise CrtError("render_denoised: device must be 0 with num_devices, callback, preview or counts "
+                           "(the render runs on devices [0, num_devices))")
+        if preview and threshold is None:
+            raise CrtError("render_denoised: preview needs an adaptive render (threshold; min_samples >= the job's "
+                           "samples renders plain passes)")
+        ad = None
+        if threshold is not None:
+            ad = _capi.AdaptiveParams(threshold, min_samples, samples_per_pass,
+                                      _capi.CRT_PROGRESS_PREVIEW if preview else 0, 0)
+        blocks = np.zeros(((cam.image_h + 3) // 4, (cam.image_w + 15) // 16), np.uint32)
+        raised = []
+
+        def trampoline(_user, done, total, active, nblocks, h_noisy, h_rgb):
+            try:
+                return 1 if callback(done, total, active, nblocks, raw if h_noisy else None, out if h_rgb else None) else 0
+            except BaseException as e:  # not through the C frames: stop, raise after the call
+                raised.append(e)
+                return 1
+
+        fn = _capi.DENOISED_FN(trampoline) if callback is not None else _capi.DENOISED_FN()
+        rc = lib().crt_render_denoised_devices(self._h, C.byref(cam), num_devices, C.byref(ad) if ad is not None else None,
+                                               C.byref(prm), fn, None, raw.ctypes.data if noisy else None,
+                                               out.ctypes.data, blocks.ctypes.data, C.byref(rendered))
+        if raised:
+            raise raised[0]
+        check(rc, "crt_render_denoised_devices")
+        return (out, raw, int(rendered.value), blocks) if counts else (out, raw, int(rendered.value))
 
     def render_progressive(self, cam: Camera, samples_per_pass: int = 0, callback=None, num_devices: int = 1,
                            preview: bool = False, noise: bool = False) -> tuple[np.ndarray, int]:

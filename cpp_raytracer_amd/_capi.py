@@ -123,6 +123,8 @@ CRT_PROGRESS_NOISE, CRT_PROGRESS_PREVIEW = 1, 2
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.c_void_p)
 # crt_adaptive_fn(user, samples_done, samples_total, active_blocks, total_blocks, h_rgb)
 ADAPTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p)
+# crt_denoised_fn(user, samples_done, samples_total, active_blocks, total_blocks, h_noisy, h_rgb)
+DENOISED_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 CRT_BLOCK_W, CRT_BLOCK_H, CRT_BLOCK_STOPPED = 16, 4, 0x80000000
 EXPORTS = {
     "crt_abi_version": (C.c_int, []),
@@ -165,6 +167,9 @@ EXPORTS = {
                                     P(DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p]),
     "crt_render_denoised": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(AdaptiveParams), P(DenoiseParams),
                                       C.c_void_p, C.c_void_p, P(C.c_uint64)]),
+    "crt_render_denoised_devices": (C.c_int, [C.c_void_p, P(Camera), C.c_int, P(AdaptiveParams), P(DenoiseParams),
+                                              DENOISED_FN, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              P(C.c_uint64)]),
     "crt_render_count": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Tiling), P(RenderStats)]),
     "crt_render": (C.c_int, [C.c_void_p, P(Camera), C.c_int, C.c_void_p, P(RenderStats)]),
     "crt_render_ppm": (C.c_int, [C.c_void_p, P(Camera), C.c_int, C.c_void_p, P(RenderStats)]),

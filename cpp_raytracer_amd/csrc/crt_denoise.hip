@@ -7,7 +7,9 @@
 // Before the first, pack_kernel packs the inputs into the two records the taps read: the state
 // (c0, c1, c2, v; 32 bytes, ping-pong between iterations) and the guide (normal, point, t, prim;
 // 64 bytes, constant), so a tap is three aligned 32-byte reads instead of reads of three arrays
-// with 24-, 8- and 88-byte records.
+// with 24-, 8- and 88-byte records. The two stages are also callable on their own
+// (device_denoise_pack, device_denoise_filter): crt_render_denoised_devices packs on every device
+// over its own rows and filters the gathered records on device 0.
 // Two tap routes, one arithmetic (filter_pixel, instantiated over the route's reader):
 //   LDS     the tile and its halo of 2 * step pixels staged in LDS as planes of doubles (a lane's
 //           neighbour is the next double: ds_read_b64 without bank conflicts); for the steps whose
@@ -61,23 +63,30 @@ __device__ __forceinline__ bool finite(double x) {
     return (static_cast<unsigned long long>(__double_as_longlong(x)) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
 }
 
+// state and guide are packed separately (a render's guide is constant, its state changes with every
+// pass): either output may be null, and then its inputs are not read. Linear in the pixel index, so
+// it packs a whole frame or a lane's packed owned rows alike.
 __global__ __launch_bounds__(256) void pack_kernel(const double* __restrict__ rgb, const double* __restrict__ var,
                                                    const crt_feature* __restrict__ feat, uint32_t n,
                                                    State* __restrict__ state, Guide* __restrict__ guide) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    State s;
-    Guide g;
-    for (int j = 0; j < 3; ++j) {
-        s.c[j] = rgb[3 * static_cast<size_t>(i) + j];
-        g.n[j] = feat[i].normal[j];
-        g.P[j] = feat[i].point[j];
+    if (state) {
+        State s;
+        for (int j = 0; j < 3; ++j) s.c[j] = rgb[3 * static_cast<size_t>(i) + j];
+        s.v = var[i];
+        state[i] = s;
     }
-    s.v = var[i];
-    g.t = feat[i].t;
-    g.prim = feat[i].prim;
-    state[i] = s;
-    guide[i] = g;
+    if (guide) {
+        Guide g;
+        for (int j = 0; j < 3; ++j) {
+            g.n[j] = feat[i].normal[j];
+            g.P[j] = feat[i].point[j];
+        }
+        g.t = feat[i].t;
+        g.prim = feat[i].prim;
+        guide[i] = g;
+    }
 }
 
 // reader of the gather route: frame coordinates -> global memory
@@ -250,31 +259,24 @@ static bool lds_route(int step) {
 
 }  // namespace dn
 
-int device_denoise(int device, uint32_t w, uint32_t h, const double* d_rgb, const double* d_var,
-                   const crt_feature* d_feat, const crt_denoise_params* prm, double* d_out, double* d_var_out,
-                   void* stream) {
-    int rc = device_check(device);
-    if (rc) return rc;
+static_assert(sizeof(dn::State) == kDenoiseStateBytes && sizeof(dn::Guide) == kDenoiseGuideBytes, "record sizes");
+
+static int check_frame(uint32_t w, uint32_t h) {
     const uint64_t n64 = static_cast<uint64_t>(w) * h;
-    if (n64 == 0) return CRT_OK;
     if (n64 >= 0x7fffffffull || w > 0x3fffffffu || h > 0x3fffffffu)
         return fail(CRT_E_INVALID, "crt_denoise_async: frame has more than 2^31-2 pixels");
-    const uint32_t n = static_cast<uint32_t>(n64);
-    DeviceGuard g(device);
-    void* pool_v = nullptr;
-    rc = device_pass_pool(device, &pool_v);
-    if (rc) return rc;
-    hipMemPool_t pool = static_cast<hipMemPool_t>(pool_v);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // one allocation: the guide, then the two states
-    char* scratch = nullptr;
-    const size_t guide_bytes = static_cast<size_t>(n) * sizeof(dn::Guide), state_bytes = static_cast<size_t>(n) * sizeof(dn::State);
-    HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&scratch), guide_bytes + 2 * state_bytes, pool, st));
-    dn::Guide* guide = reinterpret_cast<dn::Guide*>(scratch);
-    dn::State* state[2] = {reinterpret_cast<dn::State*>(scratch + guide_bytes),
-                           reinterpret_cast<dn::State*>(scratch + guide_bytes + state_bytes)};
-    hipLaunchKernelGGL(dn::pack_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_rgb, d_var, d_feat, n, state[0], guide);
-    hipError_t e = hipGetLastError();
+    return CRT_OK;
+}
+
+static hipError_t launch_pack(uint32_t n, const double* d_rgb, const double* d_var, const crt_feature* d_feat,
+                              dn::State* state, dn::Guide* guide, hipStream_t st) {
+    hipLaunchKernelGGL(dn::pack_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_rgb, d_var, d_feat, n, state, guide);
+    return hipGetLastError();
+}
+
+static hipError_t launch_filter(uint32_t w, uint32_t h, dn::State* const state[2], const dn::Guide* guide,
+                                const crt_denoise_params* prm, double* d_out, double* d_var_out, hipStream_t st) {
+    hipError_t e = hipSuccess;
     const dim3 grid((w + dn::kTileW - 1) / dn::kTileW, (h + dn::kTileH - 1) / dn::kTileH);
     for (uint32_t i = 0; i < prm->iterations && e == hipSuccess; ++i) {
         const bool last = i + 1 == prm->iterations;
@@ -289,6 +291,63 @@ int device_denoise(int device, uint32_t w, uint32_t h, const double* d_rgb, cons
                                A, out, d_out, d_var_out);
         e = hipGetLastError();
     }
+    return e;
+}
+
+int device_denoise_pack(int device, uint64_t pixels, const double* d_rgb, const double* d_var,
+                        const crt_feature* d_feat, void* d_state, void* d_guide, void* stream) {
+    const int rc = device_check(device);
+    if (rc) return rc;
+    if (pixels == 0 || (!d_state && !d_guide)) return CRT_OK;
+    if (pixels >= 0x7fffffffull) return fail(CRT_E_INVALID, "denoise pack: more than 2^31-2 pixels");
+    DeviceGuard g(device);
+    const hipError_t e = launch_pack(static_cast<uint32_t>(pixels), d_rgb, d_var, d_feat, static_cast<dn::State*>(d_state),
+                                     static_cast<dn::Guide*>(d_guide), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(CRT_E_HIP, std::string("denoise pack_kernel launch: ") + hipGetErrorString(e));
+    return CRT_OK;
+}
+
+int device_denoise_filter(int device, uint32_t w, uint32_t h, void* d_state, void* d_state_tmp, const void* d_guide,
+                          const crt_denoise_params* prm, double* d_out, double* d_var_out, void* stream) {
+    int rc = device_check(device);
+    if (rc) return rc;
+    if (static_cast<uint64_t>(w) * h == 0) return CRT_OK;
+    rc = check_frame(w, h);
+    if (rc) return rc;
+    DeviceGuard g(device);
+    dn::State* const state[2] = {static_cast<dn::State*>(d_state), static_cast<dn::State*>(d_state_tmp)};
+    const hipError_t e = launch_filter(w, h, state, static_cast<const dn::Guide*>(d_guide), prm, d_out, d_var_out,
+                                       static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(CRT_E_HIP, std::string("denoise kernels: ") + hipGetErrorString(e));
+    return CRT_OK;
+}
+
+// The two stages back to back over scratch of its own from the pass pool.
+int device_denoise(int device, uint32_t w, uint32_t h, const double* d_rgb, const double* d_var,
+                   const crt_feature* d_feat, const crt_denoise_params* prm, double* d_out, double* d_var_out,
+                   void* stream) {
+    int rc = device_check(device);
+    if (rc) return rc;
+    const uint64_t n64 = static_cast<uint64_t>(w) * h;
+    if (n64 == 0) return CRT_OK;
+    rc = check_frame(w, h);
+    if (rc) return rc;
+    const uint32_t n = static_cast<uint32_t>(n64);
+    DeviceGuard g(device);
+    void* pool_v = nullptr;
+    rc = device_pass_pool(device, &pool_v);
+    if (rc) return rc;
+    hipMemPool_t pool = static_cast<hipMemPool_t>(pool_v);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // one allocation: the guide, then the two states
+    char* scratch = nullptr;
+    const size_t guide_bytes = static_cast<size_t>(n) * sizeof(dn::Guide), state_bytes = static_cast<size_t>(n) * sizeof(dn::State);
+    HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&scratch), guide_bytes + 2 * state_bytes, pool, st));
+    dn::Guide* guide = reinterpret_cast<dn::Guide*>(scratch);
+    dn::State* const state[2] = {reinterpret_cast<dn::State*>(scratch + guide_bytes),
+                                 reinterpret_cast<dn::State*>(scratch + guide_bytes + state_bytes)};
+    hipError_t e = launch_pack(n, d_rgb, d_var, d_feat, state[0], guide, st);
+    if (e == hipSuccess) e = launch_filter(w, h, state, guide, prm, d_out, d_var_out, st);
     (void)hipFreeAsync(scratch, st);
     if (e != hipSuccess) return fail(CRT_E_HIP, std::string("denoise kernels: ") + hipGetErrorString(e));
     return CRT_OK;

@@ -1,5 +1,6 @@
 // The blocking render drivers: crt_render / crt_render_ppm (render_multi_impl),
-// crt_render_progressive, crt_render_adaptive and crt_render_denoised. Host code only: no kernel
+// crt_render_progressive, crt_render_adaptive, crt_render_denoised and
+// crt_render_denoised_devices. Host code only: no kernel
 // is defined here; the drivers go through the device_* functions of crt_device.hip and
 // crt_denoise.hip. What the drivers share is defined once, above them: the device set with its
 // concurrent upload, the per-device lane, the gather, the adaptive step and the block counts.
@@ -13,6 +14,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
+#include <cstdio>
 #include <cstdlib>
 #include <limits>
 #include <mutex>
@@ -581,6 +584,179 @@ int render_denoised(crt_scene* s, int device, const crt_camera* cam, const crt_a
         // the block words' copy goes behind the frames' and synchronizes the stream for all three
         else if (adaptive) rc = block_samples(who, &l, 1, cam->image_w, true, nullptr, &rendered);
         else rendered = static_cast<uint64_t>(done) * px;
+    }
+    if (samples_rendered) *samples_rendered = rendered;
+    return rc;
+}
+
+// crt_render_denoised_devices: render_adaptive's layout and steps (or one plain pass) over the
+// lanes, and the denoiser behind them. Every lane keeps, beside its pass buffers, the variance of
+// its pixels and their filter records (crt_denoise.hip: state 32 B, guide 64 B a pixel), packed
+// over its owned rows: the guide once per render (features depend on camera and scene only), the
+// state per denoised frame. Device 0 holds the whole-frame records, the unfiltered frame and the
+// output: lane 0's stream waits for each lane (gather_frame's event scheme), pulls record and frame
+// rows to their frame rows (gather_packed), runs the filter stage and copies both frames back.
+// Everything is allocated with hipMalloc before the first pass; the calls take their scratch from
+// the pass pool. CRT_DENOISE_TIMING=1 (tools/denoise_gain.py) prints every denoised frame's cost to
+// stderr: host clock from the end of the pass to both frames on the host, and its split by events
+// on lane 0's stream.
+int render_denoised_devices(crt_scene* s, const crt_camera* cam, int num_devices, const crt_adaptive_params* adaptive,
+                            const crt_denoise_params* denoise, crt_denoised_fn fn, void* user, double* h_noisy,
+                            double* h_rgb, uint32_t* h_block_samples, uint64_t* samples_rendered) {
+    DeviceSet ds;
+    int rc = open_devices(s, num_devices, ds);
+    if (rc) return rc;
+    const uint32_t N = cam->samples_per_pixel;
+    const size_t W = cam->image_w, H = cam->image_h, px = W * H;
+    const bool want_preview = adaptive && (adaptive->flags & CRT_PROGRESS_PREVIEW) != 0 && fn;
+    const uint32_t total_blocks = static_cast<uint32_t>(crt_block_count(cam->image_w, cam->image_h));
+    Lanes L("denoised render", ds);
+    double* frame = nullptr;
+    rc = open_pass_lanes(L, cam, true, adaptive != nullptr, frame);
+    if (rc) return rc;
+    // the denoiser's buffers: a lane's share on its device, the whole frame's on device 0
+    struct Share {
+        double* var = nullptr;
+        crt_feature* feat = nullptr;
+        char *state = nullptr, *guide = nullptr;
+    };
+    std::vector<Share> share(ds.n);
+    for (int d = 0; d < ds.n; ++d) {
+        Lane& l = L.lane[d];
+        if (!l.rows) continue;
+        DeviceGuard g(l.device);
+        l.alloc(share[d].var, l.px * sizeof(double));
+        l.alloc(share[d].feat, l.px * sizeof(crt_feature));
+        l.alloc(share[d].state, l.px * kDenoiseStateBytes);
+        l.alloc(share[d].guide, l.px * kDenoiseGuideBytes);
+        if (!l.ok) return setup_failed(L.who, l);
+    }
+    char *guide = nullptr, *state = nullptr, *state_tmp = nullptr;
+    double* out = nullptr;
+    rc = alloc_frame(L, guide, px * kDenoiseGuideBytes);
+    if (rc == CRT_OK) rc = alloc_frame(L, state, px * kDenoiseStateBytes);
+    if (rc == CRT_OK) rc = alloc_frame(L, state_tmp, px * kDenoiseStateBytes);
+    if (rc == CRT_OK) rc = alloc_frame(L, out, px * 3 * sizeof(double));
+    if (rc) return rc;
+    hipStream_t s0 = L.lane[0].stream;
+    const bool timing = std::getenv("CRT_DENOISE_TIMING") != nullptr;
+    hipEvent_t ev[5] = {};
+    struct EventsGuard {
+        hipEvent_t* ev;
+        ~EventsGuard() {
+            DeviceGuard g(0);
+            for (int i = 0; i < 5; ++i)
+                if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    } events_guard{ev};
+    if (timing) {
+        DeviceGuard g(0);
+        for (hipEvent_t& e : ev)
+            if (hipEventCreate(&e) != hipSuccess) return fail(CRT_E_HIP, L.who + ": timing events");
+    }
+    // the guide records of every lane's rows, once (the first call of the feature pass for a scene
+    // and device allocates its primitive table: before the first pass, as every allocation here)
+    for (int d = 0; d < ds.n && rc == CRT_OK; ++d) {
+        Lane& l = L.lane[d];
+        if (!l.rows) continue;
+        rc = device_render_features(s, l.device, cam, &l.tiling, share[d].feat, l.stream);
+        if (rc == CRT_OK)
+            rc = device_denoise_pack(l.device, l.px, nullptr, nullptr, share[d].feat, nullptr, share[d].guide, l.stream);
+    }
+    bool have_guide = false;
+    // The denoised frame of the state after `done` samples, the lanes' frame rows being up to date:
+    // both frames on the host when it returns.
+    auto denoised_frame = [&](uint32_t done) -> int {
+        const auto t0 = std::chrono::steady_clock::now();
+        DeviceGuard g0(0);
+        auto mark = [&](int i) { return !timing || hipEventRecord(ev[i], s0) == hipSuccess; };
+        if (!mark(0)) return fail(CRT_E_HIP, L.who + ": event");
+        for (int d = 0; d < ds.n; ++d) {
+            Lane& l = L.lane[d];
+            if (!l.rows) continue;
+            int r = device_pixel_variance(l.device, cam, &l.tiling, l.noise, adaptive ? l.blocks : nullptr, done,
+                                          share[d].var, l.stream);
+            if (r == CRT_OK)
+                r = device_denoise_pack(l.device, l.px, l.rgb, share[d].var, nullptr, share[d].state, nullptr, l.stream);
+            if (r) return r;
+            if (!ds.emulate && d > 0) enable_peer_once(0, d);
+            {
+                DeviceGuard gd(l.device);
+                if (hipEventRecord(l.done, l.stream) != hipSuccess) return fail(CRT_E_HIP, L.who + ": event");
+            }
+            if (d > 0 && hipStreamWaitEvent(s0, l.done, 0) != hipSuccess)
+                return fail(CRT_E_HIP, L.who + ": gather wait failed");
+        }
+        if (!mark(1)) return fail(CRT_E_HIP, L.who + ": event");
+        for (int d = 0; d < ds.n; ++d) {
+            const Lane& l = L.lane[d];
+            if (!l.rows) continue;
+            hipError_t e = gather_packed(state, share[d].state, H, ds.rb, ds.n, d, W * kDenoiseStateBytes, s0);
+            if (e == hipSuccess && !have_guide)
+                e = gather_packed(guide, share[d].guide, H, ds.rb, ds.n, d, W * kDenoiseGuideBytes, s0);
+            if (e == hipSuccess)
+                e = gather_packed(reinterpret_cast<char*>(frame), reinterpret_cast<const char*>(l.rgb), H, ds.rb, ds.n, d,
+                                  W * 3 * sizeof(double), s0);
+            if (e != hipSuccess)
+                return fail(CRT_E_HIP, L.who + ": gather from device " + std::to_string(d) + ": " + hipGetErrorString(e));
+        }
+        have_guide = true;
+        if (!mark(2)) return fail(CRT_E_HIP, L.who + ": event");
+        const int r = device_denoise_filter(0, cam->image_w, cam->image_h, state, state_tmp, guide, denoise, out, nullptr, s0);
+        if (r) return r;
+        if (!mark(3)) return fail(CRT_E_HIP, L.who + ": event");
+        hipError_t e = hipMemcpyAsync(h_rgb, out, px * 3 * sizeof(double), hipMemcpyDeviceToHost, s0);
+        if (e == hipSuccess && h_noisy) e = hipMemcpyAsync(h_noisy, frame, px * 3 * sizeof(double), hipMemcpyDeviceToHost, s0);
+        if (e == hipSuccess && !mark(4)) e = hipErrorUnknown;
+        if (e == hipSuccess) e = hipStreamSynchronize(s0);
+        if (e != hipSuccess) return fail(CRT_E_HIP, L.who + ": " + hipGetErrorString(e));
+        if (timing) {
+            const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            float ms[4] = {};
+            for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
+            std::fprintf(stderr,
+                         "crt_denoise_timing devices=%d emulated=%d done=%u host_ms=%.4f lanes_ms=%.4f gather_ms=%.4f "
+                         "filter_ms=%.4f d2h_ms=%.4f\n",
+                         ds.n, ds.emulate ? 1 : 0, done, host_ms, ms[0], ms[1], ms[2], ms[3]);
+        }
+        return CRT_OK;
+    };
+    uint32_t done = 0, active = 0;
+    bool have_frame = false;
+    if (!adaptive && rc == CRT_OK) {  // one plain pass, the lanes' frame rows written
+        for (Lane& l : L.lane) {
+            const RenderPass pass{0, N, l.sum, l.noise};
+            if (l.rows && rc == CRT_OK) rc = device_render(s, l.device, cam, &l.tiling, l.rgb, l.stream, nullptr, &pass);
+        }
+        done = N;
+        if (rc == CRT_OK) rc = denoised_frame(done);
+        have_frame = true;
+        if (rc == CRT_OK && fn) (void)fn(user, done, N, 0, total_blocks, nullptr, nullptr);
+    }
+    while (adaptive && rc == CRT_OK && done < N) {  // render_adaptive's loop
+        have_frame = want_preview;
+        rc = adaptive_step(s, cam, adaptive, L.lane.data(), ds.n, have_frame, &done, &active);
+        if (rc == CRT_OK && have_frame) rc = denoised_frame(done);
+        if (rc != CRT_OK) break;
+        if (fn && fn(user, done, N, active, total_blocks, have_frame ? h_noisy : nullptr, have_frame ? h_rgb : nullptr) != 0)
+            break;
+        if (active == 0) break;
+    }
+    // ended between previews: every block's sum times 1 / its own count, then the denoiser
+    if (rc == CRT_OK && !have_frame) {
+        for (const Lane& l : L.lane) {
+            if (!l.rows || rc != CRT_OK) continue;
+            DeviceGuard g(l.device);
+            rc = device_frame_from_sums(cam, &l.tiling, l.sum, l.blocks, l.rgb, l.stream);
+        }
+        if (rc == CRT_OK) rc = denoised_frame(done);
+    }
+    uint64_t rendered = 0;
+    if (rc == CRT_OK && adaptive) {
+        rc = block_samples(L.who, L.lane.data(), ds.n, cam->image_w, false, h_block_samples, &rendered);
+    } else if (rc == CRT_OK) {
+        rendered = static_cast<uint64_t>(done) * px;
+        if (h_block_samples) std::fill(h_block_samples, h_block_samples + total_blocks, done);
     }
     if (samples_rendered) *samples_rendered = rendered;
     return rc;

@@ -1384,6 +1384,33 @@ int crt_render_denoised(crt_scene* s, int device, const crt_camera* cam, const c
     return render_denoised(s, device, cam, adaptive, denoise, h_noisy, h_rgb, samples_rendered);
 }
 
+int crt_render_denoised_devices(crt_scene* s, const crt_camera* cam, int num_devices, const crt_adaptive_params* adaptive,
+                                const crt_denoise_params* denoise, crt_denoised_fn fn, void* user, double* h_noisy,
+                                double* h_rgb, uint32_t* h_block_samples, uint64_t* samples_rendered) {
+    clear_error();
+    if (samples_rendered) *samples_rendered = 0;
+    if (!s || !cam) return fail(CRT_E_INVALID, "crt_render_denoised_devices: null argument");
+    if (!h_rgb) return fail(CRT_E_INVALID, "crt_render_denoised_devices: h_rgb is null (the output is required)");
+    const int rc = check_denoise_params("crt_render_denoised_devices", denoise);
+    if (rc) return rc;
+    if (adaptive) {
+        if (adaptive->flags & ~CRT_PROGRESS_PREVIEW)
+            return fail(CRT_E_INVALID, "crt_render_denoised_devices: unknown adaptive flags (CRT_PROGRESS_PREVIEW or 0)");
+        if (adaptive->reserved != 0)
+            return fail(CRT_E_INVALID, "crt_render_denoised_devices: adaptive reserved must be 0");
+        if (!(adaptive->threshold >= 0) || !std::isfinite(adaptive->threshold))
+            return fail(CRT_E_INVALID, "crt_render_denoised_devices: threshold must be finite and >= 0");
+    }
+    if (cam->samples_per_pixel == 0) return fail(CRT_E_INVALID, "crt_render_denoised_devices: samples_per_pixel is 0");
+    if (cam->samples_per_pixel >= CRT_BLOCK_STOPPED)
+        return fail(CRT_E_INVALID, "crt_render_denoised_devices: sample counts must stay below 2^31");
+    if (cam->image_w == 0 || cam->image_h == 0) return fail(CRT_E_INVALID, "crt_render_denoised_devices: empty image");
+    if (static_cast<uint64_t>(cam->image_w) * cam->image_h >= 0x7fffffffull)
+        return fail(CRT_E_INVALID, "crt_render_denoised_devices: frame has more than 2^31-2 pixels");
+    return render_denoised_devices(s, cam, num_devices, adaptive, denoise, fn, user, h_noisy, h_rgb, h_block_samples,
+                                   samples_rendered);
+}
+
 int crt_noise_estimate(int device, const double* d_noise, size_t pixels, uint32_t samples_per_pixel,
                        uint32_t samples_done, double* sum_se, double* sum_mean, void* stream) {
     clear_error();

@@ -415,6 +415,18 @@ int device_pixel_variance(int device, const crt_camera* cam, const crt_tiling* t
 int device_denoise(int device, uint32_t w, uint32_t h, const double* d_rgb, const double* d_var,
                    const crt_feature* d_feat, const crt_denoise_params* prm, double* d_out, double* d_var_out,
                    void* stream);
+// device_denoise's two stages, for a caller with buffers of its own (crt_render_denoised_devices).
+// The records the filter's taps read: state (c0, c1, c2, v) and guide (normal, point, t, prim).
+constexpr size_t kDenoiseStateBytes = 32, kDenoiseGuideBytes = 64;
+// Pack: `pixels` consecutive pixels (a whole frame, or a lane's packed owned rows) of d_rgb and
+// d_var into d_state, of d_feat into d_guide. d_state or d_guide may be null: that record is not
+// written and its inputs are not read.
+int device_denoise_pack(int device, uint64_t pixels, const double* d_rgb, const double* d_var,
+                        const crt_feature* d_feat, void* d_state, void* d_guide, void* stream);
+// Filter: prm->iterations iterations over the whole-frame records d_state (overwritten) and d_guide,
+// ping-pong with d_state_tmp (w * h state records); the outputs as device_denoise's.
+int device_denoise_filter(int device, uint32_t w, uint32_t h, void* d_state, void* d_state_tmp, const void* d_guide,
+                          const crt_denoise_params* prm, double* d_out, double* d_var_out, void* stream);
 // CRT_OK when `device` is a visible device the library can use, else the CRT_E_NODEVICE failure
 int device_check(int device);
 // the stream-ordered scratch pool of pass renders on `device` (a hipMemPool_t)
@@ -462,4 +474,7 @@ int render_adaptive(crt_scene* s, const crt_camera* cam, int num_devices, const 
                     uint64_t* samples_rendered);
 int render_denoised(crt_scene* s, int device, const crt_camera* cam, const crt_adaptive_params* adaptive,
                     const crt_denoise_params* denoise, double* h_noisy, double* h_rgb, uint64_t* samples_rendered);
+int render_denoised_devices(crt_scene* s, const crt_camera* cam, int num_devices, const crt_adaptive_params* adaptive,
+                            const crt_denoise_params* denoise, crt_denoised_fn fn, void* user, double* h_noisy,
+                            double* h_rgb, uint32_t* h_block_samples, uint64_t* samples_rendered);
 }  // namespace crt

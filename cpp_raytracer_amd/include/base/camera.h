@@ -262,18 +262,27 @@ class Camera {
         return img;
     }
 
-    // render_scene followed by the denoiser (crt_render_denoised) on GPU 0: every sample, or with
-    // adaptive_threshold >= 0 an adaptive render at that threshold
-    Image render_scene_denoised(const crt_api::GpuScene& g, const DenoiseOptions& opt, double adaptive_threshold) {
+    // render_scene followed by the denoiser: every sample, or with adaptive_threshold >= 0 an
+    // adaptive render at that threshold. devices == 1: on GPU 0 (crt_render_denoised); 0 (all
+    // visible) or any other count: rendered over that many GPUs, filtered on GPU 0
+    // (crt_render_denoised_devices), the same picture
+    Image render_scene_denoised(const crt_api::GpuScene& g, const DenoiseOptions& opt, double adaptive_threshold,
+                                int devices) {
         crt_scene* scene = g.get();
         init();
         if (const char* dump = std::getenv("CRT_DUMP_SCENE")) dump_and_exit(g, dump);
         resolved.base_seed = SeedSeqGenerator::get_instance().next_seed();
-        int devices = 0;
-        if (crt_device_count(&devices) || devices == 0) crt_api::die("Camera::render_denoised");
+        int visible = 0;
+        if (crt_device_count(&visible) || visible == 0) crt_api::die("Camera::render_denoised");
         const bool adaptive = adaptive_threshold >= 0;
+        const bool one = devices == 1;
+        if (!one) {  // the count the render will use (crt_render_denoised_devices' rule)
+            devices = devices <= 0 ? visible : std::min(devices, visible);
+            if (const char* e = std::getenv("CRT_EMULATE_DEVICES")) devices = std::max(1, std::min(std::atoi(e), 64));
+        }
         std::cout << "Rendering " << image_w << " x " << image_h << " image (" << (adaptive ? "up to " : "")
-                  << samples_per_pixel << " spp" << (adaptive ? ", adaptive" : "") << ", denoised) on 1 GPU" << std::endl;
+                  << samples_per_pixel << " spp" << (adaptive ? ", adaptive" : "") << ", denoised) on " << devices << " GPU"
+                  << (devices > 1 ? "s" : "") << std::endl;
         std::vector<double> rgb(image_w * image_h * 3);
         crt_denoise_params dp{};
         dp.iterations = opt.iterations;
@@ -289,7 +298,9 @@ class Camera {
         }
         uint64_t rendered = 0;
         auto t0 = std::chrono::steady_clock::now();
-        if (crt_render_denoised(scene, 0, &resolved, adaptive ? &ap : nullptr, &dp, nullptr, rgb.data(), &rendered))
+        if (one ? crt_render_denoised(scene, 0, &resolved, adaptive ? &ap : nullptr, &dp, nullptr, rgb.data(), &rendered)
+                : crt_render_denoised_devices(scene, &resolved, devices, adaptive ? &ap : nullptr, &dp, nullptr, nullptr,
+                                              nullptr, rgb.data(), nullptr, &rendered))
             crt_api::die("Camera::render_denoised");
         auto ms = ms_diff(t0, std::chrono::steady_clock::now());
         std::cout << "Rendered " << static_cast<double>(rendered) / static_cast<double>(image_w * image_h)
@@ -307,19 +318,21 @@ class Camera {
 public:
     // Extension (not in the reference): render (adaptive_threshold < 0: every sample) or
     // render_adaptive (blocks stop at that threshold, default pass length and sample floor), then
-    // the feature-guided a-trous denoiser of crt_denoise_async over the frame, on one GPU. Guided
+    // the feature-guided a-trous denoiser of crt_denoise_async over the frame. Guided
     // by first-hit normals, positions and the per-pixel variance; what is seen through glass or in
     // mirrors is filtered by colour and variance alone, and albedo is not divided out.
+    // devices: 1 = everything on one GPU; 0 = rendered over all visible GPUs, or over that many,
+    // and filtered on GPU 0 (the same picture for any count).
     template <typename T>
     requires std::is_base_of_v<Hittable, T>
-    Image render_denoised(const T& world, DenoiseOptions options = {}, double adaptive_threshold = -1) {
+    Image render_denoised(const T& world, DenoiseOptions options = {}, double adaptive_threshold = -1, int devices = 1) {
         if constexpr (std::is_same_v<T, BVH>) {
-            return render_scene_denoised(world.gpu_scene(), options, adaptive_threshold);
+            return render_scene_denoised(world.gpu_scene(), options, adaptive_threshold, devices);
         } else if constexpr (std::is_same_v<T, Scene>) {
-            return render_denoised(BVH(world), options, adaptive_threshold);
+            return render_denoised(BVH(world), options, adaptive_threshold, devices);
         } else {
             crt_api::GpuScene s(world, 32, 12, true);
-            return render_scene_denoised(s, options, adaptive_threshold);
+            return render_scene_denoised(s, options, adaptive_threshold, devices);
         }
     }
 

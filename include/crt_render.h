@@ -381,7 +381,8 @@ int crt_render_adaptive(crt_scene* scene, const crt_camera* cam, int num_devices
  * Limits: the features are those of the first hit only, so detail seen through glass or in
  * mirrors is guided by colour and variance alone; albedo is reported but not divided out before
  * filtering (no albedo demodulation): textures would blur, the reference's materials have none.
- * One device per call: a multi-GPU render would have to gather its noise state first (not built).
+ * The filter itself runs on one device; crt_render_denoised_devices renders over several devices
+ * and gathers frame, variance and features to device 0 for it.
  * Below, max0(x) = x > 0 ? x : 0 (so -0 and NaN give +0), y(c) = (c0 + c1) + c2 and
  * dot(a, b) = (a0 * b0 + a1 * b1) + a2 * b2. */
 
@@ -466,12 +467,48 @@ int crt_denoise_async(int device, uint32_t w, uint32_t h, const double* d_rgb, c
  * crt_denoise_async on the same stream. h_rgb (HOST, image_w*image_h*3) receives the denoised
  * frame; h_noisy (HOST, same size, or NULL) the unfiltered one, bit for bit the frame of
  * crt_render_progressive / crt_render_adaptive on one device; *samples_rendered (or NULL) the sum
- * over the pixels of their sample counts. Multi-GPU denoising is out of scope: the filter reads
- * neighbours across row blocks, so the devices' frames and noise states would have to be gathered
- * first. */
+ * over the pixels of their sample counts. Over several devices, or with a denoised preview after
+ * every pass: crt_render_denoised_devices. */
 int crt_render_denoised(crt_scene* scene, int device, const crt_camera* cam, const crt_adaptive_params* adaptive,
                         const crt_denoise_params* denoise, double* h_noisy, double* h_rgb,
                         uint64_t* samples_rendered);
+
+/* Callback of crt_render_denoised_devices, called on the calling thread after every pass (and
+ * update). With CRT_PROGRESS_PREVIEW h_rgb is the caller's frame buffer holding the denoised frame
+ * of the state so far and h_noisy the caller's unfiltered one (NULL if the caller gave none);
+ * without it both are NULL. A non-zero return stops the render. */
+typedef int (*crt_denoised_fn)(void* user, uint32_t samples_done, uint32_t samples_total,
+                               uint32_t active_blocks, uint32_t total_blocks,
+                               const double* h_noisy, const double* h_rgb);
+
+/* Blocking denoised render over devices [0, num_devices): num_devices and CRT_EMULATE_DEVICES as
+ * in crt_render_adaptive, rows dealt as crt_tiling{4, n, d}, packed; devices that own no rows are
+ * legal. Every device renders its rows, takes their variance and packs the filter's records; device
+ * 0 gathers the records and the frame rows and runs the filter over the whole frame.
+ *   adaptive == NULL: one plain pass of all samples, as in crt_render_denoised; fn (may be NULL)
+ *     is called once, with active_blocks = 0.
+ *   adaptive != NULL: the masked passes and updates of crt_render_adaptive, under its rules for
+ *     *adaptive; flags may be 0 or CRT_PROGRESS_PREVIEW (the one difference from
+ *     crt_render_denoised). min_samples >= samples_per_pixel never stops a block: plain passes
+ *     with previews.
+ *   CRT_PROGRESS_PREVIEW with fn != NULL: before each call of fn, h_rgb (HOST, image_w*image_h*3)
+ *     holds the denoised frame of the state so far and h_noisy (HOST, same size, or NULL) the
+ *     unfiltered one; fn receives both pointers. Otherwise both buffers are written once, when the
+ *     render ends, and fn receives NULL for both.
+ *   A non-zero return from fn stops the render; the frames then describe the samples done so far.
+ * Every rule is checked before any device work (CRT_E_INVALID, the message names the rule).
+ * Bit contract: h_noisy is the frame crt_render_adaptive (crt_render_progressive when adaptive ==
+ * NULL) produces for the same job. h_rgb is crt_denoise_async applied to that frame,
+ * crt_pixel_variance_async of the job's noise state (with the block words when adaptive) and
+ * crt_render_features_async of the whole frame. Hence h_rgb equals crt_render_denoised's frame on
+ * one device, for any num_devices. h_block_samples (or NULL; every word samples_per_pixel when
+ * adaptive == NULL) and *samples_rendered (or NULL) mean what they mean in crt_render_adaptive.
+ * Device 0 holds the whole-frame records (128 bytes a pixel), the unfiltered frame and the output;
+ * every other buffer is a device's own share. */
+int crt_render_denoised_devices(crt_scene* scene, const crt_camera* cam, int num_devices,
+                                const crt_adaptive_params* adaptive, const crt_denoise_params* denoise,
+                                crt_denoised_fn fn, void* user, double* h_noisy, double* h_rgb,
+                                uint32_t* h_block_samples, uint64_t* samples_rendered);
 
 /* Instrumented pass: counts the work of the same render (never timed). */
 int crt_render_count(const crt_scene* scene, int device, const crt_camera* cam,

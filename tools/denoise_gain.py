@@ -12,7 +12,10 @@ ends the tool; nothing is started on the GPU after it):
              adaptive render at threshold 0.05 (500-spp job, 10 passes), base seed 2025; one
              process and one scene each
   python tools/denoise_gain.py [--reps 5] [--out profiles/denoise/denoise_gain.json]
-Writes the JSON file and prints it as one line."""
+Writes the JSON file and prints it as one line.
+  python tools/denoise_gain.py --devices 2 4 8 [--out profiles/denoise/denoise_devices.json]
+runs one other step instead: the cost of a denoised preview and of a whole denoised render over N
+devices (crt_render_denoised_devices) against one device (step_devices)."""
 import argparse
 import json
 import os
@@ -24,6 +27,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
+DEFAULT_OUT = str(ROOT / "profiles" / "denoise" / "denoise_gain.json")
 LIMITS = {"reference": 240, "timing": 300, "quality_plain": 240, "quality_adaptive": 240}  # seconds per step
 
 
@@ -135,8 +139,117 @@ def step_quality_adaptive(a, work):
             **quality(a, work, raw, den)}
 
 
+class Stderr:
+    """File descriptor 2 into a temporary file for the block: the library's CRT_DENOISE_TIMING lines."""
+
+    def __enter__(self):
+        sys.stderr.flush()
+        self.saved, self.tmp = os.dup(2), tempfile.TemporaryFile()
+        os.dup2(self.tmp.fileno(), 2)
+        return self
+
+    def __exit__(self, *exc):
+        os.dup2(self.saved, 2)
+        os.close(self.saved)
+        self.tmp.seek(0)
+        self.text = self.tmp.read().decode(errors="replace")
+        self.tmp.close()
+
+
+def step_devices(a, work):
+    """--devices N...: what a denoised preview and a whole denoised render cost over N devices
+    (crt_render_denoised_devices) against one device, all in this one process. Medians of --reps
+    after a warm-up; host clock around calls that end in a synchronise, and the library's own split
+    of a preview (CRT_DENOISE_TIMING: events on device 0's stream). With fewer than N devices
+    visible the N are emulated on device 0 (CRT_EMULATE_DEVICES) and labelled so: such figures say
+    what the extra copies and launches cost, not what several GPUs gain."""
+    import time
+    import torch
+    crt, s, cam = setup(a, a.spp, 2025)
+    prm = params(crt, a)
+    visible = crt.device_count()
+    chunk = crt.sample_chunk_len(a.spp)
+    per_pass = (max(1, a.spp // 10) + chunk - 1) // chunk * chunk
+    job = dict(threshold=a.threshold, min_samples=2 * per_pass, samples_per_pass=per_pass)
+
+    def med(xs):
+        return round(statistics.median(xs), 4)
+
+    def host_ms(fn):
+        fn()  # warm-up
+        ms = []
+        for _ in range(a.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return med(ms)
+
+    # one device, low-level calls on one stream: a preview is variance + filter (+ the frame's way home)
+    shape = (a.height, a.width)
+    total, out, den = (torch.empty(shape + (3,), dtype=torch.float64, device="cuda") for _ in range(3))
+    noise = torch.empty(shape + (2,), dtype=torch.float64, device="cuda")
+    var = torch.empty(shape, dtype=torch.float64, device="cuda")
+    feat = torch.empty(a.height * a.width, 88, dtype=torch.uint8, device="cuda")
+    host_den, host_raw = (torch.empty(shape + (3,), dtype=torch.float64) for _ in range(2))
+    st = torch.cuda.current_stream().cuda_stream
+    s.render_pass(0, cam, 0, a.spp, total.data_ptr(), noise.data_ptr(), out.data_ptr(), st)
+    s.render_features(0, cam, feat.data_ptr(), st)
+    torch.cuda.synchronize()
+
+    def preview_on_device():
+        crt.pixel_variance(0, cam, noise.data_ptr(), var.data_ptr(), a.spp, 0, st)
+        crt.denoise(0, a.width, a.height, out.data_ptr(), var.data_ptr(), feat.data_ptr(), prm, den.data_ptr(), 0, st)
+        torch.cuda.synchronize()
+
+    def preview_to_host():
+        crt.pixel_variance(0, cam, noise.data_ptr(), var.data_ptr(), a.spp, 0, st)
+        crt.denoise(0, a.width, a.height, out.data_ptr(), var.data_ptr(), feat.data_ptr(), prm, den.data_ptr(), 0, st)
+        host_den.copy_(den)
+        host_raw.copy_(out)
+        torch.cuda.synchronize()
+
+    res = {"spp": a.spp, "reps": a.reps, "visible_devices": visible, "job": job,
+           "one_device": {"preview_ms": host_ms(preview_on_device), "preview_to_host_ms": host_ms(preview_to_host),
+                          "render_denoised_ms": host_ms(lambda: s.render_denoised(cam, prm, noisy=True, **job)),
+                          "render_adaptive_ms": host_ms(lambda: s.render_adaptive(cam, job["threshold"], job["min_samples"],
+                                                                                  job["samples_per_pass"]))},
+           "devices": {}}
+    one_den, one_raw, one_n = s.render_denoised(cam, prm, noisy=True, **job)
+    fields = ("host_ms", "lanes_ms", "gather_ms", "filter_ms", "d2h_ms")
+    for n in a.devices:
+        emulated = n > visible
+        if emulated:
+            os.environ["CRT_EMULATE_DEVICES"] = str(n)
+        r = {"emulated": emulated}
+        r["render_denoised_ms"] = host_ms(lambda: s.render_denoised(cam, prm, noisy=True, num_devices=n, **job))
+        r["render_adaptive_ms"] = host_ms(lambda: s.render_adaptive(cam, job["threshold"], job["min_samples"],
+                                                                    job["samples_per_pass"], num_devices=n))
+        den_n, raw_n, n_n = s.render_denoised(cam, prm, noisy=True, num_devices=n, **job)
+        r["bit_identical_to_one_device"] = bool((den_n.view("u8") == one_den.view("u8")).all() and
+                                                (raw_n.view("u8") == one_raw.view("u8")).all() and n_n == one_n)
+        # previews after every pass of a job that never stops a block: the library reports each one
+        never = dict(threshold=a.threshold, min_samples=a.spp, samples_per_pass=per_pass)
+        os.environ["CRT_DENOISE_TIMING"] = "1"
+        lines = []
+        for rep in range(a.reps + 1):
+            with Stderr() as err:
+                s.render_denoised(cam, prm, noisy=True, num_devices=n, preview=True, callback=lambda *x: 0, **never)
+            if rep:  # the first call is the warm-up
+                lines += [ln for ln in err.text.splitlines() if ln.startswith("crt_denoise_timing")]
+        del os.environ["CRT_DENOISE_TIMING"]
+        rows = [dict(kv.split("=") for kv in ln.split()[1:]) for ln in lines]
+        r["previews_timed"] = len(rows)
+        r["preview"] = {f: med([float(x[f]) for x in rows]) for f in fields}
+        if emulated:
+            del os.environ["CRT_EMULATE_DEVICES"]
+        res["devices"][str(n)] = r
+    return res
+
+
 STEPS = {"reference": step_reference, "timing": step_timing, "quality_plain": step_quality_plain,
-         "quality_adaptive": step_quality_adaptive}
+         "quality_adaptive": step_quality_adaptive, "devices": step_devices}
+LIMITS["devices"] = 420
 
 
 def main():
@@ -151,7 +264,9 @@ def main():
     ap.add_argument("--squarings", type=int, default=7)
     ap.add_argument("--sigma-l", type=float, default=1.0)
     ap.add_argument("--sigma-p", type=float, default=0.05)
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "denoise" / "denoise_gain.json"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
+    ap.add_argument("--devices", type=int, nargs="+", metavar="N",
+                    help="only the several-devices step, for each N (emulated where fewer are visible)")
     ap.add_argument("--step", choices=sorted(STEPS))
     ap.add_argument("--work")
     a = ap.parse_args()
@@ -161,8 +276,11 @@ def main():
         return 0
     res = {"width": a.width, "height": a.height,
            "params": {"iterations": a.iterations, "normal_squarings": a.squarings, "sigma_l": a.sigma_l, "sigma_p": a.sigma_p}}
+    names = ("devices",) if a.devices else ("reference", "timing", "quality_plain", "quality_adaptive")
+    if a.devices and a.out == DEFAULT_OUT:
+        a.out = str(ROOT / "profiles" / "denoise" / "denoise_devices.json")
     with tempfile.TemporaryDirectory() as work:
-        for name in ("reference", "timing", "quality_plain", "quality_adaptive"):
+        for name in names:
             cmd = [sys.executable, __file__, "--step", name, "--work", work] + [x for x in sys.argv[1:]]
             try:
                 r = subprocess.run(cmd, timeout=LIMITS[name])
@@ -177,6 +295,8 @@ def main():
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps(res, indent=1) + "\n")
     print(json.dumps(res))
+    if a.devices:
+        return 0 if all(r["bit_identical_to_one_device"] for r in res["devices"]["devices"].values()) else 1
     ok = (res["quality_plain"]["finite"] and res["quality_adaptive"]["finite"] and
           res["quality_adaptive"]["noisy_is_render_adaptives_frame"] and
           res["quality_adaptive"]["full_count_pixels_equal_one_shot"] and res["timing"]["filter_all_gather_bit_identical"])
