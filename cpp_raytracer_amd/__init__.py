@@ -19,13 +19,15 @@ from . import _capi
 from ._capi import (CRT_BOX, CRT_DIELECTRIC, CRT_DIFFUSE_LIGHT, CRT_LAMBERTIAN, CRT_METAL,
                     CRT_PARALLELOGRAM, CRT_SPHERE, HIT_DTYPE, MATERIAL_DTYPE, NODE_DTYPE,
                     OBJECT_DTYPE, CRT_BLOCK_STOPPED, FEATURE_DTYPE, BVHParams, Camera, CameraSettings, CrtError,
-                    DenoiseParams, RenderStats, SceneInfo, Tiling, check, lib)
+                    DenoiseParams, RenderStats, SceneInfo, Tiling, TraceParams, CRT_TRACE_ANY, CRT_TRACE_PLAIN,
+                    check, lib)
 
 __all__ = [
     "SceneData", "GpuScene", "CameraSettings", "Camera", "Tiling", "RenderStats", "CrtError",
     "resolve_camera", "sample_seed", "rand_double", "device_count", "lib", "ppm_values", "write_ppm",
     "sample_chunk_len", "noise_estimate", "block_count", "adaptive_update", "CRT_BLOCK_STOPPED",
     "DenoiseParams", "FEATURE_DTYPE", "denoise_params", "pixel_variance", "denoise",
+    "TraceParams", "CRT_TRACE_ANY", "CRT_TRACE_PLAIN", "HIT_DTYPE",
     "CRT_LAMBERTIAN", "CRT_METAL", "CRT_DIELECTRIC", "CRT_DIFFUSE_LIGHT",
     "CRT_SPHERE", "CRT_PARALLELOGRAM", "CRT_BOX",
 ]
@@ -461,3 +463,44 @@ class GpuScene:
         check(lib().crt_closest_hits(self._h, device, rays.ctypes.data, len(rays), t_min, t_max,
                                      out.ctypes.data), "crt_closest_hits")
         return out
+
+    def trace_async(self, device: int, rays_ptr: int, n: int, hits_ptr: int = 0, occluded_ptr: int = 0,
+                    t_min: float = 1e-5, t_max: float = float("inf"), tmax_ptr: int = 0, flags: int = 0,
+                    stream: int = 0) -> None:
+        """Enqueue a ray query on device buffers (crt_trace_async): n rays of 6 doubles at rays_ptr
+        over (t_min, t_max), or up to tmax_ptr[i] for ray i. Closest hits (72-byte crt_hit records,
+        HIT_DTYPE) go to hits_ptr; with CRT_TRACE_ANY in flags, one uint32 a ray (1 = something is
+        hit) to occluded_ptr. CRT_TRACE_PLAIN takes crt_closest_hits' kernel instead of the render
+        kernel's traversal: the same results. The scene must be uploaded to `device`."""
+        prm = TraceParams(t_min, t_max, flags, 0)
+        check(lib().crt_trace_async(self._h, device, C.c_void_p(rays_ptr or None), n, C.c_void_p(tmax_ptr or None),
+                                    C.byref(prm), C.c_void_p(hits_ptr or None), C.c_void_p(occluded_ptr or None),
+                                    C.c_void_p(stream)), "crt_trace_async")
+
+    def trace(self, rays, t_min: float = 1e-5, t_max: float = float("inf"), tmax=None, any_hit: bool = False,
+              plain: bool = False):
+        """Ray query on torch tensors of a GPU: rays (n, 6) float64, tmax None or (n,) float64 of
+        per-ray upper bounds, on the rays' device. Runs on that device's current stream and does
+        not synchronise; the scene is uploaded there first if it is not yet (that, and the first
+        closest-hit call, block). Returns an (n, 72) uint8 tensor (after .cpu().numpy(),
+        .view(HIT_DTYPE) gives the records), or with any_hit an (n,) bool tensor."""
+        import torch
+        if not (rays.is_cuda and rays.dtype == torch.float64 and rays.dim() == 2 and rays.shape[1] == 6):
+            raise CrtError("trace: rays must be an (n, 6) float64 tensor on a GPU")
+        rays = rays.contiguous()
+        n, device = rays.shape[0], rays.device.index
+        if tmax is not None:
+            if not (tmax.is_cuda and tmax.device == rays.device and tmax.dtype == torch.float64 and tmax.shape == (n,)):
+                raise CrtError("trace: tmax must be an (n,) float64 tensor on the rays' device")
+            tmax = tmax.contiguous()
+        flags = (CRT_TRACE_ANY if any_hit else 0) | (CRT_TRACE_PLAIN if plain else 0)
+        with torch.cuda.device(device):
+            out = torch.empty((n,), dtype=torch.int32, device=rays.device) if any_hit else \
+                torch.empty((n, HIT_DTYPE.itemsize), dtype=torch.uint8, device=rays.device)
+            if n:
+                self.upload(device)
+                self.trace_async(device, rays.data_ptr(), n, 0 if any_hit else out.data_ptr(),
+                                 out.data_ptr() if any_hit else 0, t_min, t_max,
+                                 tmax.data_ptr() if tmax is not None else 0, flags,
+                                 torch.cuda.current_stream(device).cuda_stream)
+            return out != 0 if any_hit else out

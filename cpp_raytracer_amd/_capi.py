@@ -102,6 +102,12 @@ class DenoiseParams(C.Structure):
                 ("sigma_p", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class TraceParams(C.Structure):
+    _fields_ = [("t_min", C.c_double), ("t_max", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+CRT_TRACE_ANY, CRT_TRACE_PLAIN = 1, 2
+
 # numpy views of the same records (for bulk scene I/O)
 MATERIAL_DTYPE = np.dtype([("kind", "<u4"), ("reserved", "<u4"), ("color", "<f8", 3), ("param", "<f8")])
 OBJECT_DTYPE = np.dtype([("kind", "<u4"), ("material", "<u4"), ("v", "<f8", 9)])
@@ -175,6 +181,10 @@ EXPORTS = {
     "crt_render_ppm": (C.c_int, [C.c_void_p, P(Camera), C.c_int, C.c_void_p, P(RenderStats)]),
     "crt_closest_hits": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_double, C.c_double,
                                    C.c_void_p]),
+    "crt_trace_async": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, P(TraceParams),
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "crt_trace": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, P(TraceParams), C.c_void_p,
+                            C.c_void_p]),
     "crt_ppm_values": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "crt_ppm_write": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "crt_render_guard": (C.c_int, [C.c_void_p, C.c_int, P(C.c_uint64), C.c_int]),

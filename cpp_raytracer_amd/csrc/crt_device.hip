@@ -26,6 +26,7 @@
 #include "crt_internal.h"
 #include "crt_hip_util.h"
 #include "crt_rows.h"
+#include "crt_ray_class.h"
 #include "crt_schlick.h"
 
 #pragma clang fp contract(off)
@@ -869,6 +870,28 @@ __device__ __forceinline__ void trav_init(const double o[3], const double d[3], 
 // and only lanes with |gap'| <= th (grazing rays, ties, rays with marg = inf) run the f64 test on
 // the f64 node. Every decision is the f64 test's, so each ray visits the reference's node
 // sequence. The f32 test is 18 single-rate instructions where the f64 one is 25 half-rate ones.
+//
+// Intervals of a query (query_kernel: any caller's t_min, a per-ray t_max of either sign, where the
+// camera has t_min = 1e-5 and t_max = +inf shrinking to hit distances). The bound above used
+// "tmin', tmax' are within u M of tmin, tmax", which takes |tmin|, |tmax| <= M for granted; it
+// holds without that. Let E bound |near' - near|. RN32 is monotone and, for |tmin| <= 2^100,
+// |tmin' - tmin| <= u |tmin| + 2^-150 (the second term: f32 underflow of a tiny t_min). Compare
+// lo' = max(near', tmin') with lo = max(near, tmin):
+//   both take the node's value: |lo' - lo| <= E; both take the bound: |lo' - lo| <= u |tmin| with
+//   |tmin| <= |lo'| (1 + 2u) <= M (1 + 2u);
+//   lo' = near' >= tmin' but tmin > near: then near' - E <= near < tmin <= tmin' + u |tmin| <=
+//   near' + u |tmin|, so -E < lo - lo' <= u |tmin| and |tmin| <= (|near'| + E) (1 + 2u);
+//   lo' = tmin' > near' but near >= tmin: then tmin' - u |tmin| <= tmin <= near <= near' + E <
+//   tmin' + E, so |lo - lo'| <= max(E, u |tmin|) with |tmin| <= |lo'| (1 + 2u).
+// In every case |lo' - lo| <= max(E, u (M + E)(1 + 2u)) + 2^-150: the bound's u M term, whatever
+// the sign or size of t_min; hi' = min(far', tmax') likewise for -2^100 <= t_max <= 2^100. A
+// larger t_max is 2^100 in f32 and never binds (|t'| < 2^82). So the call's f32 walk needs
+// |t_min| <= 2^100 (device_trace clears Work::f32_ok otherwise); t_max > t_min >= -2^100 then
+// holds for every traced ray, because a ray with an empty interval (t_max <= t_min) is never
+// traced: it would fail the node test at the sentinel, the walks' only exit (query_kernel,
+// crt_ray_class.h). The speculative and the pair walk rest on
+// t_max only shrinking during a traversal and on the test being monotone in the box; neither
+// depends on where the interval starts.
 typedef __attribute__((address_space(3))) const unsigned char LdsByte;
 struct NodeLines {
     Dvec2 b[3];  // (x.min, x.max), (y.min, y.max), (z.min, z.max)
@@ -2614,6 +2637,244 @@ __global__ __launch_bounds__(kBlock) void features_kernel(SceneView S, CamView C
     out[static_cast<size_t>(W.packed ? k : row) * C.w + col] = f;
 }
 
+// ---- ray queries on device buffers (crt_trace_async) -------------------------------------------
+// What a query launch reads and writes. Closest mode writes hits[i], any-hit mode occluded[i].
+struct Query {
+    const double* rays;       // n x {ox, oy, oz, dx, dy, dz}
+    const double* tmax;       // n per-ray upper bounds, or null: t_max
+    uint32_t n, batches;      // rays; 64-ray batches (query_kernel's queue)
+    double t_min, t_max;
+    const uint32_t* ref_prim;
+    uint32_t num_spheres;
+    crt_hit* hits;
+    uint32_t* occluded;
+    uint32_t* queue;          // query_kernel: the batch counter, zeroed before the launch
+};
+
+// one ray's result: R.found / R.ref / R.tmax as the walks leave them, through hit_record and the
+// ref -> primitive table (hits_kernel's lines)
+template <bool LS, bool SPH, bool ANY>
+__device__ __forceinline__ void write_result(const SceneView& S, const Query& Q, uint32_t ray, const double o[3],
+                                             const double d[3], bool found, uint32_t ref, double t) {
+    if (ANY) {
+        Q.occluded[ray] = found ? 1u : 0u;
+        return;
+    }
+    crt_hit h{};
+    h.prim = -1;
+    if (found) {
+        double p[3], nrm[3];
+        bool front;
+        h.material = hit_record<LS, false, SPH>(S, ref, o, d, t, p, nrm, front);
+        h.t = t;
+        for (int k = 0; k < 3; ++k) { h.point[k] = p[k]; h.normal[k] = nrm[k]; }
+        h.front_face = front ? 1 : 0;
+        const uint32_t k = (!SPH && (ref & kRefQuad)) ? Q.num_spheres + (ref & ~kRefQuad) : ref;
+        h.prim = static_cast<int32_t>(Q.ref_prim[k]);
+    }
+    Q.hits[ray] = h;
+}
+
+// CRT_TRACE_PLAIN, and the scene classes without a fast instance: hits_kernel's loop, one thread
+// per ray [first, first + gridDim.x * kBlock) of the batch, with the classification in front and a
+// per-ray upper bound.
+template <bool ANY>
+__global__ __launch_bounds__(kBlock) void plain_query_kernel(SceneView S, Query Q, uint32_t first,
+                                                             uint32_t* __restrict__ gstack) {
+    const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+    if (slot >= Q.n - first) return;
+    const uint32_t i = first + slot;
+    Stack<uint32_t> st;
+    st.base = gstack + slot;
+    st.stride = gridDim.x * kBlock;
+    const double* r = Q.rays + 6 * static_cast<size_t>(i);
+    const double o[3] = {r[0], r[1], r[2]};
+    const double d[3] = {r[3], r[4], r[5]};
+    double tmax = Q.tmax ? Q.tmax[i] : Q.t_max;
+    uint32_t ref = 0;
+    LaneCounters ctr{};
+    bool found = false;
+    if (ray_traceable(o, d, tmax) && ray_interval_open(Q.t_min, tmax))
+        found = trace<uint32_t, false>(S, st, o, d, Q.t_min, tmax, ref, ctr);
+    write_result<false, false, ANY>(S, Q, i, o, d, found, ref, tmax);
+}
+
+// The render kernel's traversal as a query engine: render_kernel's rounds (walk / walk_pairs,
+// leaf_step) with "load the next ray" where it starts a path and write_result where it shades.
+// A persistent grid; a wave takes 64 consecutive rays per atomic (Q.queue counts batches), and its
+// lanes take the batch's rays in lane order as they finish one, crossing into the next batch
+// without waiting, so neighbouring rays share a wave and a lane idles only once the queue is dry.
+// A ray outside the contract (ray_traceable) goes straight to kDone as a miss: no traversal state
+// is set up for it. The scene staging and the stack set-up are render_kernel's, copied: that
+// kernel's register allocation is tuned to the spill and is left as it is.
+// PM as in render_kernel (0: sphere-only scenes, 1: any scene). ANY: a lane whose leaf step found
+// an accepted primitive is done (occlusion: any primitive in the interval).
+// The interval: t_min is the call's (wave-uniform, tmin32 = RN32(t_min) in W.tmin32), the upper
+// bound the ray's own, and only rays with t_min < t_max are traced (crt_ray_class.h): the walks
+// end at the sentinel, which a ray enters because its own interval is not empty (lo' = tmin' <=
+// hi' = tmax' there, so the f32 test enters it or leaves it to f64, where -inf < t_max and
+// t_min < inf enter it). walk()'s f32 node test holds for any such interval with |t_min| <= 2^100
+// (its comment, "Intervals of a query"); the host clears W.f32_ok for other t_min, and every node
+// test is then decided in f64. The f32 leaf filters' slack is one-sided for t_min >= 0; the host
+// clears their flags for a negative t_min (device_trace), and the leaves then run the sequential
+// loops.
+template <typename SE, bool GSTACK, bool LSCENE, int PM, bool ANY>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LSCENE ? CRT_WAVES_PER_EU_LDS : CRT_WAVES_PER_EU, 8))) void query_kernel(
+    SceneView Sg, Work W, Query Q, SE* __restrict__ gstack) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr bool kSphOnly = PM == 0;
+    SceneView S = Sg;
+    if (LSCENE) {  // render_kernel's staging: f32 nodes at LDS offset 0, then the primitives
+        if (static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsByte*)smem)) != 0) __builtin_trap();
+        stage_lds(smem, Sg.fnodes, W.bytes_nodes);
+        stage_lds(smem + W.lds_quads, Sg.quads, W.bytes_quads);
+        S.quads = reinterpret_cast<const DevQuad*>(smem + W.lds_quads);
+        S.quads_lds = W.lds_quads;
+        if (W.quads_f32) {
+            stage_lds(smem + W.lds_quadf, W.quads_flat ? static_cast<const void*>(Sg.quadbox) : Sg.quadf, W.bytes_quadf);
+            S.quadf_lds = W.lds_quadf;
+        }
+        S.refs_lds = W.lds_refs;
+        S.spheres_lds = W.spheres_f32 ? (W.bytes_sph64 ? W.lds_sph64 : ~0u) : W.lds_spheres;
+        if (W.spheres_f32) {
+            stage_lds(smem + W.lds_spheres, Sg.spair, W.bytes_spheres);
+            if (W.bytes_sph64) stage_lds(smem + W.lds_sph64, Sg.spheres, W.bytes_sph64);
+            S.spair_lds = W.lds_spheres;
+        } else {
+            stage_lds(smem + W.lds_refs, Sg.refs, W.bytes_refs);
+            stage_lds(smem + W.lds_spheres, Sg.spheres, W.bytes_spheres);
+            S.refs = reinterpret_cast<const uint32_t*>(smem + W.lds_refs);
+            S.spheres = reinterpret_cast<const DevSphere*>(smem + W.lds_spheres);
+        }
+    } else if (W.ntop) {  // HBM scene: the top of the f32 node array in LDS
+        if (static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsByte*)smem)) != 0) __builtin_trap();
+        stage_lds(smem, Sg.fnodes, W.ntop);
+        S.ntop = W.ntop;
+    }
+    __syncthreads();
+    const float tmin32 = W.tmin32;
+    const double tmin = Q.t_min;
+    const uint32_t lane = threadIdx.x & 63;
+    LaneCounters ctr{};
+    // the lane's stack above two guard levels and one more level walk() may read (render_kernel)
+    Stack<SE> st;
+    if (GSTACK) {
+        st.stride = gridDim.x * kBlock;
+        st.base = gstack + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x) + 3 * static_cast<size_t>(st.stride);
+    } else {
+        st.base = reinterpret_cast<SE*>(smem + W.lds_stack) + threadIdx.x;
+        st.stride = kBlock;
+    }
+    st.base[-static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel);
+    st.base[-2 * static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel);
+    typedef __attribute__((address_space(3))) double LdsDouble;
+    constexpr bool kInvLds = !LSCENE && !GSTACK;  // the rays' f64 1 / d in LDS (slab64_inv)
+    constexpr bool kPair = CRT_PAIR_WALK && !LSCENE;
+    const bool pw = kPair && W.pair_walk;
+    S.inv64_lds = W.lds_inv64;
+    // the wave's batch (wave-uniform): rays [b_base, b_base + b_cnt), b_pos of them taken
+    uint32_t b_base = 0, b_cnt = 0, b_pos = 0;
+    bool dry = false;
+    uint32_t ray = 0;
+    double o[3] = {0, 0, 0}, d[3] = {0, 0, 0};
+    Trav R;
+    R.state = kIdle;
+    bool need = true;
+    while (true) {
+        set_prio<kPrioInit>();
+        bool start = false;
+        while (!dry) {
+            const uint64_t m = __ballot(need);
+            if (m == 0) break;
+            if (b_pos >= b_cnt) {  // the batch is used up: the next one
+                const uint32_t leader = static_cast<uint32_t>(__ffsll(static_cast<long long>(m)) - 1);
+                uint32_t v = 0;
+                if (lane == leader) v = atomicAdd(Q.queue, 1u);
+                const uint32_t j = __builtin_amdgcn_readlane(v, leader);
+                if (j >= Q.batches) {
+                    dry = true;
+                    break;
+                }
+                b_base = j * 64u;
+                b_pos = 0;
+                b_cnt = min(64u, Q.n - b_base);
+            }
+            const uint32_t take = min(static_cast<uint32_t>(__popcll(m)), b_cnt - b_pos);
+            const uint32_t r = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32),
+                                                         __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
+            if (need && r < take) {
+                ray = b_base + b_pos + r;
+                need = false;
+                start = true;
+            }
+            b_pos += take;
+        }
+        if (dry) need = false;
+        if (start) {
+            const double* src = Q.rays + 6 * static_cast<size_t>(ray);
+            o[0] = src[0]; o[1] = src[1]; o[2] = src[2];
+            d[0] = src[3]; d[1] = src[4]; d[2] = src[5];
+            const double tm = Q.tmax ? Q.tmax[ray] : Q.t_max;
+            if (ray_traceable(o, d, tm) && ray_interval_open(tmin, tm)) {
+                trav_init(o, d, W.f32_ok != 0, R);
+                R.tmax = tm;
+                R.tmax32 = tmax_f32(tm);
+                const bool tok = kPair && pw && !(R.neg & kZeroDir);
+                st.base[-static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel | (tok ? kTokAlone : 0u));
+                st.base[-2 * static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel | (tok ? kTokAlone : 0u));
+                if (tok) R.cur = kTokAlone;
+                if (kInvLds) {
+                    uint32_t t = threadIdx.x;
+                    asm volatile("" : "+v"(t));
+                    LdsDouble* const inv_l = (LdsDouble*)static_cast<uintptr_t>(W.lds_inv64 + t * 8);
+                    inv_l[0] = 1 / d[0];
+                    inv_l[kBlock] = 1 / d[1];
+                    inv_l[2 * kBlock] = 1 / d[2];
+                }
+            } else {  // outside the contract, or an empty interval: a miss, never traced
+                R.found = false;
+                R.ref = 0;
+                R.tmax = 0;
+                R.state = kDone;
+            }
+        }
+        // render_kernel's traversal rounds
+        while (true) {
+            set_prio<kPrioWalk>();
+            if (kPair && pw) {
+                if (__ballot(R.state == kWalk && (R.neg & kZeroDir)) != 0) {
+                    if (R.state == kWalk && (R.neg & kZeroDir))
+                        walk<SE, false, true, kTopTreelet && !LSCENE, LSCENE, GSTACK, false>(S, st, o, d, tmin, tmin32, R, ctr);
+                }
+                if (R.state == kWalk && !(R.neg & kZeroDir))
+                    walk_pairs<SE, false, kTopTreelet && !LSCENE, kInvLds>(S, st, o, d, tmin, tmin32, R, ctr);
+            } else if (!W.exact_slab && __ballot(R.state == kWalk && (R.neg & kZeroDir)) == 0) {
+                if (R.state == kWalk)
+                    walk<SE, false, false, kTopTreelet && !LSCENE, LSCENE, GSTACK, true, kInvLds>(S, st, o, d, tmin, tmin32, R, ctr);
+            } else {
+                if (R.state == kWalk) walk<SE, false, true, kTopTreelet && !LSCENE, LSCENE, GSTACK, false>(S, st, o, d, tmin, tmin32, R, ctr);
+            }
+            set_prio<kPrioLeaf>();
+            if (R.state == kLeaf) {
+                leaf_step<SE, false, kTopTreelet && !LSCENE, LSCENE>(S, st, o, d, tmin, tmin32, kSphOnly || W.sphere_only != 0,
+                                                                     W.spheres_f32 != 0, !kSphOnly && W.quads_f32 != 0,
+                                                                     !kSphOnly && W.quads_flat != 0, R, ctr);
+                if (ANY && R.found) R.state = kDone;
+            }
+            const uint64_t pending = __ballot(R.state == kWalk);
+            const int nfin = __popcll(__ballot(R.state == kDone));
+            if (pending == 0 || nfin >= kShadeBatch) break;
+        }
+        if (__ballot(R.state == kDone) == 0) break;  // every lane idle: the queue is dry
+        set_prio<kPrioShade>();
+        if (R.state == kDone) {
+            write_result<LSCENE, kSphOnly, ANY>(S, Q, ray, o, d, R.found, R.ref, R.tmax);
+            R.state = kIdle;
+            need = true;
+        }
+    }
+}
+
 // crt_pixel_variance_async: thread i = owned row i / w, column i % w. n = samples_done, or the
 // pixel's block word (adaptive_update_kernel's block numbering) without the stopped bit;
 // noise_stage1_kernel's expressions for m and the variance of the mean, without its sqrt.
@@ -3373,6 +3634,8 @@ int device_render(const crt_scene* s, int device, const crt_camera* cam, const c
     return r;
 }
 
+static int ref_prim_table(const crt_scene* cs, int device, const uint32_t** out);
+
 int device_closest_hits(crt_scene* s, int device, const double* rays, size_t n, double t_min,
                         double t_max, crt_hit* out) {
     int rc = device_upload(s, device);
@@ -3382,29 +3645,18 @@ int device_closest_hits(crt_scene* s, int device, const double* rays, size_t n, 
     DeviceGuard g(device);
     const DeviceCopy& c = s->dev[device];
     const uint32_t blocks = static_cast<uint32_t>((n + dev::kBlock - 1) / dev::kBlock);
-    // ref -> primitive index: spheres at [0, nsp), parallelograms at [nsp, nsp + nq)
-    const size_t nsp = s->num_spheres, nq = s->num_quads;
-    std::vector<uint32_t> ref_prim(std::max<size_t>(1, nsp + nq));
-    std::vector<uint32_t> dev_refs;  // a scene set up on the device has no host refs
-    const uint32_t* refs = s->refs.data();
-    if (s->refs.size() != s->num_prims) {
-        dev_refs.resize(s->num_prims);
-        HIP_TRY(hipMemcpy(dev_refs.data(), c.refs, s->num_prims * 4, hipMemcpyDeviceToHost));
-        refs = dev_refs.data();
-    }
-    for (size_t slot = 0; slot < s->num_prims; ++slot) {
-        uint32_t r = refs[slot];
-        ref_prim[(r & kRefQuad) ? nsp + (r & ~kRefQuad) : r] = s->order[slot];
-    }
+    // ref -> primitive index: the table cached beside the device copy (ref_prim_table)
+    const size_t nsp = s->num_spheres;
+    const uint32_t* d_sp = nullptr;
+    rc = ref_prim_table(s, device, &d_sp);
+    if (rc) return rc;
     double* d_rays = nullptr;
     crt_hit* d_out = nullptr;
-    uint32_t *d_sp = nullptr, *d_stack = nullptr;
+    uint32_t* d_stack = nullptr;
     HIP_TRY(hipMalloc(&d_rays, n * 6 * sizeof(double)));
     HIP_TRY(hipMalloc(&d_out, n * sizeof(crt_hit)));
-    HIP_TRY(hipMalloc(&d_sp, ref_prim.size() * 4));
     HIP_TRY(hipMalloc(&d_stack, static_cast<size_t>(s->depth + 1) * blocks * dev::kBlock * 4));
     HIP_TRY(hipMemcpy(d_rays, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_sp, ref_prim.data(), ref_prim.size() * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(dev::hits_kernel, dim3(blocks), dim3(dev::kBlock), 0, 0, view_of(c), d_rays,
                        static_cast<uint32_t>(n), t_min, t_max, d_sp, static_cast<uint32_t>(nsp), d_out, d_stack);
     hipError_t le = hipGetLastError();
@@ -3413,7 +3665,6 @@ int device_closest_hits(crt_scene* s, int device, const double* rays, size_t n, 
         se = hipMemcpy(out, d_out, n * sizeof(crt_hit), hipMemcpyDeviceToHost);
     (void)hipFree(d_rays);
     (void)hipFree(d_out);
-    (void)hipFree(d_sp);
     (void)hipFree(d_stack);
     if (le != hipSuccess) return fail(CRT_E_HIP, std::string("hits_kernel launch: ") + hipGetErrorString(le));
     if (se != hipSuccess) return fail(CRT_E_HIP, std::string("hits_kernel: ") + hipGetErrorString(se));
@@ -3664,6 +3915,220 @@ int device_render_features(const crt_scene* s, int device, const crt_camera* cam
     const hipError_t e = hipGetLastError();
     (void)hipFreeAsync(d_stack, st);
     if (e != hipSuccess) return fail(CRT_E_HIP, std::string("features_kernel launch: ") + hipGetErrorString(e));
+    return CRT_OK;
+}
+
+// ---- ray queries (crt_trace_async) -------------------------------------------------------------
+// One query_kernel launch: the grid is every resident block (CRT_GRID_BLOCKS: fewer), or as many as
+// the batches fill; scratch (HBM stacks, the batch counter) is stream-ordered from the pass pool.
+template <typename SE, bool GSTACK, bool LSCENE, int PM>
+static int launch_trace(const crt_scene* s, int device, dev::Work W, size_t lds, dev::Query Q, bool any,
+                        hipMemPool_t pool, hipStream_t stream) {
+    if (!LSCENE && !GSTACK) {  // the rays' f64 1 / d (query_kernel: kInvLds)
+        W.lds_inv64 = static_cast<uint32_t>(align16(lds));
+        lds = W.lds_inv64 + kInvBytes;
+    }
+    const void* kfn = any ? reinterpret_cast<const void*>(dev::query_kernel<SE, GSTACK, LSCENE, PM, true>)
+                          : reinterpret_cast<const void*>(dev::query_kernel<SE, GSTACK, LSCENE, PM, false>);
+    int cus = 0, per_cu = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, dev::kBlock, lds));
+    uint64_t resident = static_cast<uint64_t>(std::max(1, cus)) * std::max(1, per_cu);
+    if (const char* e = std::getenv("CRT_GRID_BLOCKS"))
+        resident = std::max<uint64_t>(1, std::min<uint64_t>(resident, static_cast<uint64_t>(std::max(1, std::atoi(e)))));
+    constexpr uint32_t kWavesPerBlock = dev::kBlock / 64;
+    const uint32_t blocks = static_cast<uint32_t>(
+        std::max<uint64_t>(1, std::min<uint64_t>(resident, (Q.batches + kWavesPerBlock - 1) / kWavesPerBlock)));
+    SE* gstack = nullptr;
+    if (GSTACK)  // levels 0..depth, two guard levels and the level below them (render_kernel's layout)
+        HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&gstack),
+                                       static_cast<size_t>(s->depth + 4) * blocks * dev::kBlock * sizeof(SE), pool, stream));
+    uint32_t* queue = nullptr;
+    HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&queue), 256, pool, stream));
+    HIP_TRY(hipMemsetAsync(queue, 0, sizeof(uint32_t), stream));
+    Q.queue = queue;
+    const dev::SceneView S = view_of(s->dev[device]);
+    if (any)
+        hipLaunchKernelGGL((dev::query_kernel<SE, GSTACK, LSCENE, PM, true>), dim3(blocks), dim3(dev::kBlock), lds, stream,
+                           S, W, Q, gstack);
+    else
+        hipLaunchKernelGGL((dev::query_kernel<SE, GSTACK, LSCENE, PM, false>), dim3(blocks), dim3(dev::kBlock), lds, stream,
+                           S, W, Q, gstack);
+    const hipError_t e = hipGetLastError();
+    (void)hipFreeAsync(queue, stream);
+    if (gstack) (void)hipFreeAsync(gstack, stream);
+    if (e != hipSuccess) return fail(CRT_E_HIP, std::string("query_kernel launch: ") + hipGetErrorString(e));
+    return CRT_OK;
+}
+
+static int launch_plain(const crt_scene* s, int device, const dev::Query& Q, bool any, hipMemPool_t pool,
+                        hipStream_t st);
+
+// dispatch_render's decisions for a query: the scene in LDS when it and the stack fit, else the top
+// of the node array and the stack, else the stack in HBM too. Four waves per SIMD throughout: the
+// five-wave and flat-parallelogram-only instances of the render kernel have no query twin (a scene
+// of axis-aligned parallelograms runs its flat-box filter in the general instance).
+template <typename SE>
+static int dispatch_trace(const crt_scene* s, int device, dev::Work W, const dev::Query& Q, bool any,
+                          hipMemPool_t pool, hipStream_t st) {
+    const size_t stack_bytes = align16(static_cast<size_t>(s->depth + 1) * dev::kBlock * sizeof(SE));
+    W.bytes_nodes = static_cast<uint32_t>(align16(s->num_dnodes * sizeof(DevNodeF)));
+    W.bytes_refs = W.spheres_f32 ? 0u : static_cast<uint32_t>(align16(s->num_prims * 4));
+    W.bytes_spheres = static_cast<uint32_t>(align16(s->num_spheres * (W.spheres_f32 ? sizeof(DevSpherePair)
+                                                                                         : sizeof(DevSphere))));
+    W.bytes_quads = static_cast<uint32_t>(align16(s->num_quads * sizeof(DevQuad)));
+    W.bytes_quadf = W.quads_f32 ? static_cast<uint32_t>(s->num_quads * (W.quads_flat ? sizeof(DevQuadBox) : sizeof(DevQuadF)))
+                                : 0u;
+    const size_t scene_bytes = static_cast<size_t>(W.bytes_nodes) + W.bytes_refs + W.bytes_spheres + W.bytes_quads +
+                               W.bytes_quadf;
+    const uint32_t level = static_cast<uint32_t>(dev::kBlock * sizeof(SE));
+    W.sentinel = static_cast<uint32_t>(s->num_dnodes - 1) << kNodeFShift;
+    // the guard levels' place, as dispatch_render lays them out
+    auto stack_at = [&](size_t data_bytes) { return static_cast<uint32_t>(std::max<size_t>(data_bytes, 2 * level) + 2 * level); };
+    if (std::getenv("CRT_NO_LDS_SCENE") == nullptr && stack_at(scene_bytes) + stack_bytes <= kLdsSceneBudget) {
+        W.lds_nodes = 0;
+        W.lds_refs = W.lds_nodes + W.bytes_nodes;
+        W.lds_spheres = W.lds_refs + W.bytes_refs;
+        W.lds_quads = W.lds_spheres + W.bytes_spheres;
+        W.lds_quadf = W.lds_quads + W.bytes_quads;
+        W.lds_sph64 = W.lds_quadf + W.bytes_quadf;
+        const uint32_t sph64 = static_cast<uint32_t>(s->num_spheres * sizeof(DevSphere));
+        if (W.spheres_f32 && stack_at(scene_bytes + sph64) + stack_bytes <= kLdsSceneBudget) W.bytes_sph64 = sph64;
+        W.lds_stack = stack_at(scene_bytes + W.bytes_sph64);
+        const size_t lds = W.lds_stack + stack_bytes;
+        // Scenes this small are traced faster by the plain loop (rays of a few node tests each: the
+        // persistent grid's per-ray costs dominate; DESIGN section 6d has the figures), so that is
+        // their route; CRT_TRACE_FAST=1 takes the LDS-scene instances (tests, tools/ray_query_rate.py)
+        if (std::getenv("CRT_TRACE_FAST") == nullptr) return launch_plain(s, device, Q, any, pool, st);
+        if (W.sphere_only) return launch_trace<SE, false, true, 0>(s, device, W, lds, Q, any, pool, st);
+        return launch_trace<SE, false, true, 1>(s, device, W, lds, Q, any, pool, st);
+    }
+    const size_t per_block = 160 * 1024 * dev::kBlock / (256 * CRT_WAVES_PER_EU);
+    const bool no_top = std::getenv("CRT_NO_LDS_TOP") != nullptr;
+    const size_t all_nodes = s->num_dnodes * sizeof(DevNodeF);
+    auto top_bytes = [&](size_t room) {  // whole 64-byte sibling pairs
+        return no_top ? 0u : static_cast<uint32_t>(std::min(all_nodes, room / (2 * sizeof(DevNodeF)) * (2 * sizeof(DevNodeF))));
+    };
+    if (stack_bytes <= kLdsStackBudget && std::getenv("CRT_FORCE_GSTACK") == nullptr) {
+        const size_t taken = stack_bytes + 3 * level + kInvBytes;
+        const size_t room = per_block > taken ? per_block - taken : 0;
+        W.ntop = top_bytes(room);
+        W.lds_nodes = 0;
+        W.lds_stack = stack_at(align16(W.ntop));
+        if (W.sphere_only) return launch_trace<SE, false, false, 0>(s, device, W, W.lds_stack + stack_bytes, Q, any, pool, st);
+        return launch_trace<SE, false, false, 1>(s, device, W, W.lds_stack + stack_bytes, Q, any, pool, st);
+    }
+    W.ntop = top_bytes(per_block);
+    W.lds_nodes = 0;
+    if (W.sphere_only) return launch_trace<SE, true, false, 0>(s, device, W, W.ntop, Q, any, pool, st);
+    return launch_trace<SE, true, false, 1>(s, device, W, W.ntop, Q, any, pool, st);
+}
+
+// CRT_TRACE_PLAIN: plain_query_kernel over the batch in launches of at most kPlainRays rays that
+// share one set of stacks (stream order keeps them apart)
+static int launch_plain(const crt_scene* s, int device, const dev::Query& Q, bool any, hipMemPool_t pool,
+                        hipStream_t st) {
+    constexpr uint32_t kPlainRays = 1u << 20;
+    const uint32_t per = std::min<uint32_t>(Q.n, kPlainRays);
+    const uint32_t max_blocks = (per + dev::kBlock - 1) / dev::kBlock;
+    uint32_t* d_stack = nullptr;  // trace()'s stacks, [level][thread]
+    HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&d_stack),
+                                   static_cast<size_t>(s->depth + 1) * max_blocks * dev::kBlock * 4, pool, st));
+    const dev::SceneView S = view_of(s->dev[device]);
+    hipError_t e = hipSuccess;
+    for (uint64_t first = 0; first < Q.n && e == hipSuccess; first += kPlainRays) {
+        // the same grid for every launch (the stacks' stride is its thread count); the kernel
+        // bounds itself by the rays left
+        if (any)
+            hipLaunchKernelGGL(dev::plain_query_kernel<true>, dim3(max_blocks), dim3(dev::kBlock), 0, st, S, Q,
+                               static_cast<uint32_t>(first), d_stack);
+        else
+            hipLaunchKernelGGL(dev::plain_query_kernel<false>, dim3(max_blocks), dim3(dev::kBlock), 0, st, S, Q,
+                               static_cast<uint32_t>(first), d_stack);
+        e = hipGetLastError();
+    }
+    (void)hipFreeAsync(d_stack, st);
+    if (e != hipSuccess) return fail(CRT_E_HIP, std::string("plain_query_kernel launch: ") + hipGetErrorString(e));
+    return CRT_OK;
+}
+
+int device_trace(const crt_scene* s, int device, const double* d_rays, size_t n, const double* d_tmax,
+                 const crt_trace_params* prm, crt_hit* d_hits, uint32_t* d_occluded, void* stream) {
+    int rc = check_device(device);
+    if (rc) return rc;
+    if (!s->dev[device].valid)
+        return fail(CRT_E_NOT_UPLOADED, "scene not uploaded to device " + std::to_string(device));
+    if (n == 0) return CRT_OK;
+    DeviceGuard g(device);
+    const bool any = (prm->flags & CRT_TRACE_ANY) != 0;
+    dev::Query Q{};
+    Q.rays = d_rays;
+    Q.tmax = d_tmax;
+    Q.n = static_cast<uint32_t>(n);
+    Q.batches = static_cast<uint32_t>((n + 63) / 64);
+    Q.t_min = prm->t_min;
+    Q.t_max = prm->t_max;
+    Q.num_spheres = static_cast<uint32_t>(s->num_spheres);
+    Q.hits = d_hits;
+    Q.occluded = d_occluded;
+    if (!any) {  // the first call builds and uploads the table, blocking
+        rc = ref_prim_table(s, device, &Q.ref_prim);
+        if (rc) return rc;
+    }
+    hipMemPool_t pool = nullptr;
+    rc = pass_pool(device, &pool);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (prm->flags & CRT_TRACE_PLAIN) return launch_plain(s, device, Q, any, pool, st);
+    // device_render's scene classes; the walk's and the filters' interval rules (walk(), query_kernel)
+    const DeviceCopy& c = s->dev[device];
+    dev::Work W{};
+    const bool filters = prm->t_min >= 0;
+    W.f32_ok = (c.f32_ok && std::fabs(prm->t_min) <= 0x1p100) ? 1u : 0u;
+    W.tmin32 = static_cast<float>(prm->t_min);
+    W.sphere_only = (s->num_quads == 0 && s->num_spheres != 0) ? 1u : 0u;
+    W.spheres_f32 = (W.sphere_only && c.spheres_f32_ok && filters) ? 1u : 0u;
+    W.quads_f32 = (s->num_spheres == 0 && s->num_quads != 0 && c.quads_f32_ok && filters) ? 1u : 0u;
+    W.quads_flat = (W.quads_f32 && c.quads_flat_ok && W.f32_ok) ? 1u : 0u;
+    W.exact_slab = (s->exact_slab || std::getenv("CRT_EXACT_SLAB") != nullptr) ? 1u : 0u;
+    W.pair_walk = (CRT_PAIR_WALK && !W.exact_slab && std::getenv("CRT_NO_PAIR_WALK") == nullptr) ? 1u : 0u;
+    if ((s->num_dnodes << kNodeFShift) <= 65536) return dispatch_trace<uint16_t>(s, device, W, Q, any, pool, st);
+    return dispatch_trace<uint32_t>(s, device, W, Q, any, pool, st);
+}
+
+// crt_trace: device_trace for host arrays, blocking: one upload of the rays (and bounds), one query,
+// one copy back, on a stream of its own
+int device_trace_host(crt_scene* s, int device, const double* rays, size_t n, const double* tmax,
+                      const crt_trace_params* prm, crt_hit* hits, uint32_t* occluded) {
+    int rc = device_upload(s, device);
+    if (rc) return rc;
+    DeviceGuard g(device);
+    const bool any = (prm->flags & CRT_TRACE_ANY) != 0;
+    const size_t out_bytes = n * (any ? sizeof(uint32_t) : sizeof(crt_hit));
+    void* host_out = any ? static_cast<void*>(occluded) : static_cast<void*>(hits);
+    double *d_rays = nullptr, *d_tmax = nullptr;
+    void* d_out = nullptr;
+    hipStream_t st = nullptr;
+    hipError_t e = hipStreamCreate(&st);
+    if (e == hipSuccess) e = hipMalloc(&d_rays, n * 6 * sizeof(double));
+    if (e == hipSuccess && tmax) e = hipMalloc(&d_tmax, n * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&d_out, out_bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rays, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && tmax) e = hipMemcpyAsync(d_tmax, tmax, n * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        rc = device_trace(s, device, d_rays, n, d_tmax, prm, any ? nullptr : static_cast<crt_hit*>(d_out),
+                          any ? static_cast<uint32_t*>(d_out) : nullptr, st);
+    if (e == hipSuccess && rc == CRT_OK) e = hipMemcpyAsync(host_out, d_out, out_bytes, hipMemcpyDeviceToHost, st);
+    if (st) {
+        const hipError_t se = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = se;
+        (void)hipStreamDestroy(st);
+    }
+    (void)hipFree(d_rays);
+    (void)hipFree(d_tmax);
+    (void)hipFree(d_out);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(CRT_E_HIP, std::string("crt_trace: ") + hipGetErrorString(e));
     return CRT_OK;
 }
 

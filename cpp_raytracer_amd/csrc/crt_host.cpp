@@ -1483,6 +1483,46 @@ int crt_ppm_write(const char* path, uint32_t w, uint32_t h, const int32_t* value
     return ok ? CRT_OK : fail(CRT_E_INVALID, std::string("crt_ppm_write: write failed: ") + path);
 }
 
+// ---- ray queries: every rule is checked here, before any device work ---------------------------
+static int check_trace(const std::string& who, const void* s, const void* rays, const char* rays_name, size_t n,
+                       const crt_trace_params* params, const void* hits, const char* hits_name, const void* occluded,
+                       const char* occ_name) {
+    if (!s) return fail(CRT_E_INVALID, who + "scene is null");
+    if (!params) return fail(CRT_E_INVALID, who + "params is null");
+    if (params->flags & ~(CRT_TRACE_ANY | CRT_TRACE_PLAIN)) return fail(CRT_E_INVALID, who + "unknown flags");
+    if (params->reserved != 0) return fail(CRT_E_INVALID, who + "params->reserved must be 0");
+    if (!std::isfinite(params->t_min)) return fail(CRT_E_INVALID, who + "t_min must be finite");
+    if (std::isnan(params->t_max)) return fail(CRT_E_INVALID, who + "t_max must not be NaN");
+    if (n > 0x7fffffffu) return fail(CRT_E_INVALID, who + "more than 2^31-1 rays");
+    if (params->flags & CRT_TRACE_ANY) {
+        if (hits) return fail(CRT_E_INVALID, who + hits_name + " must be null with CRT_TRACE_ANY");
+        if (n && !occluded) return fail(CRT_E_INVALID, who + occ_name + " is null (the output of CRT_TRACE_ANY)");
+    } else {
+        if (occluded) return fail(CRT_E_INVALID, who + occ_name + " must be null without CRT_TRACE_ANY");
+        if (n && !hits) return fail(CRT_E_INVALID, who + hits_name + " is null (the output is required)");
+    }
+    if (n && !rays) return fail(CRT_E_INVALID, who + rays_name + " is null");
+    return CRT_OK;
+}
+
+int crt_trace_async(const crt_scene* s, int device, const double* d_rays, size_t n, const double* d_tmax,
+                    const crt_trace_params* params, crt_hit* d_hits, uint32_t* d_occluded, void* stream) {
+    clear_error();
+    const int rc = check_trace("crt_trace_async: ", s, d_rays, "d_rays", n, params, d_hits, "d_hits", d_occluded, "d_occluded");
+    if (rc) return rc;
+    if (n == 0) return CRT_OK;  // no work
+    return device_trace(s, device, d_rays, n, d_tmax, params, d_hits, d_occluded, stream);
+}
+
+int crt_trace(crt_scene* s, int device, const double* rays, size_t n, const double* tmax,
+              const crt_trace_params* params, crt_hit* hits, uint32_t* occluded) {
+    clear_error();
+    const int rc = check_trace("crt_trace: ", s, rays, "rays", n, params, hits, "hits", occluded, "occluded");
+    if (rc) return rc;
+    if (n == 0) return CRT_OK;
+    return device_trace_host(s, device, rays, n, tmax, params, hits, occluded);
+}
+
 int crt_closest_hits(crt_scene* s, int device, const double* rays, size_t n, double t_min,
                      double t_max, crt_hit* out) {
     clear_error();

@@ -406,6 +406,12 @@ bool device_redo_gather(const double* d_rgb, const uint32_t* d_list, uint32_t n,
 bool device_scale(const double* d_sum, double* d_out, uint64_t count, double factor, void* stream);
 int device_closest_hits(crt_scene* s, int device, const double* rays, size_t n, double t_min,
                         double t_max, crt_hit* out);
+// ray queries on device buffers (crt_trace_async, which checks the arguments): enqueued on `stream`
+int device_trace(const crt_scene* s, int device, const double* d_rays, size_t n, const double* d_tmax,
+                 const crt_trace_params* prm, crt_hit* d_hits, uint32_t* d_occluded, void* stream);
+// crt_trace: the same query for host arrays, blocking (uploads the scene if needed)
+int device_trace_host(crt_scene* s, int device, const double* rays, size_t n, const double* tmax,
+                      const crt_trace_params* prm, crt_hit* hits, uint32_t* occluded);
 // denoising: first-hit features and the per-pixel variance (crt_device.hip), the filter
 // (crt_denoise.hip); the callers check the arguments
 int device_render_features(const crt_scene* s, int device, const crt_camera* cam, const crt_tiling* t,

@@ -134,6 +134,17 @@ public:
 
     const crt_api::GpuScene& gpu_scene() const { return *scene; }
 
+    // the C ABI's ray records: {ox, oy, oz, dx, dy, dz}
+    static std::vector<double> crt_rays(const std::vector<Ray3D>& rays) {
+        std::vector<double> r(rays.size() * 6);
+        for (size_t i = 0; i < rays.size(); ++i) {
+            const Ray3D& q = rays[i];
+            const double v[6] = {q.origin.x, q.origin.y, q.origin.z, q.dir.x, q.dir.y, q.dir.z};
+            for (int k = 0; k < 6; ++k) r[6 * i + k] = v[k];
+        }
+        return r;
+    }
+
     // BVH::hit_by (bvh.h:585-715) for one ray, on the GPU
     std::optional<hit_info> hit_by(const Ray3D& ray, const Interval& t) const override {
         double r[6] = {ray.origin.x, ray.origin.y, ray.origin.z, ray.dir.x, ray.dir.y, ray.dir.z};
@@ -146,6 +157,37 @@ public:
         info.hit_from_outside = h.front_face != 0;
         info.unit_surface_normal = Vec3D{h.normal[0], h.normal[1], h.normal[2]};
         return info;
+    }
+
+    // Not in the reference: hit_by for a batch of rays over one interval, through the render
+    // kernel's traversal (crt_trace: one upload of the rays, one launch, one copy back). Element i
+    // is what hit_by(rays[i], t) returns. A ray with a non-finite component or an all-zero
+    // direction is not traced: no hit.
+    std::vector<std::optional<hit_info>> hit_by_batch(const std::vector<Ray3D>& rays, const Interval& t) const {
+        std::vector<crt_hit> h(rays.size());
+        const std::vector<double> r = crt_rays(rays);
+        const crt_trace_params p{t.min, t.max, 0u, 0u};
+        if (crt_trace(scene->get(), 0, r.data(), rays.size(), nullptr, &p, h.data(), nullptr)) crt_api::die("crt_trace");
+        std::vector<std::optional<hit_info>> out(rays.size());
+        for (size_t i = 0; i < rays.size(); ++i) {
+            if (h[i].prim < 0) continue;
+            hit_info info(h[i].t, Point3D{h[i].point[0], h[i].point[1], h[i].point[2]},
+                          Vec3D{h[i].normal[0], h[i].normal[1], h[i].normal[2]}, rays[i], scene->materials[h[i].material]);
+            info.hit_from_outside = h[i].front_face != 0;
+            info.unit_surface_normal = Vec3D{h[i].normal[0], h[i].normal[1], h[i].normal[2]};
+            out[i] = info;
+        }
+        return out;
+    }
+
+    // Not in the reference: element i says whether hit_by(rays[i], t) would return a hit
+    // (occlusion: the traversal stops at the first accepted primitive).
+    std::vector<bool> occluded_batch(const std::vector<Ray3D>& rays, const Interval& t) const {
+        std::vector<uint32_t> occ(rays.size());
+        const std::vector<double> r = crt_rays(rays);
+        const crt_trace_params p{t.min, t.max, CRT_TRACE_ANY, 0u};
+        if (crt_trace(scene->get(), 0, r.data(), rays.size(), nullptr, &p, nullptr, occ.data())) crt_api::die("crt_trace");
+        return std::vector<bool>(occ.begin(), occ.end());
     }
 
     AABB get_aabb() const override { return bounds; }

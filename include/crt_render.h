@@ -532,6 +532,42 @@ int crt_render_ppm(crt_scene* scene, const crt_camera* cam, int num_devices, int
 int crt_closest_hits(crt_scene* scene, int device, const double* rays, size_t n,
                      double t_min, double t_max, crt_hit* out);
 
+/* Ray queries on device buffers: crt_closest_hits without the host round trip, through the render
+ * kernel's traversal (f32 node test, LDS scene and stack, speculative and sibling-pair walks, f32
+ * leaf filters). */
+#define CRT_TRACE_ANY   1u  /* occlusion: is there any accepted primitive in the interval */
+#define CRT_TRACE_PLAIN 2u  /* hits_kernel's walk (trace()) on the same buffers: the cross-check and the A/B */
+typedef struct crt_trace_params {
+    double t_min, t_max;      /* exclusive interval, as BVH::hit_by; t_min finite, t_max not NaN (+inf allowed) */
+    uint32_t flags, reserved; /* unknown flag bits or reserved != 0: CRT_E_INVALID */
+} crt_trace_params;           /* 24 bytes */
+
+/* d_rays: DEVICE memory on `device`, n x {ox, oy, oz, dx, dy, dz}. d_tmax: DEVICE, n doubles, or
+ * NULL; with it ray i's upper bound is d_tmax[i] instead of params->t_max (t_min is call-wide).
+ * Closest mode (no CRT_TRACE_ANY): d_hits[i] (DEVICE, n records) is exactly the record
+ *   crt_closest_hits writes for that ray and interval (a miss: prim = -1, every other field zero);
+ *   d_occluded must be NULL.
+ * Any mode (CRT_TRACE_ANY): d_occluded[i] (DEVICE, n words) = 1 iff closest mode would report
+ *   prim >= 0, else 0; d_hits must be NULL.
+ * A ray with a non-finite component, an all-zero direction or a NaN upper bound is outside the
+ * contract: it is not traced and is written as a miss.
+ * The scene must be resident on `device` (CRT_E_NOT_UPLOADED). The first closest-mode call for a
+ * scene and device builds the table of primitive numbers and uploads it, blocking (the table
+ * crt_render_features_async uses); after that the call only enqueues on `stream`. Scratch comes
+ * from the pass pool. n == 0 is CRT_OK with no work. CRT_E_INVALID, checked before any device work
+ * (the message names the rule): n > 2^31 - 1, d_rays or params NULL, t_min not finite, t_max NaN,
+ * unknown flags, reserved != 0, an output pointer missing for the mode or given for the other one.
+ * Both routes obey the render kernel's run-time switches. */
+int crt_trace_async(const crt_scene* scene, int device, const double* d_rays, size_t n,
+                    const double* d_tmax, const crt_trace_params* params,
+                    crt_hit* d_hits, uint32_t* d_occluded, void* stream);
+
+/* crt_trace_async for HOST arrays, blocking: uploads the scene to `device` if it is not resident,
+ * then one upload of the rays (and bounds), one query on a stream of its own, one copy back. Same
+ * rules, same results (the C++ drop-in's BVH::hit_by_batch / occluded_batch). */
+int crt_trace(crt_scene* scene, int device, const double* rays, size_t n, const double* tmax,
+              const crt_trace_params* params, crt_hit* hits, uint32_t* occluded);
+
 /* The integers Image::send_as_ppm prints (image.h:38-56; RGB::as_string rgb.h:99-115 with its
  * defaults: Reinhard tone map by luminance, gamma 2, static_cast<int>(255.999999 * v)) for the
  * n-pixel frame d_rgb (device memory on `device`, row-major RGB f64, e.g. crt_render_async's
