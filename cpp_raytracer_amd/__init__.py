@@ -20,7 +20,7 @@ from ._capi import (CRT_BOX, CRT_DIELECTRIC, CRT_DIFFUSE_LIGHT, CRT_LAMBERTIAN, 
                     CRT_PARALLELOGRAM, CRT_SPHERE, HIT_DTYPE, MATERIAL_DTYPE, NODE_DTYPE,
                     OBJECT_DTYPE, CRT_BLOCK_STOPPED, FEATURE_DTYPE, BVHParams, Camera, CameraSettings, CrtError,
                     DenoiseParams, RenderStats, SceneInfo, Tiling, TraceParams, CRT_TRACE_ANY, CRT_TRACE_PLAIN,
-                    check, lib)
+                    RadianceParams, CRT_RADIANCE_PLAIN, check, lib)
 
 __all__ = [
     "SceneData", "GpuScene", "CameraSettings", "Camera", "Tiling", "RenderStats", "CrtError",
@@ -28,6 +28,7 @@ __all__ = [
     "sample_chunk_len", "noise_estimate", "block_count", "adaptive_update", "CRT_BLOCK_STOPPED",
     "DenoiseParams", "FEATURE_DTYPE", "denoise_params", "pixel_variance", "denoise",
     "TraceParams", "CRT_TRACE_ANY", "CRT_TRACE_PLAIN", "HIT_DTYPE",
+    "RadianceParams", "CRT_RADIANCE_PLAIN",
     "CRT_LAMBERTIAN", "CRT_METAL", "CRT_DIELECTRIC", "CRT_DIFFUSE_LIGHT",
     "CRT_SPHERE", "CRT_PARALLELOGRAM", "CRT_BOX",
 ]
@@ -504,3 +505,82 @@ class GpuScene:
                                  tmax.data_ptr() if tmax is not None else 0, flags,
                                  torch.cuda.current_stream(device).cuda_stream)
             return out != 0 if any_hit else out
+
+    def radiance_async(self, device: int, rays_ptr: int, n: int, out_ptr: int, states_ptr: int = 0, *,
+                       max_depth: int, background, t_min: float = 1e-5, base_seed: int = 0, flags: int = 0,
+                       stream: int = 0) -> None:
+        """Enqueue a radiance query on device buffers (crt_radiance_async): n rays of 6 doubles at
+        rays_ptr, each the first segment of one path of ray_color with `max_depth` bounces over
+        (t_min, inf). Path i's LCG state is the uint32 states_ptr[i], or sample_seed(base_seed, i, 0)
+        with states_ptr = 0. Three doubles a path go to out_ptr: what the sample adds to a pixel's
+        sum in a render. CRT_RADIANCE_PLAIN takes one thread a path: the same bits. The scene must be
+        uploaded to `device`."""
+        prm = RadianceParams(max_depth, base_seed & 0xFFFFFFFF, _capi.D3(*[float(v) for v in background]), t_min,
+                             flags, 0)
+        check(lib().crt_radiance_async(self._h, device, C.c_void_p(rays_ptr or None), n, C.c_void_p(states_ptr or None),
+                                       C.byref(prm), C.c_void_p(out_ptr or None), C.c_void_p(stream)),
+              "crt_radiance_async")
+
+    def radiance(self, rays, states=None, max_depth: int = 50, background=(0.7, 0.8, 1.0), t_min: float = 1e-5,
+                 base_seed: int = 0, plain: bool = False):
+        """Path-traced radiance of the caller's rays on torch tensors of a GPU: rays (n, 6) float64,
+        states None or an (n,) int32 tensor on the rays' device whose bits are the paths' LCG states
+        (None: sample_seed(base_seed, i, 0)). Runs on the rays' device and its current stream and
+        does not synchronise; the scene is uploaded there first if it is not yet (that blocks).
+        Returns an (n, 3) float64 tensor."""
+        import torch
+        if not (rays.is_cuda and rays.dtype == torch.float64 and rays.dim() == 2 and rays.shape[1] == 6):
+            raise CrtError("radiance: rays must be an (n, 6) float64 tensor on a GPU")
+        rays = rays.contiguous()
+        n, device = rays.shape[0], rays.device.index
+        if states is not None:
+            if not (states.is_cuda and states.device == rays.device and states.dtype == torch.int32 and
+                    states.shape == (n,)):
+                raise CrtError("radiance: states must be an (n,) int32 tensor on the rays' device")
+            states = states.contiguous()
+        with torch.cuda.device(device):
+            out = torch.empty((n, 3), dtype=torch.float64, device=rays.device)
+            if n:
+                self.upload(device)
+                self.radiance_async(device, rays.data_ptr(), n, out.data_ptr(),
+                                    states.data_ptr() if states is not None else 0, max_depth=max_depth,
+                                    background=background, t_min=t_min, base_seed=base_seed,
+                                    flags=CRT_RADIANCE_PLAIN if plain else 0,
+                                    stream=torch.cuda.current_stream(device).cuda_stream)
+            return out
+
+    def camera_rays(self, cam: Camera, first_sample: int = 0, num_samples: Optional[int] = None,
+                    tiling: Optional[Tiling] = None, device: int = 0):
+        """The camera's own rays and the LCG states after their draws (crt_camera_rays_async), on
+        `device` and its current stream, without synchronising: (rays (n, 6) float64, states (n,)
+        int32) for the tiling's owned pixels (None: the whole frame; owned rows in order, packed) and
+        samples [first_sample, first_sample + num_samples) (None: up to cam.samples_per_pixel), record
+        pixel * num_samples + (sample - first_sample). radiance(rays, states, cam.max_depth,
+        cam.background, cam.t_min) is then the per-sample radiance of a render with cam."""
+        import torch
+        from .tiles import owned_rows
+        if not isinstance(cam, Camera):
+            raise CrtError("camera_rays: cam must be a resolved Camera (resolve_camera)")
+        if num_samples is None:
+            num_samples = cam.samples_per_pixel - first_sample
+        if first_sample < 0 or num_samples < 0:
+            raise CrtError("camera_rays: first_sample and num_samples must not be negative")
+        if first_sample + num_samples > 0xFFFFFFFF:
+            raise CrtError("camera_rays: first_sample + num_samples exceeds 2^32-1")
+        rows = cam.image_h
+        if tiling is not None:
+            if not isinstance(tiling, Tiling) or tiling.row_block == 0 or tiling.tile_index >= tiling.tile_count:
+                raise CrtError("camera_rays: bad tiling")
+            rows = len(owned_rows(cam.image_h, tiling.row_block, tiling.tile_count, tiling.tile_index))
+        n = rows * cam.image_w * num_samples
+        with torch.cuda.device(device):
+            dev = torch.device("cuda", device)
+            rays = torch.empty((n, 6), dtype=torch.float64, device=dev)
+            states = torch.empty((n,), dtype=torch.int32, device=dev)
+            if n:
+                check(lib().crt_camera_rays_async(device, C.byref(cam), C.byref(tiling) if tiling is not None else None,
+                                                  first_sample, num_samples, C.c_void_p(rays.data_ptr()),
+                                                  C.c_void_p(states.data_ptr()),
+                                                  C.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+                      "crt_camera_rays_async")
+            return rays, states

@@ -108,6 +108,15 @@ class TraceParams(C.Structure):
 
 CRT_TRACE_ANY, CRT_TRACE_PLAIN = 1, 2
 
+
+class RadianceParams(C.Structure):
+    _fields_ = [("max_depth", C.c_uint32), ("base_seed", C.c_uint32), ("background", D3), ("t_min", C.c_double),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+CRT_RADIANCE_PLAIN = 1
+assert C.sizeof(RadianceParams) == 48
+
 # numpy views of the same records (for bulk scene I/O)
 MATERIAL_DTYPE = np.dtype([("kind", "<u4"), ("reserved", "<u4"), ("color", "<f8", 3), ("param", "<f8")])
 OBJECT_DTYPE = np.dtype([("kind", "<u4"), ("material", "<u4"), ("v", "<f8", 9)])
@@ -185,6 +194,12 @@ EXPORTS = {
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "crt_trace": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, P(TraceParams), C.c_void_p,
                             C.c_void_p]),
+    "crt_radiance_async": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, P(RadianceParams),
+                                     C.c_void_p, C.c_void_p]),
+    "crt_radiance": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, P(RadianceParams),
+                               C.c_void_p]),
+    "crt_camera_rays_async": (C.c_int, [C.c_int, P(Camera), P(Tiling), C.c_uint32, C.c_uint32, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     "crt_ppm_values": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "crt_ppm_write": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "crt_render_guard": (C.c_int, [C.c_void_p, C.c_int, P(C.c_uint64), C.c_int]),

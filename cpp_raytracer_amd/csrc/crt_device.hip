@@ -2875,6 +2875,252 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LSCENE ?
     }
 }
 
+// ---- radiance queries on device buffers (crt_radiance_async) -----------------------------------
+// What a radiance launch reads and writes: path i starts on rays[i] with the LCG state states[i]
+// (null: sample_seed(base_seed, i, 0)) and writes rgb[3i .. 3i + 2]. The background and the call's
+// t_min travel in a CamView (shade reads C.bg), the depth here.
+struct Radiance {
+    const double* rays;       // n x {ox, oy, oz, dx, dy, dz}
+    const uint32_t* states;   // n LCG states before ray_color's first draw, or null
+    double* rgb;              // n x 3
+    uint32_t n, batches;      // paths; 64-path batches (radiance_kernel's queue)
+    uint32_t max_depth;       // > 0: a call with depth 0 is answered without a launch
+    uint32_t base_seed;
+    uint32_t* queue;          // radiance_kernel: the batch counter, zeroed before the launch
+};
+
+// path `ray` of a launch, before its first segment. False: the caller's ray is outside the query
+// contract (crt_ray_class.h) and must not be traced; shade's miss branch then gives 0 + 1 * bg.
+__device__ __forceinline__ bool load_path(const Radiance& Q, uint32_t ray, Path& P) {
+    const double* src = Q.rays + 6 * static_cast<size_t>(ray);
+    P.o[0] = src[0]; P.o[1] = src[1]; P.o[2] = src[2];
+    P.d[0] = src[3]; P.d[1] = src[4]; P.d[2] = src[5];
+    P.T[0] = 1; P.T[1] = 1; P.T[2] = 1;
+    P.depth = Q.max_depth;
+    P.rng = Q.states ? Q.states[ray] : sample_seed(Q.base_seed, ray, 0);
+    return ray_traceable(P.o, P.d, __builtin_inf());
+}
+
+// CRT_RADIANCE_PLAIN: ray_color as a loop of trace() and shade, one thread per path
+// [first, first + gridDim.x * kBlock) of the call. Scattered rays go to trace() as they are: it is
+// the reference's sequence for any ray.
+__global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, CamView C, Radiance Q, uint32_t first,
+                                                                uint32_t* __restrict__ gstack) {
+    const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+    if (slot >= Q.n - first) return;
+    const uint32_t i = first + slot;
+    Stack<uint32_t> st;
+    st.base = gstack + slot;
+    st.stride = gridDim.x * kBlock;
+    Path P;
+    bool traced = load_path(Q, i, P);
+    LaneCounters ctr{};
+    double acc[3] = {0, 0, 0};
+    while (true) {
+        double tmax = __builtin_inf();
+        uint32_t ref = 0;
+        const bool found = traced && trace<uint32_t, false>(S, st, P.o, P.d, C.t_min, tmax, ref, ctr);
+        traced = true;
+        if (shade<false>(S, C, P, found, ref, tmax, acc) || P.depth == 0) break;
+    }
+    double* dst = Q.rgb + 3 * static_cast<size_t>(i);
+    dst[0] = acc[0];
+    dst[1] = acc[1];
+    dst[2] = acc[2];
+}
+
+// The render kernel's integrator as a query engine: query_kernel's front end (the persistent grid,
+// the batch queue, "load the next ray") joined to render_kernel's back end (shade, then continue
+// the scattered ray or end the path). A lane keeps its path over all its segments; a path that
+// ends stores 0 + T * (emit | background), or +0, and the lane asks for the next ray.
+// The caller's ray is classified before any traversal state exists (load_path); one outside the
+// contract goes to kDone as a miss and is shaded as one. Scattered rays are render_kernel's: set up
+// by the common trav_init block, which rewrites both guard levels (the f32 walk's store at the
+// sentinel overwrote one). Every segment runs over (t_min, +inf) with t_min >= 0 (the ABI's rule),
+// so the leaf filters hold as in a render. The staging and the stack set-up are query_kernel's,
+// copied like that kernel's; the camera copy in LDS is render_kernel's (shade reads the background
+// from it).
+template <typename SE, bool GSTACK, bool LSCENE, int PM>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LSCENE ? CRT_WAVES_PER_EU_LDS : CRT_WAVES_PER_EU, 8))) void radiance_kernel(
+    SceneView Sg, CamView C, Work W, Radiance Q, SE* __restrict__ gstack) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr bool kSphOnly = PM == 0;
+    SceneView S = Sg;
+    if (LSCENE) {  // render_kernel's staging: f32 nodes at LDS offset 0, then the primitives
+        if (static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsByte*)smem)) != 0) __builtin_trap();
+        stage_lds(smem, Sg.fnodes, W.bytes_nodes);
+        stage_lds(smem + W.lds_quads, Sg.quads, W.bytes_quads);
+        S.quads = reinterpret_cast<const DevQuad*>(smem + W.lds_quads);
+        S.quads_lds = W.lds_quads;
+        if (W.quads_f32) {
+            stage_lds(smem + W.lds_quadf, W.quads_flat ? static_cast<const void*>(Sg.quadbox) : Sg.quadf, W.bytes_quadf);
+            S.quadf_lds = W.lds_quadf;
+        }
+        S.refs_lds = W.lds_refs;
+        S.spheres_lds = W.spheres_f32 ? (W.bytes_sph64 ? W.lds_sph64 : ~0u) : W.lds_spheres;
+        if (W.spheres_f32) {
+            stage_lds(smem + W.lds_spheres, Sg.spair, W.bytes_spheres);
+            if (W.bytes_sph64) stage_lds(smem + W.lds_sph64, Sg.spheres, W.bytes_sph64);
+            S.spair_lds = W.lds_spheres;
+        } else {
+            stage_lds(smem + W.lds_refs, Sg.refs, W.bytes_refs);
+            stage_lds(smem + W.lds_spheres, Sg.spheres, W.bytes_spheres);
+            S.refs = reinterpret_cast<const uint32_t*>(smem + W.lds_refs);
+            S.spheres = reinterpret_cast<const DevSphere*>(smem + W.lds_spheres);
+        }
+    } else if (W.ntop) {  // HBM scene: the top of the f32 node array in LDS
+        if (static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsByte*)smem)) != 0) __builtin_trap();
+        stage_lds(smem, Sg.fnodes, W.ntop);
+        S.ntop = W.ntop;
+    }
+    if (threadIdx.x == 0) *reinterpret_cast<CamView*>(smem + W.lds_cam) = C;
+    __syncthreads();
+    const CamView& CL = *reinterpret_cast<const CamView*>(smem + W.lds_cam);
+    const float tmin32 = W.tmin32;
+    const double tmin = C.t_min;
+    const uint32_t lane = threadIdx.x & 63;
+    LaneCounters ctr{};
+    // the lane's stack above two guard levels and one more level walk() may read (render_kernel)
+    Stack<SE> st;
+    if (GSTACK) {
+        st.stride = gridDim.x * kBlock;
+        st.base = gstack + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x) + 3 * static_cast<size_t>(st.stride);
+    } else {
+        st.base = reinterpret_cast<SE*>(smem + W.lds_stack) + threadIdx.x;
+        st.stride = kBlock;
+    }
+    st.base[-static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel);
+    st.base[-2 * static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel);
+    typedef __attribute__((address_space(3))) double LdsDouble;
+    constexpr bool kInvLds = !LSCENE && !GSTACK;  // the rays' f64 1 / d in LDS (slab64_inv)
+    constexpr bool kPair = CRT_PAIR_WALK && !LSCENE;
+    const bool pw = kPair && W.pair_walk;
+    S.inv64_lds = W.lds_inv64;
+    // the wave's batch (wave-uniform): paths [b_base, b_base + b_cnt), b_pos of them taken
+    uint32_t b_base = 0, b_cnt = 0, b_pos = 0;
+    bool dry = false;
+    uint32_t ray = 0;
+    Path P;
+    Trav R;
+    R.state = kIdle;
+    bool need = true, cont = false;
+    while (true) {
+        set_prio<kPrioInit>();
+        bool start = false;
+        while (!dry) {
+            const uint64_t m = __ballot(need);
+            if (m == 0) break;
+            if (b_pos >= b_cnt) {  // the batch is used up: the next one
+                const uint32_t leader = static_cast<uint32_t>(__ffsll(static_cast<long long>(m)) - 1);
+                uint32_t v = 0;
+                if (lane == leader) v = atomicAdd(Q.queue, 1u);
+                const uint32_t j = __builtin_amdgcn_readlane(v, leader);
+                if (j >= Q.batches) {
+                    dry = true;
+                    break;
+                }
+                b_base = j * 64u;
+                b_pos = 0;
+                b_cnt = min(64u, Q.n - b_base);
+            }
+            const uint32_t take = min(static_cast<uint32_t>(__popcll(m)), b_cnt - b_pos);
+            const uint32_t r = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32),
+                                                         __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
+            if (need && r < take) {
+                ray = b_base + b_pos + r;
+                need = false;
+                start = true;
+            }
+            b_pos += take;
+        }
+        if (dry) need = false;
+        if (start && !load_path(Q, ray, P)) {  // outside the contract: a miss, never traced
+            start = false;
+            R.found = false;
+            R.ref = 0;
+            R.tmax = 0;
+            R.state = kDone;
+        }
+        // render_kernel's traversal set-up, for new paths and scattered rays alike
+        if (start || cont) {
+            trav_init(P.o, P.d, W.f32_ok != 0, R);
+            const bool tok = kPair && pw && !(R.neg & kZeroDir);
+            st.base[-static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel | (tok ? kTokAlone : 0u));
+            st.base[-2 * static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel | (tok ? kTokAlone : 0u));
+            if (tok) R.cur = kTokAlone;
+            if (kInvLds) {
+                uint32_t t = threadIdx.x;
+                asm volatile("" : "+v"(t));
+                LdsDouble* const inv_l = (LdsDouble*)static_cast<uintptr_t>(W.lds_inv64 + t * 8);
+                inv_l[0] = 1 / P.d[0];
+                inv_l[kBlock] = 1 / P.d[1];
+                inv_l[2 * kBlock] = 1 / P.d[2];
+            }
+        }
+        cont = false;
+        // render_kernel's traversal rounds
+        while (true) {
+            set_prio<kPrioWalk>();
+            if (kPair && pw) {
+                if (__ballot(R.state == kWalk && (R.neg & kZeroDir)) != 0) {
+                    if (R.state == kWalk && (R.neg & kZeroDir))
+                        walk<SE, false, true, kTopTreelet && !LSCENE, LSCENE, GSTACK, false>(S, st, P.o, P.d, tmin, tmin32, R, ctr);
+                }
+                if (R.state == kWalk && !(R.neg & kZeroDir))
+                    walk_pairs<SE, false, kTopTreelet && !LSCENE, kInvLds>(S, st, P.o, P.d, tmin, tmin32, R, ctr);
+            } else if (!W.exact_slab && __ballot(R.state == kWalk && (R.neg & kZeroDir)) == 0) {
+                if (R.state == kWalk)
+                    walk<SE, false, false, kTopTreelet && !LSCENE, LSCENE, GSTACK, true, kInvLds>(S, st, P.o, P.d, tmin, tmin32, R, ctr);
+            } else {
+                if (R.state == kWalk) walk<SE, false, true, kTopTreelet && !LSCENE, LSCENE, GSTACK, false>(S, st, P.o, P.d, tmin, tmin32, R, ctr);
+            }
+            set_prio<kPrioLeaf>();
+            if (R.state == kLeaf)
+                leaf_step<SE, false, kTopTreelet && !LSCENE, LSCENE>(S, st, P.o, P.d, tmin, tmin32, kSphOnly || W.sphere_only != 0,
+                                                                     W.spheres_f32 != 0, !kSphOnly && W.quads_f32 != 0,
+                                                                     !kSphOnly && W.quads_flat != 0, R, ctr);
+            const uint64_t pending = __ballot(R.state == kWalk);
+            const int nfin = __popcll(__ballot(R.state == kDone));
+            if (pending == 0 || nfin >= kShadeBatch) break;
+        }
+        if (__ballot(R.state == kDone) == 0) break;  // every lane idle: the queue is dry
+        set_prio<kPrioShade>();
+        if (R.state == kDone) {
+            double acc[3] = {0, 0, 0};
+            bool ended = shade<LSCENE, kSphOnly>(S, CL, P, R.found, R.ref, R.tmax, acc);
+            // a scattered ray with no bounce left returns RGB::zero() (camera.h:211-213)
+            if (!ended && P.depth == 0) ended = true;
+            if (!ended) {
+                cont = true;
+            } else {
+                double* dst = Q.rgb + 3 * static_cast<size_t>(ray);
+                dst[0] = acc[0];
+                dst[1] = acc[1];
+                dst[2] = acc[2];
+                R.state = kIdle;
+                need = true;
+            }
+        }
+    }
+}
+
+// crt_camera_rays_async: start_path as a kernel of its own, one thread per record. Record
+// j * ns + (s - s0) holds owned pixel j's (owned rows in order, packed) sample s: the ray and the
+// LCG state after its draws.
+__global__ __launch_bounds__(256) void camera_rays_kernel(CamView C, Work W, uint32_t n, uint32_t s0, uint32_t ns,
+                                                          double* __restrict__ rays, uint32_t* __restrict__ states) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t j = i / ns, s = s0 + i % ns;
+    const uint32_t col = j % C.w, row = owned_row(W, j / C.w);
+    Path P;
+    start_path(C, row, col, sample_seed(C.base_seed, row * C.w + col, s), P);
+    double* dst = rays + 6 * static_cast<size_t>(i);
+    dst[0] = P.o[0]; dst[1] = P.o[1]; dst[2] = P.o[2];
+    dst[3] = P.d[0]; dst[4] = P.d[1]; dst[5] = P.d[2];
+    states[i] = P.rng;
+}
+
 // crt_pixel_variance_async: thread i = owned row i / w, column i % w. n = samples_done, or the
 // pixel's block word (adaptive_update_kernel's block numbering) without the stopped bit;
 // noise_stage1_kernel's expressions for m and the variance of the mean, without its sqrt.
@@ -3968,9 +4214,13 @@ static int launch_plain(const crt_scene* s, int device, const dev::Query& Q, boo
 // of the node array and the stack, else the stack in HBM too. Four waves per SIMD throughout: the
 // five-wave and flat-parallelogram-only instances of the render kernel have no query twin (a scene
 // of axis-aligned parallelograms runs its flat-box filter in the general instance).
+// query_layout fills W's LDS layout for the class it returns and *lds with the bytes laid out so far
+// (the launchers add what their instance keeps behind that: `extra` bytes besides the rays' 1 / d,
+// which the treelet leaves free); crt_trace_async and crt_radiance_async share it.
+enum QueryClass { kQueryLdsScene, kQueryLdsStack, kQueryHbmStack };
+
 template <typename SE>
-static int dispatch_trace(const crt_scene* s, int device, dev::Work W, const dev::Query& Q, bool any,
-                          hipMemPool_t pool, hipStream_t st) {
+static QueryClass query_layout(const crt_scene* s, dev::Work& W, size_t extra, size_t* lds) {
     const size_t stack_bytes = align16(static_cast<size_t>(s->depth + 1) * dev::kBlock * sizeof(SE));
     W.bytes_nodes = static_cast<uint32_t>(align16(s->num_dnodes * sizeof(DevNodeF)));
     W.bytes_refs = W.spheres_f32 ? 0u : static_cast<uint32_t>(align16(s->num_prims * 4));
@@ -3995,13 +4245,8 @@ static int dispatch_trace(const crt_scene* s, int device, dev::Work W, const dev
         const uint32_t sph64 = static_cast<uint32_t>(s->num_spheres * sizeof(DevSphere));
         if (W.spheres_f32 && stack_at(scene_bytes + sph64) + stack_bytes <= kLdsSceneBudget) W.bytes_sph64 = sph64;
         W.lds_stack = stack_at(scene_bytes + W.bytes_sph64);
-        const size_t lds = W.lds_stack + stack_bytes;
-        // Scenes this small are traced faster by the plain loop (rays of a few node tests each: the
-        // persistent grid's per-ray costs dominate; DESIGN section 6d has the figures), so that is
-        // their route; CRT_TRACE_FAST=1 takes the LDS-scene instances (tests, tools/ray_query_rate.py)
-        if (std::getenv("CRT_TRACE_FAST") == nullptr) return launch_plain(s, device, Q, any, pool, st);
-        if (W.sphere_only) return launch_trace<SE, false, true, 0>(s, device, W, lds, Q, any, pool, st);
-        return launch_trace<SE, false, true, 1>(s, device, W, lds, Q, any, pool, st);
+        *lds = W.lds_stack + stack_bytes;
+        return kQueryLdsScene;
     }
     const size_t per_block = 160 * 1024 * dev::kBlock / (256 * CRT_WAVES_PER_EU);
     const bool no_top = std::getenv("CRT_NO_LDS_TOP") != nullptr;
@@ -4010,18 +4255,39 @@ static int dispatch_trace(const crt_scene* s, int device, dev::Work W, const dev
         return no_top ? 0u : static_cast<uint32_t>(std::min(all_nodes, room / (2 * sizeof(DevNodeF)) * (2 * sizeof(DevNodeF))));
     };
     if (stack_bytes <= kLdsStackBudget && std::getenv("CRT_FORCE_GSTACK") == nullptr) {
-        const size_t taken = stack_bytes + 3 * level + kInvBytes;
+        const size_t taken = stack_bytes + 3 * level + kInvBytes + extra;
         const size_t room = per_block > taken ? per_block - taken : 0;
         W.ntop = top_bytes(room);
         W.lds_nodes = 0;
         W.lds_stack = stack_at(align16(W.ntop));
-        if (W.sphere_only) return launch_trace<SE, false, false, 0>(s, device, W, W.lds_stack + stack_bytes, Q, any, pool, st);
-        return launch_trace<SE, false, false, 1>(s, device, W, W.lds_stack + stack_bytes, Q, any, pool, st);
+        *lds = W.lds_stack + stack_bytes;
+        return kQueryLdsStack;
     }
-    W.ntop = top_bytes(per_block);
+    W.ntop = top_bytes(per_block - extra);
     W.lds_nodes = 0;
-    if (W.sphere_only) return launch_trace<SE, true, false, 0>(s, device, W, W.ntop, Q, any, pool, st);
-    return launch_trace<SE, true, false, 1>(s, device, W, W.ntop, Q, any, pool, st);
+    *lds = W.ntop;
+    return kQueryHbmStack;
+}
+
+template <typename SE>
+static int dispatch_trace(const crt_scene* s, int device, dev::Work W, const dev::Query& Q, bool any,
+                          hipMemPool_t pool, hipStream_t st) {
+    size_t lds = 0;
+    switch (query_layout<SE>(s, W, 0, &lds)) {
+    case kQueryLdsScene:
+        // Scenes this small are traced faster by the plain loop (rays of a few node tests each: the
+        // persistent grid's per-ray costs dominate; DESIGN section 6d has the figures), so that is
+        // their route; CRT_TRACE_FAST=1 takes the LDS-scene instances (tests, tools/ray_query_rate.py)
+        if (std::getenv("CRT_TRACE_FAST") == nullptr) return launch_plain(s, device, Q, any, pool, st);
+        if (W.sphere_only) return launch_trace<SE, false, true, 0>(s, device, W, lds, Q, any, pool, st);
+        return launch_trace<SE, false, true, 1>(s, device, W, lds, Q, any, pool, st);
+    case kQueryLdsStack:
+        if (W.sphere_only) return launch_trace<SE, false, false, 0>(s, device, W, lds, Q, any, pool, st);
+        return launch_trace<SE, false, false, 1>(s, device, W, lds, Q, any, pool, st);
+    default:
+        if (W.sphere_only) return launch_trace<SE, true, false, 0>(s, device, W, lds, Q, any, pool, st);
+        return launch_trace<SE, true, false, 1>(s, device, W, lds, Q, any, pool, st);
+    }
 }
 
 // CRT_TRACE_PLAIN: plain_query_kernel over the batch in launches of at most kPlainRays rays that
@@ -4129,6 +4395,182 @@ int device_trace_host(crt_scene* s, int device, const double* rays, size_t n, co
     (void)hipFree(d_out);
     if (rc) return rc;
     if (e != hipSuccess) return fail(CRT_E_HIP, std::string("crt_trace: ") + hipGetErrorString(e));
+    return CRT_OK;
+}
+
+// ---- radiance queries (crt_radiance_async) -----------------------------------------------------
+// One radiance_kernel launch: launch_trace's grid and scratch, with the camera copy behind the rest
+// of the LDS layout (launch_render's place for it).
+template <typename SE, bool GSTACK, bool LSCENE, int PM>
+static int launch_radiance(const crt_scene* s, int device, dev::Work W, size_t lds, const dev::CamView& C,
+                           dev::Radiance Q, hipMemPool_t pool, hipStream_t stream) {
+    W.lds_cam = static_cast<uint32_t>(align16(lds));
+    lds = W.lds_cam + align16(sizeof(dev::CamView));
+    if (!LSCENE && !GSTACK) {  // the rays' f64 1 / d (radiance_kernel: kInvLds)
+        W.lds_inv64 = static_cast<uint32_t>(align16(lds));
+        lds = W.lds_inv64 + kInvBytes;
+    }
+    const void* kfn = reinterpret_cast<const void*>(dev::radiance_kernel<SE, GSTACK, LSCENE, PM>);
+    int cus = 0, per_cu = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, dev::kBlock, lds));
+    uint64_t resident = static_cast<uint64_t>(std::max(1, cus)) * std::max(1, per_cu);
+    if (const char* e = std::getenv("CRT_GRID_BLOCKS"))
+        resident = std::max<uint64_t>(1, std::min<uint64_t>(resident, static_cast<uint64_t>(std::max(1, std::atoi(e)))));
+    constexpr uint32_t kWavesPerBlock = dev::kBlock / 64;
+    const uint32_t blocks = static_cast<uint32_t>(
+        std::max<uint64_t>(1, std::min<uint64_t>(resident, (Q.batches + kWavesPerBlock - 1) / kWavesPerBlock)));
+    SE* gstack = nullptr;
+    if (GSTACK)  // levels 0..depth, two guard levels and the level below them (render_kernel's layout)
+        HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&gstack),
+                                       static_cast<size_t>(s->depth + 4) * blocks * dev::kBlock * sizeof(SE), pool, stream));
+    uint32_t* queue = nullptr;
+    HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&queue), 256, pool, stream));
+    HIP_TRY(hipMemsetAsync(queue, 0, sizeof(uint32_t), stream));
+    Q.queue = queue;
+    hipLaunchKernelGGL((dev::radiance_kernel<SE, GSTACK, LSCENE, PM>), dim3(blocks), dim3(dev::kBlock), lds, stream,
+                       view_of(s->dev[device]), C, W, Q, gstack);
+    const hipError_t e = hipGetLastError();
+    (void)hipFreeAsync(queue, stream);
+    if (gstack) (void)hipFreeAsync(gstack, stream);
+    if (e != hipSuccess) return fail(CRT_E_HIP, std::string("radiance_kernel launch: ") + hipGetErrorString(e));
+    return CRT_OK;
+}
+
+// CRT_RADIANCE_PLAIN: plain_radiance_kernel in launches of at most 2^20 paths that share one set of
+// stacks (launch_plain's scheme)
+static int launch_plain_radiance(const crt_scene* s, int device, const dev::CamView& C, const dev::Radiance& Q,
+                                 hipMemPool_t pool, hipStream_t st) {
+    constexpr uint32_t kPlainPaths = 1u << 20;
+    const uint32_t per = std::min<uint32_t>(Q.n, kPlainPaths);
+    const uint32_t max_blocks = (per + dev::kBlock - 1) / dev::kBlock;
+    uint32_t* d_stack = nullptr;  // trace()'s stacks, [level][thread]
+    HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&d_stack),
+                                   static_cast<size_t>(s->depth + 1) * max_blocks * dev::kBlock * 4, pool, st));
+    const dev::SceneView S = view_of(s->dev[device]);
+    hipError_t e = hipSuccess;
+    for (uint64_t first = 0; first < Q.n && e == hipSuccess; first += kPlainPaths) {
+        hipLaunchKernelGGL(dev::plain_radiance_kernel, dim3(max_blocks), dim3(dev::kBlock), 0, st, S, C, Q,
+                           static_cast<uint32_t>(first), d_stack);
+        e = hipGetLastError();
+    }
+    (void)hipFreeAsync(d_stack, st);
+    if (e != hipSuccess) return fail(CRT_E_HIP, std::string("plain_radiance_kernel launch: ") + hipGetErrorString(e));
+    return CRT_OK;
+}
+
+// dispatch_trace's classes; every class takes the fast route (a path is many segments per queue
+// visit, unlike a single ray: DESIGN section 6e)
+template <typename SE>
+static int dispatch_radiance(const crt_scene* s, int device, dev::Work W, const dev::CamView& C,
+                             const dev::Radiance& Q, hipMemPool_t pool, hipStream_t st) {
+    size_t lds = 0;
+    switch (query_layout<SE>(s, W, align16(sizeof(dev::CamView)), &lds)) {
+    case kQueryLdsScene:
+        if (W.sphere_only) return launch_radiance<SE, false, true, 0>(s, device, W, lds, C, Q, pool, st);
+        return launch_radiance<SE, false, true, 1>(s, device, W, lds, C, Q, pool, st);
+    case kQueryLdsStack:
+        if (W.sphere_only) return launch_radiance<SE, false, false, 0>(s, device, W, lds, C, Q, pool, st);
+        return launch_radiance<SE, false, false, 1>(s, device, W, lds, C, Q, pool, st);
+    default:
+        if (W.sphere_only) return launch_radiance<SE, true, false, 0>(s, device, W, lds, C, Q, pool, st);
+        return launch_radiance<SE, true, false, 1>(s, device, W, lds, C, Q, pool, st);
+    }
+}
+
+int device_radiance(const crt_scene* s, int device, const double* d_rays, size_t n, const uint32_t* d_states,
+                    const crt_radiance_params* prm, double* d_rgb, void* stream) {
+    int rc = check_device(device);
+    if (rc) return rc;
+    if (!s->dev[device].valid)
+        return fail(CRT_E_NOT_UPLOADED, "scene not uploaded to device " + std::to_string(device));
+    if (n == 0) return CRT_OK;
+    DeviceGuard g(device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (prm->max_depth == 0) {  // ray_color returns RGB::zero() before any query (camera.h:211-213)
+        HIP_TRY(hipMemsetAsync(d_rgb, 0, n * 3 * sizeof(double), st));
+        return CRT_OK;
+    }
+    dev::CamView C{};
+    for (int k = 0; k < 3; ++k) C.bg[k] = prm->background[k];
+    C.t_min = prm->t_min;
+    C.max_depth = prm->max_depth;
+    C.base_seed = prm->base_seed;
+    dev::Radiance Q{};
+    Q.rays = d_rays;
+    Q.states = d_states;
+    Q.rgb = d_rgb;
+    Q.n = static_cast<uint32_t>(n);
+    Q.batches = static_cast<uint32_t>((n + 63) / 64);
+    Q.max_depth = prm->max_depth;
+    Q.base_seed = prm->base_seed;
+    hipMemPool_t pool = nullptr;
+    rc = pass_pool(device, &pool);
+    if (rc) return rc;
+    if (prm->flags & CRT_RADIANCE_PLAIN) return launch_plain_radiance(s, device, C, Q, pool, st);
+    // device_trace's scene classes and interval rules; 0 <= t_min <= 2^100 here (crt_radiance_async)
+    const DeviceCopy& c = s->dev[device];
+    dev::Work W{};
+    W.f32_ok = c.f32_ok ? 1u : 0u;
+    W.tmin32 = static_cast<float>(prm->t_min);
+    W.sphere_only = (s->num_quads == 0 && s->num_spheres != 0) ? 1u : 0u;
+    W.spheres_f32 = (W.sphere_only && c.spheres_f32_ok) ? 1u : 0u;
+    W.quads_f32 = (s->num_spheres == 0 && s->num_quads != 0 && c.quads_f32_ok) ? 1u : 0u;
+    W.quads_flat = (W.quads_f32 && c.quads_flat_ok && W.f32_ok) ? 1u : 0u;
+    W.exact_slab = (s->exact_slab || std::getenv("CRT_EXACT_SLAB") != nullptr) ? 1u : 0u;
+    W.pair_walk = (CRT_PAIR_WALK && !W.exact_slab && std::getenv("CRT_NO_PAIR_WALK") == nullptr) ? 1u : 0u;
+    if ((s->num_dnodes << kNodeFShift) <= 65536) return dispatch_radiance<uint16_t>(s, device, W, C, Q, pool, st);
+    return dispatch_radiance<uint32_t>(s, device, W, C, Q, pool, st);
+}
+
+// crt_radiance: device_radiance for host arrays, blocking: one upload of the rays (and states), one
+// query, one copy back, on a stream of its own
+int device_radiance_host(crt_scene* s, int device, const double* rays, size_t n, const uint32_t* states,
+                         const crt_radiance_params* prm, double* rgb) {
+    int rc = device_upload(s, device);
+    if (rc) return rc;
+    DeviceGuard g(device);
+    double *d_rays = nullptr, *d_rgb = nullptr;
+    uint32_t* d_states = nullptr;
+    hipStream_t st = nullptr;
+    hipError_t e = hipStreamCreate(&st);
+    if (e == hipSuccess) e = hipMalloc(&d_rays, n * 6 * sizeof(double));
+    if (e == hipSuccess && states) e = hipMalloc(&d_states, n * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&d_rgb, n * 3 * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rays, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && states) e = hipMemcpyAsync(d_states, states, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) rc = device_radiance(s, device, d_rays, n, d_states, prm, d_rgb, st);
+    if (e == hipSuccess && rc == CRT_OK) e = hipMemcpyAsync(rgb, d_rgb, n * 3 * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (st) {
+        const hipError_t se = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = se;
+        (void)hipStreamDestroy(st);
+    }
+    (void)hipFree(d_rays);
+    (void)hipFree(d_states);
+    (void)hipFree(d_rgb);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(CRT_E_HIP, std::string("crt_radiance: ") + hipGetErrorString(e));
+    return CRT_OK;
+}
+
+int device_camera_rays(int device, const crt_camera* cam, const crt_tiling* t, uint32_t first_sample,
+                       uint32_t num_samples, double* d_rays, uint32_t* d_states, void* stream) {
+    int rc = check_device(device);
+    if (rc) return rc;
+    dev::Work W;
+    rc = tiling_work(cam, t, W);
+    if (rc) return rc;
+    const uint64_t pixels = static_cast<uint64_t>(W.owned_rows) * cam->image_w;
+    if (pixels == 0 || num_samples == 0) return CRT_OK;
+    if (pixels > 0x7fffffffull / num_samples)
+        return fail(CRT_E_INVALID, "crt_camera_rays_async: more than 2^31-1 records");
+    const uint32_t n = static_cast<uint32_t>(pixels * num_samples);
+    DeviceGuard g(device);
+    hipLaunchKernelGGL(dev::camera_rays_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       cam_view(cam), W, n, first_sample, num_samples, d_rays, d_states);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(CRT_E_HIP, std::string("camera_rays_kernel launch: ") + hipGetErrorString(e));
     return CRT_OK;
 }
 

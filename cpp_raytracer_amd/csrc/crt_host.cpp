@@ -1523,6 +1523,52 @@ int crt_trace(crt_scene* s, int device, const double* rays, size_t n, const doub
     return device_trace_host(s, device, rays, n, tmax, params, hits, occluded);
 }
 
+// ---- radiance queries: check_trace's order (scene, params, flags, the interval, the count, the
+// output, the rays) ------------------------------------------------------------------------------
+static int check_radiance(const std::string& who, const void* s, const void* rays, const char* rays_name, size_t n,
+                          const crt_radiance_params* params, const void* rgb, const char* rgb_name) {
+    if (!s) return fail(CRT_E_INVALID, who + "scene is null");
+    if (!params) return fail(CRT_E_INVALID, who + "params is null");
+    if (params->flags & ~CRT_RADIANCE_PLAIN) return fail(CRT_E_INVALID, who + "unknown flags");
+    if (params->reserved != 0) return fail(CRT_E_INVALID, who + "params->reserved must be 0");
+    if (!(params->t_min >= 0 && params->t_min <= 0x1p100))
+        return fail(CRT_E_INVALID, who + "t_min must be finite, >= 0 and <= 2^100");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(params->background[k])) return fail(CRT_E_INVALID, who + "background must be finite");
+    if (n > 0x7fffffffu) return fail(CRT_E_INVALID, who + "more than 2^31-1 rays");
+    if (n && !rgb) return fail(CRT_E_INVALID, who + rgb_name + " is null (the output is required)");
+    if (n && !rays) return fail(CRT_E_INVALID, who + rays_name + " is null");
+    return CRT_OK;
+}
+
+int crt_radiance_async(const crt_scene* s, int device, const double* d_rays, size_t n, const uint32_t* d_states,
+                       const crt_radiance_params* params, double* d_rgb, void* stream) {
+    clear_error();
+    const int rc = check_radiance("crt_radiance_async: ", s, d_rays, "d_rays", n, params, d_rgb, "d_rgb");
+    if (rc) return rc;
+    if (n == 0) return CRT_OK;  // no work
+    return device_radiance(s, device, d_rays, n, d_states, params, d_rgb, stream);
+}
+
+int crt_radiance(crt_scene* s, int device, const double* rays, size_t n, const uint32_t* states,
+                 const crt_radiance_params* params, double* rgb) {
+    clear_error();
+    const int rc = check_radiance("crt_radiance: ", s, rays, "rays", n, params, rgb, "rgb");
+    if (rc) return rc;
+    if (n == 0) return CRT_OK;
+    return device_radiance_host(s, device, rays, n, states, params, rgb);
+}
+
+int crt_camera_rays_async(int device, const crt_camera* cam, const crt_tiling* tiling, uint32_t first_sample,
+                          uint32_t num_samples, double* d_rays, uint32_t* d_states, void* stream) {
+    clear_error();
+    if (!cam) return fail(CRT_E_INVALID, "crt_camera_rays_async: cam is null");
+    if (!d_rays || !d_states) return fail(CRT_E_INVALID, "crt_camera_rays_async: d_rays or d_states is null");
+    if (static_cast<uint64_t>(first_sample) + num_samples > 0xffffffffull)
+        return fail(CRT_E_INVALID, "crt_camera_rays_async: first_sample + num_samples exceeds 2^32-1");
+    return device_camera_rays(device, cam, tiling, first_sample, num_samples, d_rays, d_states, stream);
+}
+
 int crt_closest_hits(crt_scene* s, int device, const double* rays, size_t n, double t_min,
                      double t_max, crt_hit* out) {
     clear_error();

@@ -412,6 +412,14 @@ int device_trace(const crt_scene* s, int device, const double* d_rays, size_t n,
 // crt_trace: the same query for host arrays, blocking (uploads the scene if needed)
 int device_trace_host(crt_scene* s, int device, const double* rays, size_t n, const double* tmax,
                       const crt_trace_params* prm, crt_hit* hits, uint32_t* occluded);
+// radiance queries on device buffers (crt_radiance_async, which checks the arguments), the same for
+// host arrays, blocking (uploads the scene if needed), and the camera's own rays and states
+int device_radiance(const crt_scene* s, int device, const double* d_rays, size_t n, const uint32_t* d_states,
+                    const crt_radiance_params* prm, double* d_rgb, void* stream);
+int device_radiance_host(crt_scene* s, int device, const double* rays, size_t n, const uint32_t* states,
+                         const crt_radiance_params* prm, double* rgb);
+int device_camera_rays(int device, const crt_camera* cam, const crt_tiling* t, uint32_t first_sample,
+                       uint32_t num_samples, double* d_rays, uint32_t* d_states, void* stream);
 // denoising: first-hit features and the per-pixel variance (crt_device.hip), the filter
 // (crt_denoise.hip); the callers check the arguments
 int device_render_features(const crt_scene* s, int device, const crt_camera* cam, const crt_tiling* t,

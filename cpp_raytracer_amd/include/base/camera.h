@@ -392,6 +392,31 @@ public:
     // camera.h:301-303: a Scene renders through BVH(world)
     Image render(const Scene& world) { return render(BVH(world)); }
 
+    // Extension (not in the reference): ray_color (camera.h:205-258) for the caller's own rays, one
+    // path a ray with this camera's max_depth and background (crt_radiance: one upload, one launch,
+    // one copy back). Element i is what the sample starting on rays[i] with the LCG state
+    // states[i] adds to a pixel's sum in render(). An empty `states` seeds path i like sample 0 of
+    // pixel i of a render (crt_sample_seed with the next seed of the SeedSeqGenerator). A ray with
+    // a non-finite component or an all-zero direction sees the background.
+    std::vector<RGB> ray_colors(const std::vector<Ray3D>& rays, const std::vector<uint32_t>& states, const BVH& world) {
+        if (!states.empty() && states.size() != rays.size()) crt_api::die("Camera::ray_colors: one state a ray, or none");
+        init();
+        crt_radiance_params p{};
+        p.max_depth = resolved.max_depth;
+        p.base_seed = states.empty() ? SeedSeqGenerator::get_instance().next_seed() : 0u;
+        for (int k = 0; k < 3; ++k) p.background[k] = resolved.background[k];
+        p.t_min = resolved.t_min;
+        const std::vector<double> r = BVH::crt_rays(rays);
+        std::vector<double> rgb(rays.size() * 3);
+        if (crt_radiance(world.gpu_scene().get(), 0, r.data(), rays.size(), states.empty() ? nullptr : states.data(), &p,
+                         rgb.data()))
+            crt_api::die("crt_radiance");
+        std::vector<RGB> out;
+        out.reserve(rays.size());
+        for (size_t i = 0; i < rays.size(); ++i) out.push_back(RGB::from_mag(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]));
+        return out;
+    }
+
     Camera& set_camera_center(const Point3D& p) { camera.origin = p; return *this; }
     Camera& set_camera_direction(const Vec3D& d) { camera.dir = d; return *this; }
     Camera& set_camera_direction_towards(const Point3D& p) {

@@ -568,6 +568,64 @@ int crt_trace_async(const crt_scene* scene, int device, const double* d_rays, si
 int crt_trace(crt_scene* scene, int device, const double* rays, size_t n, const double* tmax,
               const crt_trace_params* params, crt_hit* hits, uint32_t* occluded);
 
+/* Radiance queries on device buffers: ray_color (camera.h:205-258) for the caller's own rays, through
+ * the render kernel's traversal and its shading, one path a ray. */
+#define CRT_RADIANCE_PLAIN 1u /* one thread a path over trace(): the cross-check and the A/B */
+typedef struct crt_radiance_params {
+    uint32_t max_depth;       /* ray_color's depth (camera.h:207-213) */
+    uint32_t base_seed;       /* used only when d_states == NULL */
+    double   background[3];   /* finite */
+    double   t_min;           /* finite, >= 0, <= 2^100; the camera's is 1e-5 */
+    uint32_t flags, reserved; /* unknown flag bits or reserved != 0: CRT_E_INVALID */
+} crt_radiance_params;        /* 48 bytes */
+
+/* d_rays: DEVICE memory on `device`, n x {ox, oy, oz, dx, dy, dz}: ray i is path i's first segment.
+ * d_states: DEVICE, n words, or NULL. Path i's LCG state before the first draw of ray_color is
+ *   d_states[i], or crt_sample_seed(base_seed, (uint32_t)i, 0) when d_states == NULL. Any 32-bit
+ *   state is legal (the LCG is mod 2^32).
+ * d_rgb: DEVICE, 3n doubles. d_rgb[3i .. 3i + 2] is exactly what that sample adds to a pixel's sum
+ *   in crt_render_async. With T the product of the attenuations in bounce order, starting from
+ *   (1, 1, 1), and E the background (the path ends at a miss) or the material's precomputed emission
+ *   (it ends at a DiffuseLight), channel k is 0.0 + T[k] * E[k]. Every other path writes +0 in every
+ *   channel: max_depth == 0 (nothing is traced then), an absorbed ray, a scattered ray with no bounce
+ *   left.
+ * Every segment is traced over (t_min, +inf). The caller's ray is classified by crt_trace_async's
+ * contract before anything is traced: one with a non-finite component or an all-zero direction is a
+ * miss, 0.0 + 1 * background[k] (+0 with max_depth == 0). Scattered rays are traced as a render
+ * traces them. Dielectric decisions count into the scene's parity guard (crt_render_guard) as a
+ * render's do.
+ * The scene must be resident on `device` (CRT_E_NOT_UPLOADED). Scratch comes from the pass pool; the
+ * call only enqueues on `stream`. n == 0 is CRT_OK with no work. CRT_E_INVALID, checked before any
+ * device work (the message names the rule): scene or params NULL, unknown flags, reserved != 0,
+ * t_min outside [0, 2^100] or NaN, a background component not finite, n > 2^31 - 1, d_rgb or d_rays
+ * NULL with n > 0. Both routes obey the render kernel's run-time switches and give
+ * the same bits. One device, one path per ray, one t_min and depth per call. */
+int crt_radiance_async(const crt_scene* scene, int device, const double* d_rays, size_t n,
+                       const uint32_t* d_states, const crt_radiance_params* params,
+                       double* d_rgb, void* stream);
+
+/* crt_radiance_async for HOST arrays, blocking: uploads the scene to `device` if it is not resident,
+ * then one upload of the rays (and states), one query on a stream of its own, one copy back. Same
+ * rules, same results (the C++ drop-in's Camera::ray_colors). */
+int crt_radiance(crt_scene* scene, int device, const double* rays, size_t n, const uint32_t* states,
+                 const crt_radiance_params* params, double* rgb);
+
+/* The camera's own rays: random_ray_through_pixel (camera.h:184-200, defocus disk :160-168) as a
+ * kernel, one thread a record. Pixels are the tiling's owned pixels, owned rows in order, packed (as
+ * under CRT_TILING_PACKED; tiling == NULL: the whole frame): pixel j = k * image_w + col for owned
+ * row k. For sample s in [first_sample, first_sample + num_samples), record
+ * r = j * num_samples + (s - first_sample) holds
+ *   d_rays[6r .. 6r + 5] (DEVICE): the ray whose draws start from the state
+ *     crt_sample_seed(cam->base_seed, row * image_w + col, s), row = the frame row of owned row k;
+ *   d_states[r] (DEVICE): the state after those draws,
+ * so crt_radiance_async on the two buffers with cam's max_depth, background and t_min gives the
+ * radiance of the samples crt_render_async sums for that pixel, bit for bit. Enqueues on `stream`.
+ * CRT_E_INVALID: cam, d_rays or d_states NULL, a bad tiling, first_sample + num_samples > 2^32 - 1,
+ * more than 2^31 - 1 records. No records (no owned rows, num_samples == 0) is CRT_OK. */
+int crt_camera_rays_async(int device, const crt_camera* cam, const crt_tiling* tiling,
+                          uint32_t first_sample, uint32_t num_samples,
+                          double* d_rays, uint32_t* d_states, void* stream);
+
 /* The integers Image::send_as_ppm prints (image.h:38-56; RGB::as_string rgb.h:99-115 with its
  * defaults: Reinhard tone map by luminance, gamma 2, static_cast<int>(255.999999 * v)) for the
  * n-pixel frame d_rgb (device memory on `device`, row-major RGB f64, e.g. crt_render_async's
