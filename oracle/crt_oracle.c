@@ -686,3 +686,66 @@ void oracle_ppm_values(const double* rgb, size_t n, int32_t* out) {
         }
     }
 }
+
+/* ---- caller-supplied rays --------------------------------------------------------------- */
+/* Camera::ray_color (camera.h:205-258) on rays that no camera made: record i is the first segment
+ * {o, d} = rays[6i .. 6i+5] of one path with LCG state states[i]. The camera carries only what
+ * ray_color reads of it, the background and the interval's lower end. */
+int oracle_radiance(const crt_material* mats, size_t nm, const crt_object* objs, size_t no,
+                    const double* rays, const uint32_t* states, size_t n, uint32_t max_depth,
+                    const double background[3], double t_min, int threads, double* rgb) {
+    (void)nm;
+    crt_camera cam;
+    memset(&cam, 0, sizeof cam);
+    for (int k = 0; k < 3; ++k) cam.background[k] = background[k];
+    cam.t_min = t_min;
+    World w;
+    world_make(mats, objs, no, 32, 12, &w);
+#ifdef _OPENMP
+    if (threads > 0) omp_set_num_threads(threads);
+#else
+    (void)threads;
+#endif
+#pragma omp parallel
+    {
+        size_t* stack = (size_t*)malloc(sizeof(size_t) * (w.depth + 2));
+#pragma omp for schedule(dynamic, 64)
+        for (long i = 0; i < (long)n; ++i) {
+            uint32_t rng = states[i];
+            ray_color(&w, &cam, ld(rays + 6 * i), ld(rays + 6 * i + 3), max_depth, &rng, rgb + 3 * i,
+                      NULL, stack);
+        }
+        free(stack);
+    }
+    world_free(&w);
+    return 0;
+}
+
+/* What a path's first event is, for choosing test inputs (tests/probe_sets.py): 0 for a miss, else
+ * the material kind of the first hit, + ORACLE_EVENT_BACK for a back face, + ORACLE_EVENT_TIR when
+ * Dielectric::scatter's ratio * sin_theta > 1 test (material.h:185-218) reflects there. */
+int oracle_first_events(const crt_material* mats, size_t nm, const crt_object* objs, size_t no,
+                        const double* rays, size_t n, double t_min, uint32_t* events) {
+    (void)nm;
+    World w;
+    world_make(mats, objs, no, 32, 12, &w);
+    size_t* stack = (size_t*)malloc(sizeof(size_t) * (w.depth + 2));
+    for (size_t i = 0; i < n; ++i) {
+        V3 o = ld(rays + 6 * i), d = ld(rays + 6 * i + 3);
+        Hit h;
+        events[i] = 0;
+        if (!bvh_hit(&w, o, d, t_min, INFINITY, &h, NULL, stack)) continue;
+        const crt_material* m = &mats[h.mat];
+        uint32_t e = m->kind;
+        if (!h.front) e += ORACLE_EVENT_BACK;
+        if (m->kind == CRT_DIELECTRIC) {
+            double ratio = h.front ? 1. / m->param : m->param / 1.;
+            double cos_t = fmin(dot(neg(unit(d)), h.n), 1.);
+            if (ratio * sqrt(1 - cos_t * cos_t) > 1) e += ORACLE_EVENT_TIR;
+        }
+        events[i] = e;
+    }
+    free(stack);
+    world_free(&w);
+    return 0;
+}

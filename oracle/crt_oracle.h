@@ -48,6 +48,22 @@ int oracle_hits(const crt_material* mats, size_t nm, const crt_object* objs, siz
 
 uint32_t oracle_sample_seed(uint32_t base, uint32_t pixel, uint32_t sample);
 
+/* Camera::ray_color (camera.h:205-258) on n caller-supplied rays {ox,oy,oz,dx,dy,dz}: record i is
+ * the first segment of one path of max_depth bounces over (t_min, +inf) with LCG state states[i];
+ * misses see `background`. rgb: 3n doubles. The world is BVH(world, 32, 12) as in oracle_render;
+ * records are split over `threads` OpenMP threads (<= 0: the runtime's default). */
+int oracle_radiance(const crt_material* mats, size_t nm, const crt_object* objs, size_t no,
+                    const double* rays, const uint32_t* states, size_t n, uint32_t max_depth,
+                    const double background[3], double t_min, int threads, double* rgb);
+
+/* The first event of each of n such paths: 0 = miss, else the first hit's material kind
+ * (+ ORACLE_EVENT_BACK: a back face; + ORACLE_EVENT_TIR: Dielectric::scatter reflects there because
+ * ratio * sin_theta > 1). For choosing test inputs only. */
+#define ORACLE_EVENT_BACK 8u
+#define ORACLE_EVENT_TIR 16u
+int oracle_first_events(const crt_material* mats, size_t nm, const crt_object* objs, size_t no,
+                        const double* rays, size_t n, double t_min, uint32_t* events);
+
 /* The integers Image::send_as_ppm prints (image.h:38-56) for n RGB pixels: RGB::as_string
  * (rgb.h:99-115) with its defaults — Reinhard by luminance (rgb.h:27-29), gamma 2 via
  * std::pow(x, 1/2) (rgb.h:10-13), static_cast<int>(255.999999 * .) — as the x86-64 g++ build

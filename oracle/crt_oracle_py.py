@@ -32,6 +32,8 @@ def lib():
         _lib.oracle_sample_seed.argtypes = [u32, u32, u32]
         _lib.oracle_sample_seed.restype = u32
         _lib.oracle_ppm_values.argtypes = [vp, sz, vp]
+        _lib.oracle_radiance.argtypes = [vp, sz, vp, sz, vp, vp, sz, u32, vp, C.c_double, C.c_int, vp]
+        _lib.oracle_first_events.argtypes = [vp, sz, vp, sz, vp, sz, C.c_double, vp]
     return _lib
 
 
@@ -86,6 +88,54 @@ def hits(scene, rays, t_min=1e-5, t_max=float("inf")):
     lib().oracle_hits(m.ctypes.data, len(m), o.ctypes.data, len(o), rays.ctypes.data, len(rays), t_min, t_max,
                       out.ctypes.data)
     return out
+
+
+EVENT_BACK, EVENT_TIR = 8, 16
+
+
+def _query_rays(rays):
+    """(n, 6) float64 rays, refused unless every one is inside the query contract of
+    csrc/crt_ray_class.h (six finite numbers, a direction that is not all zero): what a ray outside
+    it returns is the ABI's rule, not the reference's."""
+    rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+    bad = ~np.isfinite(rays).all(1) | (rays[:, 3:] == 0).all(1)
+    if bad.any():
+        raise ValueError(f"ray {int(np.flatnonzero(bad)[0])} is outside the query contract: {rays[bad][0].tolist()}")
+    return rays
+
+
+def radiance(scene, rays, states, max_depth, background, t_min=1e-5, threads=0):
+    """Camera::ray_color of caller-supplied rays (n, 6) with LCG states (n,) uint32 over
+    (t_min, inf): (n, 3) float64."""
+    m, o = _arrays(scene)
+    rays = _query_rays(rays)
+    states = np.ascontiguousarray(states, np.uint32).reshape(-1)
+    if len(states) != len(rays):
+        raise ValueError(f"{len(states)} states for {len(rays)} rays")
+    bg = np.array([float(v) for v in background], np.float64)
+    if bg.shape != (3,):
+        raise ValueError("background must have three components")
+    out = np.zeros((len(rays), 3))
+    rc = lib().oracle_radiance(m.ctypes.data, len(m), o.ctypes.data, len(o), rays.ctypes.data, states.ctypes.data,
+                               len(rays), int(max_depth), bg.ctypes.data, float(t_min), threads, out.ctypes.data)
+    if rc:
+        raise RuntimeError(f"oracle_radiance failed ({rc})")
+    return out
+
+
+def first_events(scene, rays, t_min=1e-5):
+    """Per ray 0 for a miss, else the first hit's material kind (+ EVENT_BACK on a back face,
+    + EVENT_TIR where a Dielectric reflects totally there): (n,) uint32."""
+    m, o = _arrays(scene)
+    rays = _query_rays(rays)
+    out = np.zeros(len(rays), np.uint32)
+    lib().oracle_first_events(m.ctypes.data, len(m), o.ctypes.data, len(o), rays.ctypes.data, len(rays), float(t_min),
+                              out.ctypes.data)
+    return out
+
+
+def sample_seed(base, pixel, sample):
+    return int(lib().oracle_sample_seed(base & 0xFFFFFFFF, pixel, sample))
 
 
 def ppm_values(frame):

@@ -18,6 +18,10 @@
  *                                        as render_linear, with the objects regrouped into nested
  *                                        Scenes (runs of <group> objects, pairs of those again)
  *   hits    <scene> <rays> <out>         BVH::hit_by closest hits          (bvh.h:585-715)
+ *   radiance <scene> <in> <depth> <out>  Camera::ray_color (camera.h:205-258) of caller-supplied rays:
+ *                                        <in> holds n rays of six doubles, then n uint32 LCG states;
+ *                                        state injected per record, the scene's background, the
+ *                                        reference's own t_min = 1e-5; n x 3 doubles
  *   time    <scene> <threads> [rows]     unmodified Camera::render timing  (CPU baseline)
  *   refsum  <scene> <seed>               1-thread unmodified render checksum (shim check)
  *   ppm     <frame.f64> <h> <w> <out.ppm>  Image::send_as_ppm of a raw row-major f64 RGB frame
@@ -340,6 +344,34 @@ int main(int argc, char** argv) {
             o[8] = h->hit_from_outside ? 1 : 0;
         }
         write_npy(argv[4], out, {n, 9});
+        return 0;
+    }
+    if (mode == "radiance") {
+        // <in>: n rays of six doubles, then n uint32 LCG states
+        if (argc < 6) return 2;
+        std::vector<char> raw;
+        {
+            std::ifstream g(argv[3], std::ios::binary);
+            raw.assign(std::istreambuf_iterator<char>(g), {});
+        }
+        const size_t rec = 6 * sizeof(double) + sizeof(uint32_t);
+        if (raw.empty() || raw.size() % rec) { std::fprintf(stderr, "radiance: bad input size\n"); return 2; }
+        const size_t n = raw.size() / rec;
+        std::vector<double> r(6 * n);
+        std::vector<uint32_t> st(n);
+        std::memcpy(r.data(), raw.data(), 6 * n * sizeof(double));
+        std::memcpy(st.data(), raw.data() + 6 * n * sizeof(double), n * sizeof(uint32_t));
+        const size_t depth = std::strtoul(argv[4], nullptr, 10);
+        Camera cam = make_camera(L.cs);
+        BVH bvh(L.world);
+        std::vector<double> out(n * 3, 0.0);
+        for (size_t i = 0; i < n; ++i) {
+            crt_oracle_set_state(st[i]);
+            Ray3D ray{Point3D{r[6 * i], r[6 * i + 1], r[6 * i + 2]}, Vec3D{r[6 * i + 3], r[6 * i + 4], r[6 * i + 5]}};
+            auto c = cam.ray_color(ray, depth, bvh);
+            out[3 * i] = c.r; out[3 * i + 1] = c.g; out[3 * i + 2] = c.b;
+        }
+        write_npy(argv[5], out, {n, 3});
         return 0;
     }
 #endif

@@ -8,6 +8,8 @@ the scenes as CRTS files with the library's named-scene builders, and asks the r
   * per-sample-seeded renders       -> render_<case>.npz  (per-pixel RGB, float64)
   * per-sample radiance             -> samples_<case>.npz
   * closest-hit records             -> hits_<scene>.npz
+  * ray_color of probe rays         -> radiance_<scene>.npz (rays, states, depths, background,
+                                       scene digest, rgb per depth)
 Fixtures hold inputs and expected outputs only. Usage: python tests/golden/gen_golden.py
 """
 from __future__ import annotations
@@ -190,6 +192,28 @@ def gen_linear(tmp: Path, meta: dict) -> None:
                                  else f"nested scenes (group {group})"}
 
 
+def gen_radiance(tmp: Path) -> None:
+    """The reference's Camera::ray_color on rays that no camera made (oracle/_ref radiance mode):
+    tests/probe_sets.py's fixture_records of each scene at depths 1, 3 and 50, with the scene's own
+    background and the reference's t_min = 1e-5."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    import probe_sets as ps
+    for name in ps.FIXTURE_SCENES:
+        d = ps.scene_data(crt, name)
+        p = tmp / f"{name}_radiance.crts"
+        d.save(p)
+        rays, states = ps.fixture_records(crt, name)
+        src, out = tmp / "q.bin", tmp / "q.npy"
+        src.write_bytes(rays.astype("<f8").tobytes() + states.astype("<u4").tobytes())
+        rgb = []
+        for depth in ps.FIXTURE_DEPTHS:
+            run("radiance", p, src, depth, out)
+            rgb.append(np.load(out))
+        np.savez_compressed(GOLD / f"radiance_{name}.npz", rays=rays, states=states,
+                            depths=np.array(ps.FIXTURE_DEPTHS, np.uint32), background=np.array(d.camera.background[:]),
+                            scene_digest=np.array(scene_digest(d)), rgb=np.stack(rgb))
+
+
 def main() -> None:
     subprocess.run(["make", "-C", str(ROOT / "oracle"), "ref"], check=True)
     meta = {"generator": "tests/golden/gen_golden.py", "reference": "DeltaPavonis/cpp_raytracer (oracle/_ref)",
@@ -252,6 +276,7 @@ def main() -> None:
         gen_linear(tmp, meta)
         gen_ppm(tmp)
         gen_bvh_ties(tmp)
+        gen_radiance(tmp)
     (GOLD / "golden.json").write_text(json.dumps(meta, indent=1, sort_keys=True))
     print("golden fixtures written to", GOLD)
 
@@ -263,9 +288,9 @@ if __name__ == "__main__":
         with tempfile.TemporaryDirectory() as td:
             gen_linear(Path(td), m)
         (GOLD / "golden.json").write_text(json.dumps(m, indent=1, sort_keys=True))
-    elif sys.argv[1:] in (["ppm"], ["ties"]):  # only the PPM-value / tie-BVH fixtures
+    elif sys.argv[1:] in (["ppm"], ["ties"], ["radiance"]):  # only the PPM-value / tie-BVH / radiance fixtures
         subprocess.run(["make", "-C", str(ROOT / "oracle"), "ref"], check=True)
         with tempfile.TemporaryDirectory() as td:
-            (gen_ppm if sys.argv[1] == "ppm" else gen_bvh_ties)(Path(td))
+            {"ppm": gen_ppm, "ties": gen_bvh_ties, "radiance": gen_radiance}[sys.argv[1]](Path(td))
     else:
         main()
