@@ -641,9 +641,15 @@ int oracle_bvh(const crt_material* mats, size_t nm, const crt_object* objs, size
 
 int oracle_hits(const crt_material* mats, size_t nm, const crt_object* objs, size_t no,
                 const double* rays, size_t n, double t_min, double t_max, crt_hit* out) {
+    return oracle_hits_bvh(mats, nm, objs, no, 32, 12, rays, n, t_min, t_max, out);
+}
+
+int oracle_hits_bvh(const crt_material* mats, size_t nm, const crt_object* objs, size_t no,
+                    uint32_t num_buckets, uint32_t max_prims, const double* rays, size_t n,
+                    double t_min, double t_max, crt_hit* out) {
     (void)nm;
     World w;
-    world_make(mats, objs, no, 32, 12, &w);
+    world_make(mats, objs, no, num_buckets, max_prims, &w);
     size_t* stack = (size_t*)malloc(sizeof(size_t) * (w.depth + 2));
     for (size_t i = 0; i < n; ++i) {
         V3 o = ld(rays + 6 * i), d = ld(rays + 6 * i + 3);
@@ -694,13 +700,21 @@ void oracle_ppm_values(const double* rgb, size_t n, int32_t* out) {
 int oracle_radiance(const crt_material* mats, size_t nm, const crt_object* objs, size_t no,
                     const double* rays, const uint32_t* states, size_t n, uint32_t max_depth,
                     const double background[3], double t_min, int threads, double* rgb) {
+    return oracle_radiance_bvh(mats, nm, objs, no, 32, 12, rays, states, n, max_depth, background, t_min,
+                               threads, rgb);
+}
+
+int oracle_radiance_bvh(const crt_material* mats, size_t nm, const crt_object* objs, size_t no,
+                        uint32_t num_buckets, uint32_t max_prims, const double* rays,
+                        const uint32_t* states, size_t n, uint32_t max_depth,
+                        const double background[3], double t_min, int threads, double* rgb) {
     (void)nm;
     crt_camera cam;
     memset(&cam, 0, sizeof cam);
     for (int k = 0; k < 3; ++k) cam.background[k] = background[k];
     cam.t_min = t_min;
     World w;
-    world_make(mats, objs, no, 32, 12, &w);
+    world_make(mats, objs, no, num_buckets, max_prims, &w);
 #ifdef _OPENMP
     if (threads > 0) omp_set_num_threads(threads);
 #else

@@ -45,6 +45,10 @@ int oracle_render(const crt_material* mats, size_t nm, const crt_object* objs, s
 /* BVH::hit_by for n rays {ox,oy,oz,dx,dy,dz}, interval (t_min, t_max). */
 int oracle_hits(const crt_material* mats, size_t nm, const crt_object* objs, size_t no,
                 const double* rays, size_t n, double t_min, double t_max, crt_hit* out);
+/* The same through BVH(world, num_buckets, max_prims) (bvh.h:756); oracle_hits is (32, 12). */
+int oracle_hits_bvh(const crt_material* mats, size_t nm, const crt_object* objs, size_t no,
+                    uint32_t num_buckets, uint32_t max_prims, const double* rays, size_t n,
+                    double t_min, double t_max, crt_hit* out);
 
 uint32_t oracle_sample_seed(uint32_t base, uint32_t pixel, uint32_t sample);
 
@@ -55,6 +59,11 @@ uint32_t oracle_sample_seed(uint32_t base, uint32_t pixel, uint32_t sample);
 int oracle_radiance(const crt_material* mats, size_t nm, const crt_object* objs, size_t no,
                     const double* rays, const uint32_t* states, size_t n, uint32_t max_depth,
                     const double background[3], double t_min, int threads, double* rgb);
+/* The same through BVH(world, num_buckets, max_prims); oracle_radiance is (32, 12). */
+int oracle_radiance_bvh(const crt_material* mats, size_t nm, const crt_object* objs, size_t no,
+                        uint32_t num_buckets, uint32_t max_prims, const double* rays,
+                        const uint32_t* states, size_t n, uint32_t max_depth,
+                        const double background[3], double t_min, int threads, double* rgb);
 
 /* The first event of each of n such paths: 0 = miss, else the first hit's material kind
  * (+ ORACLE_EVENT_BACK: a back face; + ORACLE_EVENT_TIR: Dielectric::scatter reflects there because

@@ -17,7 +17,11 @@
  *   render_nested <scene> <base> <out> <group> [r0 r1 c0 c1]
  *                                        as render_linear, with the objects regrouped into nested
  *                                        Scenes (runs of <group> objects, pairs of those again)
- *   hits    <scene> <rays> <out>         BVH::hit_by closest hits          (bvh.h:585-715)
+ *   hits    <scene> <rays> <out> [num_buckets max_prims]
+ *                                        BVH::hit_by closest hits          (bvh.h:585-715); with the
+ *                                        two numbers through BVH(world, num_buckets, max_prims)
+ *                                        (bvh.h:756), and the primitive is then the only one whose own
+ *                                        hit has that time, material and normal (-3: more than one)
  *   radiance <scene> <in> <depth> <out>  Camera::ray_color (camera.h:205-258) of caller-supplied rays:
  *                                        <in> holds n rays of six doubles, then n uint32 LCG states;
  *                                        state injected per record, the scene's background, the
@@ -319,10 +323,10 @@ int main(int argc, char** argv) {
         }
         size_t n = raw.size() / (6 * sizeof(double));
         const double* r = reinterpret_cast<const double*>(raw.data());
-        BVH bvh(L.world);
+        const bool strict = argc >= 7;
+        BVH bvh = strict ? BVH(L.world, std::strtoul(argv[5], nullptr, 10), std::strtoul(argv[6], nullptr, 10))
+                         : BVH(L.world);
         auto prims = L.world.get_primitive_components();
-        std::map<const Hittable*, uint32_t> idx;
-        for (size_t i = 0; i < prims.size(); ++i) idx[prims[i].get()] = static_cast<uint32_t>(i);
         // output per ray: t, point[3], normal[3], prim (as double), front (as double)
         std::vector<double> out(n * 9, 0.0);
         for (size_t i = 0; i < n; ++i) {
@@ -339,7 +343,10 @@ int main(int argc, char** argv) {
             o[7] = -2;
             for (size_t p = 0; p < prims.size(); ++p) {
                 auto hp = prims[p]->hit_by(ray, Interval(0.00001, std::numeric_limits<double>::infinity()));
-                if (hp && hp->hit_time == h->hit_time && hp->material == h->material) { o[7] = static_cast<double>(p); break; }
+                if (!(hp && hp->hit_time == h->hit_time && hp->material == h->material)) continue;
+                if (!strict) { o[7] = static_cast<double>(p); break; }
+                const Vec3D &a = hp->unit_surface_normal, &b = h->unit_surface_normal;
+                if (a.x == b.x && a.y == b.y && a.z == b.z) o[7] = o[7] == -2 ? static_cast<double>(p) : -3;
             }
             o[8] = h->hit_from_outside ? 1 : 0;
         }

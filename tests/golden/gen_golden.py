@@ -10,6 +10,8 @@ the scenes as CRTS files with the library's named-scene builders, and asks the r
   * closest-hit records             -> hits_<scene>.npz
   * ray_color of probe rays         -> radiance_<scene>.npz (rays, states, depths, background,
                                        scene digest, rgb per depth)
+  * closest-hit records of the edge-ray families (tests/edge_rays.py), through the default BVH
+    and BVH(world, 8, 1)            -> hits_edge_rays.npz
 Fixtures hold inputs and expected outputs only. Usage: python tests/golden/gen_golden.py
 """
 from __future__ import annotations
@@ -214,6 +216,37 @@ def gen_radiance(tmp: Path) -> None:
                             scene_digest=np.array(scene_digest(d)), rgb=np.stack(rgb))
 
 
+def gen_edge_rays(tmp: Path, meta: dict) -> None:
+    """The reference's BVH::hit_by over (1e-5, inf) (oracle/_ref hits mode) on tests/edge_rays.py's
+    families, in FAMILIES' order (`all` is a permutation of them), through both of its trees: the
+    driver hands the tree's two numbers to BVH's constructor (bvh.h:756). The same rays go through
+    the world's three parts (er.WORLDS: the scenes in which the leaf filters run). Per world and
+    tree: t, point and normal as float64, the primitive (unique by hit time, material and normal:
+    never -2 or -3) and hit_from_outside. The worlds' digests go to golden.json's worlds (scenes
+    holds the named scenes only)."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    import edge_rays as er
+    w = er.world(crt)
+    rays = np.concatenate([w.rays[k] for k in er.FAMILIES])
+    src, dst = tmp / "e.bin", tmp / "e.npy"
+    src.write_bytes(rays.astype("<f8").tobytes())
+    out = {"rays": rays, "families": np.array(er.FAMILIES)}
+    for part, d in w.data.items():
+        p = tmp / f"edge_rays_{part}.crts"
+        d.save(p)
+        out[part + "_scene_digest"] = np.array(scene_digest(d))
+        for tree, kw in er.TREES.items():
+            run("hits", p, src, dst, kw.get("num_buckets", 32), kw.get("max_prims_in_node", 12))
+            h = np.load(dst)
+            assert (h[:, 7] >= -1).all(), "a hit the driver could not give to one primitive"
+            out[f"{part}_{tree}_t_point_normal"] = h[:, :7]
+            out[f"{part}_{tree}_prim"] = h[:, 7].astype(np.int16)
+            out[f"{part}_{tree}_front"] = h[:, 8].astype(np.uint8)
+        meta.setdefault("worlds", {})["edge_rays_" + part] = {"seed": er.SEED, "objects": int(len(d.objects)),
+                                                              "materials": int(len(d.materials)), "sha256": scene_digest(d)}
+    np.savez_compressed(GOLD / "hits_edge_rays.npz", **out)
+
+
 def main() -> None:
     subprocess.run(["make", "-C", str(ROOT / "oracle"), "ref"], check=True)
     meta = {"generator": "tests/golden/gen_golden.py", "reference": "DeltaPavonis/cpp_raytracer (oracle/_ref)",
@@ -277,16 +310,17 @@ def main() -> None:
         gen_ppm(tmp)
         gen_bvh_ties(tmp)
         gen_radiance(tmp)
+        gen_edge_rays(tmp, meta)
     (GOLD / "golden.json").write_text(json.dumps(meta, indent=1, sort_keys=True))
     print("golden fixtures written to", GOLD)
 
 
 if __name__ == "__main__":
-    if sys.argv[1:] == ["linear"]:  # only the linear-world renders, merged into golden.json
+    if sys.argv[1:] in (["linear"], ["edge_rays"]):  # only the linear-world renders / the edge rays, merged into golden.json
         subprocess.run(["make", "-C", str(ROOT / "oracle"), "ref"], check=True)
         m = json.loads((GOLD / "golden.json").read_text())
         with tempfile.TemporaryDirectory() as td:
-            gen_linear(Path(td), m)
+            {"linear": gen_linear, "edge_rays": gen_edge_rays}[sys.argv[1]](Path(td), m)
         (GOLD / "golden.json").write_text(json.dumps(m, indent=1, sort_keys=True))
     elif sys.argv[1:] in (["ppm"], ["ties"], ["radiance"]):  # only the PPM-value / tie-BVH / radiance fixtures
         subprocess.run(["make", "-C", str(ROOT / "oracle"), "ref"], check=True)
