@@ -20,7 +20,8 @@ from ._capi import (CRT_BOX, CRT_DIELECTRIC, CRT_DIFFUSE_LIGHT, CRT_LAMBERTIAN, 
                     CRT_PARALLELOGRAM, CRT_SPHERE, HIT_DTYPE, MATERIAL_DTYPE, NODE_DTYPE,
                     OBJECT_DTYPE, CRT_BLOCK_STOPPED, FEATURE_DTYPE, BVHParams, Camera, CameraSettings, CrtError,
                     DenoiseParams, RenderStats, SceneInfo, Tiling, TraceParams, CRT_TRACE_ANY, CRT_TRACE_PLAIN,
-                    RadianceParams, CRT_RADIANCE_PLAIN, check, lib)
+                    RadianceParams, CRT_RADIANCE_PLAIN, ProbeParams, CRT_PROBE_SPHERE, CRT_PROBE_HEMISPHERE,
+                    CRT_SH_RADIANCE, CRT_SH_IRRADIANCE, check, lib)
 
 __all__ = [
     "SceneData", "GpuScene", "CameraSettings", "Camera", "Tiling", "RenderStats", "CrtError",
@@ -29,6 +30,7 @@ __all__ = [
     "DenoiseParams", "FEATURE_DTYPE", "denoise_params", "pixel_variance", "denoise",
     "TraceParams", "CRT_TRACE_ANY", "CRT_TRACE_PLAIN", "HIT_DTYPE",
     "RadianceParams", "CRT_RADIANCE_PLAIN",
+    "ProbeParams", "CRT_PROBE_SPHERE", "CRT_PROBE_HEMISPHERE", "CRT_SH_RADIANCE", "CRT_SH_IRRADIANCE", "sh_eval",
     "CRT_LAMBERTIAN", "CRT_METAL", "CRT_DIELECTRIC", "CRT_DIFFUSE_LIGHT",
     "CRT_SPHERE", "CRT_PARALLELOGRAM", "CRT_BOX",
 ]
@@ -114,6 +116,34 @@ def denoise(device: int, width: int, height: int, rgb_ptr: int, var_ptr: int, fe
                                   C.c_void_p(feat_ptr or None), C.byref(params) if params is not None else None,
                                   C.c_void_p(out_ptr or None), C.c_void_p(var_out_ptr or None), C.c_void_p(stream)),
           "crt_denoise_async")
+
+
+def sh_eval(coeff, index, dirs, irradiance: bool = False):
+    """Evaluates the spherical-harmonic coefficients of GpuScene.probes(mode="sphere") on torch tensors
+    of a GPU (crt_sh_eval_async): coeff (num_probes, 9, 3) float64, index (m,) int32 (the probe of
+    each query, its bits a uint32) and dirs (m, 3) float64 unit directions on coeff's device. Returns
+    an (m, 3) float64 tensor: the band-limited radiance from dirs[i], or with irradiance=True the
+    irradiance of a surface whose normal is dirs[i]. A query whose index is not a probe gives zeros.
+    Runs on coeff's device and its current stream and does not synchronise."""
+    import torch
+    if not (coeff.is_cuda and coeff.dtype == torch.float64 and coeff.dim() == 3 and tuple(coeff.shape[1:]) == (9, 3)):
+        raise CrtError("sh_eval: coeff must be a (num_probes, 9, 3) float64 tensor on a GPU")
+    m = index.shape[0] if index.dim() == 1 else -1
+    if not (index.is_cuda and index.device == coeff.device and index.dtype == torch.int32 and m >= 0):
+        raise CrtError("sh_eval: index must be an (m,) int32 tensor on coeff's device")
+    if not (dirs.is_cuda and dirs.device == coeff.device and dirs.dtype == torch.float64 and tuple(dirs.shape) == (m, 3)):
+        raise CrtError("sh_eval: dirs must be an (m, 3) float64 tensor on coeff's device")
+    coeff, index, dirs = coeff.contiguous(), index.contiguous(), dirs.contiguous()
+    device = coeff.device.index
+    with torch.cuda.device(device):
+        out = torch.empty((m, 3), dtype=torch.float64, device=coeff.device)
+        if m:
+            check(lib().crt_sh_eval_async(device, C.c_void_p(coeff.data_ptr() or None), coeff.shape[0],
+                                          C.c_void_p(index.data_ptr()), C.c_void_p(dirs.data_ptr()), m,
+                                          CRT_SH_IRRADIANCE if irradiance else CRT_SH_RADIANCE,
+                                          C.c_void_p(out.data_ptr()),
+                                          C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "crt_sh_eval_async")
+        return out
 
 
 def device_count() -> int:
@@ -548,6 +578,89 @@ class GpuScene:
                                     flags=CRT_RADIANCE_PLAIN if plain else 0,
                                     stream=torch.cuda.current_stream(device).cuda_stream)
             return out
+
+    @staticmethod
+    def _probe_params(samples, mode, max_depth, background, t_min, base_seed, batch_probes, flags) -> ProbeParams:
+        if isinstance(mode, str):
+            if mode not in ("sphere", "hemisphere"):
+                raise CrtError('probes: mode must be "sphere" or "hemisphere"')
+            mode = CRT_PROBE_HEMISPHERE if mode == "hemisphere" else CRT_PROBE_SPHERE
+        return ProbeParams(samples, max_depth, base_seed & 0xFFFFFFFF, mode, _capi.D3(*[float(v) for v in background]),
+                           t_min, batch_probes, flags)
+
+    def probes_async(self, device: int, points_ptr: int, normals_ptr: int, n: int, out_ptr: int, *, samples: int,
+                     mode=CRT_PROBE_SPHERE, max_depth: int, background, t_min: float = 1e-5, base_seed: int = 0,
+                     batch_probes: int = 0, flags: int = 0, stream: int = 0) -> None:
+        """Enqueue a probe bake on device buffers (crt_probes_async): n points of 3 doubles at
+        points_ptr, with CRT_PROBE_HEMISPHERE their unit normals at normals_ptr (0 with
+        CRT_PROBE_SPHERE). `samples` directions a probe are drawn on the device, path-traced as
+        radiance_async traces them and reduced in a fixed order: n x 9 x 3 doubles (SH coefficients of
+        bands 0..2 per channel) or n x 1 x 3 (irradiance) go to out_ptr. batch_probes sizes the
+        internal batches only; flags may hold CRT_RADIANCE_PLAIN: the same bits either way. The scene
+        must be uploaded to `device`."""
+        prm = self._probe_params(samples, mode, max_depth, background, t_min, base_seed, batch_probes, flags)
+        check(lib().crt_probes_async(self._h, device, C.c_void_p(points_ptr or None), C.c_void_p(normals_ptr or None), n,
+                                     C.byref(prm), C.c_void_p(out_ptr or None), C.c_void_p(stream)), "crt_probes_async")
+
+    @staticmethod
+    def _probe_inputs(who, points, normals, mode):
+        import torch
+        if mode not in ("sphere", "hemisphere"):
+            raise CrtError(f'{who}: mode must be "sphere" or "hemisphere"')
+        if not (points.is_cuda and points.dtype == torch.float64 and points.dim() == 2 and points.shape[1] == 3):
+            raise CrtError(f"{who}: points must be an (n, 3) float64 tensor on a GPU")
+        if (normals is not None) != (mode == "hemisphere"):
+            raise CrtError(f'{who}: normals are required with mode="hemisphere" and must be None with mode="sphere"')
+        if normals is not None:
+            if not (normals.is_cuda and normals.device == points.device and normals.dtype == torch.float64 and
+                    normals.shape == points.shape):
+                raise CrtError(f"{who}: normals must be an (n, 3) float64 tensor on the points' device")
+            normals = normals.contiguous()
+        return points.contiguous(), normals
+
+    def probes(self, points, normals=None, samples: int = 1024, mode: str = "sphere", max_depth: int = 50,
+               background=(0.7, 0.8, 1.0), t_min: float = 1e-5, base_seed: int = 0, batch_probes: int = 0,
+               plain: bool = False):
+        """Probe bake on torch tensors of a GPU: points (n, 3) float64; with mode="hemisphere", normals
+        (n, 3) float64 unit vectors on the points' device (None with mode="sphere"). Runs on the
+        points' device and its current stream and does not synchronise; the scene is uploaded there
+        first if it is not yet (that blocks). Returns an (n, 9, 3) float64 tensor of SH coefficients
+        (sphere; sh_eval evaluates them) or (n, 1, 3) of irradiance (hemisphere)."""
+        import torch
+        points, normals = self._probe_inputs("probes", points, normals, mode)
+        n, device = points.shape[0], points.device.index
+        with torch.cuda.device(device):
+            out = torch.empty((n, 9 if mode == "sphere" else 1, 3), dtype=torch.float64, device=points.device)
+            if n:
+                self.upload(device)
+                self.probes_async(device, points.data_ptr(), normals.data_ptr() if normals is not None else 0, n,
+                                  out.data_ptr(), samples=samples, mode=mode, max_depth=max_depth, background=background,
+                                  t_min=t_min, base_seed=base_seed, batch_probes=batch_probes,
+                                  flags=CRT_RADIANCE_PLAIN if plain else 0,
+                                  stream=torch.cuda.current_stream(device).cuda_stream)
+            return out
+
+    def probe_rays(self, points, normals=None, samples: int = 1024, mode: str = "sphere", base_seed: int = 0):
+        """The rays and LCG states a bake of these probes traces (crt_probe_rays_async), on the points'
+        device and its current stream, without synchronising: (rays (n * samples, 6) float64, states
+        (n * samples,) int32), record probe * samples + sample. radiance(rays, states, ...) is the
+        per-sample radiance that probes(...) reduces."""
+        import torch
+        points, normals = self._probe_inputs("probe_rays", points, normals, mode)
+        n, device = points.shape[0], points.device.index
+        prm = self._probe_params(samples, mode, 1, (0.0, 0.0, 0.0), 1e-5, base_seed, 0, 0)
+        with torch.cuda.device(device):
+            records = n * samples if n else 0
+            rays = torch.empty((records, 6), dtype=torch.float64, device=points.device)
+            states = torch.empty((records,), dtype=torch.int32, device=points.device)
+            if n:
+                check(lib().crt_probe_rays_async(device, C.c_void_p(points.data_ptr()),
+                                                 C.c_void_p(normals.data_ptr() if normals is not None else None), n,
+                                                 C.byref(prm), C.c_void_p(rays.data_ptr() or None),
+                                                 C.c_void_p(states.data_ptr() or None),
+                                                 C.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+                      "crt_probe_rays_async")
+            return rays, states
 
     def camera_rays(self, cam: Camera, first_sample: int = 0, num_samples: Optional[int] = None,
                     tiling: Optional[Tiling] = None, device: int = 0):

@@ -117,6 +117,16 @@ class RadianceParams(C.Structure):
 CRT_RADIANCE_PLAIN = 1
 assert C.sizeof(RadianceParams) == 48
 
+
+class ProbeParams(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("max_depth", C.c_uint32), ("base_seed", C.c_uint32), ("mode", C.c_uint32),
+                ("background", D3), ("t_min", C.c_double), ("batch_probes", C.c_uint32), ("flags", C.c_uint32)]
+
+
+CRT_PROBE_SPHERE, CRT_PROBE_HEMISPHERE = 0, 1
+CRT_SH_RADIANCE, CRT_SH_IRRADIANCE = 0, 1
+assert C.sizeof(ProbeParams) == 56
+
 # numpy views of the same records (for bulk scene I/O)
 MATERIAL_DTYPE = np.dtype([("kind", "<u4"), ("reserved", "<u4"), ("color", "<f8", 3), ("param", "<f8")])
 OBJECT_DTYPE = np.dtype([("kind", "<u4"), ("material", "<u4"), ("v", "<f8", 9)])
@@ -200,6 +210,13 @@ EXPORTS = {
                                C.c_void_p]),
     "crt_camera_rays_async": (C.c_int, [C.c_int, P(Camera), P(Tiling), C.c_uint32, C.c_uint32, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    "crt_probe_rays_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, P(ProbeParams), C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "crt_probes_async": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, P(ProbeParams),
+                                   C.c_void_p, C.c_void_p]),
+    "crt_probes": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, P(ProbeParams), C.c_void_p]),
+    "crt_sh_eval_async": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                    C.c_void_p, C.c_void_p]),
     "crt_ppm_values": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "crt_ppm_write": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "crt_render_guard": (C.c_int, [C.c_void_p, C.c_int, P(C.c_uint64), C.c_int]),

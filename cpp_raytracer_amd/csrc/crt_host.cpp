@@ -1569,6 +1569,80 @@ int crt_camera_rays_async(int device, const crt_camera* cam, const crt_tiling* t
     return device_camera_rays(device, cam, tiling, first_sample, num_samples, d_rays, d_states, stream);
 }
 
+// ---- irradiance probes: check_radiance's order (scene, params, then the fields, the count, the
+// pointers) ----------------------------------------------------------------------------------------
+static int check_probes(const std::string& who, bool need_scene, const void* s, const void* points,
+                        const char* points_name, const void* normals, const char* normals_name, size_t n,
+                        const crt_probe_params* params) {
+    if (need_scene && !s) return fail(CRT_E_INVALID, who + "scene is null");
+    if (!params) return fail(CRT_E_INVALID, who + "params is null");
+    if (params->samples < 1 || params->samples > (1u << 20))
+        return fail(CRT_E_INVALID, who + "samples must be in 1 .. 2^20");
+    if (params->mode != CRT_PROBE_SPHERE && params->mode != CRT_PROBE_HEMISPHERE)
+        return fail(CRT_E_INVALID, who + "unknown mode");
+    if (params->flags & ~CRT_RADIANCE_PLAIN) return fail(CRT_E_INVALID, who + "unknown flags");
+    if (!(params->t_min >= 0 && params->t_min <= 0x1p100))
+        return fail(CRT_E_INVALID, who + "t_min must be finite, >= 0 and <= 2^100");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(params->background[k])) return fail(CRT_E_INVALID, who + "background must be finite");
+    if (n > 0x7fffffffu) return fail(CRT_E_INVALID, who + "more than 2^31-1 probes");
+    if (params->mode == CRT_PROBE_HEMISPHERE) {
+        if (n && !normals) return fail(CRT_E_INVALID, who + normals_name + " is null (CRT_PROBE_HEMISPHERE needs the normals)");
+    } else if (normals) {
+        return fail(CRT_E_INVALID, who + normals_name + " must be null with CRT_PROBE_SPHERE");
+    }
+    if (n && !points) return fail(CRT_E_INVALID, who + points_name + " is null");
+    return CRT_OK;
+}
+
+int crt_probe_rays_async(int device, const double* d_points, const double* d_normals, size_t n,
+                         const crt_probe_params* params, double* d_rays, uint32_t* d_states, void* stream) {
+    clear_error();
+    const std::string who = "crt_probe_rays_async: ";
+    const int rc = check_probes(who, false, nullptr, d_points, "d_points", d_normals, "d_normals", n, params);
+    if (rc) return rc;
+    if (n > 0x7fffffffu / params->samples) return fail(CRT_E_INVALID, who + "more than 2^31-1 records");
+    if (n && (!d_rays || !d_states)) return fail(CRT_E_INVALID, who + "d_rays or d_states is null (the outputs are required)");
+    if (n == 0) return CRT_OK;  // no work
+    return device_probe_rays(device, d_points, d_normals, n, params, d_rays, d_states, stream);
+}
+
+int crt_probes_async(const crt_scene* s, int device, const double* d_points, const double* d_normals, size_t n,
+                     const crt_probe_params* params, double* d_coeff, void* stream) {
+    clear_error();
+    const std::string who = "crt_probes_async: ";
+    const int rc = check_probes(who, true, s, d_points, "d_points", d_normals, "d_normals", n, params);
+    if (rc) return rc;
+    if (n && !d_coeff) return fail(CRT_E_INVALID, who + "d_coeff is null (the output is required)");
+    if (n == 0) return CRT_OK;  // no work
+    return device_probes(s, device, d_points, d_normals, n, params, d_coeff, stream);
+}
+
+int crt_probes(crt_scene* s, int device, const double* points, const double* normals, size_t n,
+               const crt_probe_params* params, double* coeff) {
+    clear_error();
+    const std::string who = "crt_probes: ";
+    const int rc = check_probes(who, true, s, points, "points", normals, "normals", n, params);
+    if (rc) return rc;
+    if (n && !coeff) return fail(CRT_E_INVALID, who + "coeff is null (the output is required)");
+    if (n == 0) return CRT_OK;
+    return device_probes_host(s, device, points, normals, n, params, coeff);
+}
+
+int crt_sh_eval_async(int device, const double* d_coeff, size_t num_probes, const uint32_t* d_index,
+                      const double* d_dirs, size_t m, uint32_t what, double* d_rgb, void* stream) {
+    clear_error();
+    const std::string who = "crt_sh_eval_async: ";
+    if (what > CRT_SH_IRRADIANCE) return fail(CRT_E_INVALID, who + "what must be CRT_SH_RADIANCE or CRT_SH_IRRADIANCE");
+    if (m > 0x7fffffffu) return fail(CRT_E_INVALID, who + "more than 2^31-1 queries");
+    if (m && !d_coeff) return fail(CRT_E_INVALID, who + "d_coeff is null");
+    if (m && !d_index) return fail(CRT_E_INVALID, who + "d_index is null");
+    if (m && !d_dirs) return fail(CRT_E_INVALID, who + "d_dirs is null");
+    if (m && !d_rgb) return fail(CRT_E_INVALID, who + "d_rgb is null (the output is required)");
+    if (m == 0) return CRT_OK;  // no work
+    return device_sh_eval(device, d_coeff, num_probes, d_index, d_dirs, m, what, d_rgb, stream);
+}
+
 int crt_closest_hits(crt_scene* s, int device, const double* rays, size_t n, double t_min,
                      double t_max, crt_hit* out) {
     clear_error();

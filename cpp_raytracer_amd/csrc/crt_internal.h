@@ -420,6 +420,17 @@ int device_radiance_host(crt_scene* s, int device, const double* rays, size_t n,
                          const crt_radiance_params* prm, double* rgb);
 int device_camera_rays(int device, const crt_camera* cam, const crt_tiling* t, uint32_t first_sample,
                        uint32_t num_samples, double* d_rays, uint32_t* d_states, void* stream);
+// irradiance probes (crt_probes.hip; crt_host.cpp's entry points check the arguments): the generator
+// alone, the bake on device buffers, the same for host arrays, blocking (uploads the scene if
+// needed), and the evaluation of SH coefficients
+int device_probe_rays(int device, const double* d_points, const double* d_normals, size_t n,
+                      const crt_probe_params* prm, double* d_rays, uint32_t* d_states, void* stream);
+int device_probes(const crt_scene* s, int device, const double* d_points, const double* d_normals, size_t n,
+                  const crt_probe_params* prm, double* d_coeff, void* stream);
+int device_probes_host(crt_scene* s, int device, const double* points, const double* normals, size_t n,
+                       const crt_probe_params* prm, double* coeff);
+int device_sh_eval(int device, const double* d_coeff, size_t num_probes, const uint32_t* d_index,
+                   const double* d_dirs, size_t m, uint32_t what, double* d_rgb, void* stream);
 // denoising: first-hit features and the per-pixel variance (crt_device.hip), the filter
 // (crt_denoise.hip); the callers check the arguments
 int device_render_features(const crt_scene* s, int device, const crt_camera* cam, const crt_tiling* t,

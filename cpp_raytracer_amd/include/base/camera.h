@@ -417,6 +417,38 @@ public:
         return out;
     }
 
+    // Extension (not in the reference): a probe bake (crt_probes: one upload, the bake, one copy
+    // back). For each point, `samples` directions are drawn on the device, path-traced with this
+    // camera's max_depth, background and t_min, and reduced in crt_probes_async's fixed order, seeded
+    // with the next seed of the SeedSeqGenerator. mode CRT_PROBE_SPHERE: `normals` must be empty, nine
+    // spherical-harmonic coefficients (bands 0..2) a point; CRT_PROBE_HEMISPHERE: one unit normal a
+    // point, one cosine-weighted irradiance value a point. Returns the coefficients, K RGBs a point:
+    // element p * K + k is coefficient k of point p.
+    std::vector<RGB> probes(const BVH& world, const std::vector<Point3D>& points, const std::vector<Vec3D>& normals,
+                            uint32_t samples, uint32_t mode = CRT_PROBE_SPHERE) {
+        if (!normals.empty() && normals.size() != points.size()) crt_api::die("Camera::probes: one normal a point, or none");
+        init();
+        crt_probe_params p{};
+        p.samples = samples;
+        p.max_depth = resolved.max_depth;
+        p.base_seed = SeedSeqGenerator::get_instance().next_seed();
+        p.mode = mode;
+        for (int k = 0; k < 3; ++k) p.background[k] = resolved.background[k];
+        p.t_min = resolved.t_min;
+        const size_t n = points.size(), K = mode == CRT_PROBE_SPHERE ? 9 : 1;
+        std::vector<double> pts(n * 3), nrm(normals.size() * 3), coeff(n * K * 3);
+        for (size_t i = 0; i < n; ++i)
+            for (size_t k = 0; k < 3; ++k) pts[3 * i + k] = points[i][k];
+        for (size_t i = 0; i < normals.size(); ++i)
+            for (size_t k = 0; k < 3; ++k) nrm[3 * i + k] = normals[i][k];
+        if (crt_probes(world.gpu_scene().get(), 0, pts.data(), normals.empty() ? nullptr : nrm.data(), n, &p, coeff.data()))
+            crt_api::die("crt_probes");
+        std::vector<RGB> out;
+        out.reserve(n * K);
+        for (size_t i = 0; i < n * K; ++i) out.push_back(RGB::from_mag(coeff[3 * i], coeff[3 * i + 1], coeff[3 * i + 2]));
+        return out;
+    }
+
     Camera& set_camera_center(const Point3D& p) { camera.origin = p; return *this; }
     Camera& set_camera_direction(const Vec3D& d) { camera.dir = d; return *this; }
     Camera& set_camera_direction_towards(const Point3D& p) {

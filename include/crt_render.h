@@ -626,6 +626,95 @@ int crt_camera_rays_async(int device, const crt_camera* cam, const crt_tiling* t
                           uint32_t first_sample, uint32_t num_samples,
                           double* d_rays, uint32_t* d_states, void* stream);
 
+/* Irradiance probes: a whole probe bake on the device. For each of n points, S directions are drawn
+ * on the device, traced by crt_radiance_async's integrator and reduced in a fixed order to nine
+ * spherical-harmonic coefficients a colour channel (SPHERE) or one cosine-weighted irradiance value
+ * (HEMISPHERE). Every output bit is specified below; it depends on neither the grid nor the batch
+ * size nor the radiance route. */
+#define CRT_PROBE_SPHERE     0u  /* uniform directions; K = 9 SH coefficients (bands 0..2) per channel */
+#define CRT_PROBE_HEMISPHERE 1u  /* cosine-weighted about the normal; K = 1: irradiance */
+typedef struct crt_probe_params {
+    uint32_t samples;        /* S, 1 .. 2^20 */
+    uint32_t max_depth;      /* as crt_radiance_params */
+    uint32_t base_seed;
+    uint32_t mode;           /* CRT_PROBE_SPHERE or CRT_PROBE_HEMISPHERE */
+    double   background[3];  /* finite */
+    double   t_min;          /* finite, >= 0, <= 2^100 (crt_radiance_params' rule) */
+    uint32_t batch_probes;   /* probes per internal batch; 0 = the library picks. Sizes only: any value gives the same bits */
+    uint32_t flags;          /* 0 or CRT_RADIANCE_PLAIN (passed to the radiance query) */
+} crt_probe_params;          /* 56 bytes */
+
+/* The bake's first stage, also callable on its own: the rays and LCG states of n probes, S = samples
+ * records a probe, record r = p * S + s (probe-major). Of params only samples, base_seed and mode
+ * are used, the rest is checked as in crt_probes_async.
+ *   The state starts as crt_sample_seed(base_seed, (uint32_t)p, s). u = Vec3D::random_unit_vector
+ *   (vec3d.h:64-75) on it, as a render's shading draws it: x, y, z = crt_rand_double(state, -1, 1)
+ *   in that order until x*x + y*y + z*z < 1, then each times 1 / sqrt(x*x + y*y + z*z) (IEEE sqrt and
+ *   division).
+ *   d_rays[6r .. 6r + 5] (DEVICE) = {P, d}, P = d_points[3p .. 3p + 2]; SPHERE: d = u; HEMISPHERE:
+ *   d[k] = N[k] + u[k], N = d_normals[3p .. 3p + 2], the caller's unit normal, which the library does
+ *   not normalise. d_states[r] (DEVICE) = the state after the draws: the path's state.
+ * Lambertian's near_zero substitution (material.h) is not made: a generated ray outside
+ * crt_trace_async's contract (a non-finite component, e.g. from a NaN point, or d = 0 when u = -N
+ * exactly) is a miss under crt_radiance_async's rule and sees the background.
+ * CRT_E_INVALID as crt_probes_async's, and for n * samples > 2^31 - 1 records or a NULL output with
+ * n > 0. n == 0 is CRT_OK with no work. Enqueues on `stream`. */
+int crt_probe_rays_async(int device, const double* d_points, const double* d_normals, size_t n,
+                         const crt_probe_params* params, double* d_rays, uint32_t* d_states, void* stream);
+
+/* d_points: DEVICE memory on `device`, n x 3. d_normals: DEVICE, n x 3, required for HEMISPHERE and
+ * NULL for SPHERE. d_coeff: DEVICE, n x K x 3 doubles, d_coeff[(p * K + k) * 3 + j] for probe p,
+ * coefficient k, channel j.
+ * Paths: L_s = crt_radiance_async's output (max_depth, background, t_min, flags of params) for the ray
+ * and state of record p * S + s of crt_probe_rays_async.
+ * Basis (SPHERE), with (x, y, z) = d_s:
+ *   Y0 = 0.28209479177387814
+ *   Y1 = 0.4886025119029199 * y,  Y2 = 0.4886025119029199 * z,  Y3 = 0.4886025119029199 * x
+ *   Y4 = 1.0925484305920792 * (x * y),  Y5 = 1.0925484305920792 * (y * z),  Y7 = 1.0925484305920792 * (x * z)
+ *   Y6 = 0.31539156525252005 * ((3.0 * z) * z - 1.0)
+ *   Y8 = 0.5462742152960396 * (x * x - y * y)
+ * HEMISPHERE has the single term Y = 1, used without a multiply.
+ * Reduction, per probe p, coefficient k, channel j: the term of sample s is Y_k(d_s) * L_s[j]. Lane l
+ * (0..63) starts at 0.0 and adds the terms of samples s = l, l + 64, ... in increasing s. Then for
+ * step = 32, 16, 8, 4, 2, 1, lane l < step becomes lane[l] + lane[l + step]. The result is
+ * lane[0] * (W / (double)S), W = 12.566370614359172 (4 pi) for SPHERE and 3.141592653589793 for
+ * HEMISPHERE (the pdf is cos / pi, so E = pi * mean). No floating-point atomics are used.
+ * Batches: the probes are traced in batches of batch_probes whole probes (0: the most whose scratch
+ * of 76 bytes a record stays at or under 256 MiB; never fewer than one, never more than 2^31 - 1
+ * records), each generated, traced, reduced and freed in order on `stream`, scratch from the pass
+ * pool. Nothing is accumulated across batches.
+ * max_depth == 0 writes every coefficient +0 and n == 0 is CRT_OK with no work; neither launches a
+ * kernel. The scene must be resident on `device` (CRT_E_NOT_UPLOADED). CRT_E_INVALID, checked before
+ * any device work (the message names the rule): scene or params NULL, samples outside 1 .. 2^20,
+ * unknown mode, unknown flags, t_min outside [0, 2^100] or NaN, a background component not finite,
+ * n > 2^31 - 1, d_normals NULL for HEMISPHERE or given for SPHERE, d_points or d_coeff NULL with
+ * n > 0. Dielectric decisions count into the scene's parity guard as crt_radiance_async's do.
+ * One device, one depth and t_min a call, bands 0..2, no per-probe noise estimate. */
+int crt_probes_async(const crt_scene* scene, int device, const double* d_points, const double* d_normals,
+                     size_t n, const crt_probe_params* params, double* d_coeff, void* stream);
+
+/* crt_probes_async for HOST arrays, blocking: uploads the scene to `device` if it is not resident,
+ * then one upload of the points (and normals), the bake on a stream of its own, one copy back. Same
+ * rules, same results (the C++ drop-in's Camera::probes). */
+int crt_probes(crt_scene* scene, int device, const double* points, const double* normals, size_t n,
+               const crt_probe_params* params, double* coeff);
+
+/* Evaluates SPHERE coefficients: query i reads probe d_index[i] of d_coeff (DEVICE, num_probes x 9 x
+ * 3) at the unit direction d_dirs[3i .. 3i + 2] (DEVICE) and writes d_rgb[3i .. 3i + 2] (DEVICE):
+ * channel j is the sum over k = 0..8, in k order from 0.0, of A_k * (c[k][j] * Y_k(dir)), with
+ * crt_probes_async's basis. `what` = CRT_SH_RADIANCE: every A_k = 1, the band-limited radiance from
+ * direction dir. CRT_SH_IRRADIANCE: A_0 = CRT_SH_A0, A_1..3 = CRT_SH_A1, A_4..8 = CRT_SH_A2 (the
+ * clamped-cosine lobe's band factors), the irradiance of a surface with normal dir. A query with
+ * d_index[i] >= num_probes is written as zeros. m == 0 is CRT_OK with no work. CRT_E_INVALID:
+ * what > 1, m > 2^31 - 1, a NULL pointer with m > 0. Enqueues on `stream`. */
+#define CRT_SH_RADIANCE   0u
+#define CRT_SH_IRRADIANCE 1u
+#define CRT_SH_A0 3.141592653589793   /* pi */
+#define CRT_SH_A1 2.0943951023931953  /* 2 pi / 3 */
+#define CRT_SH_A2 0.7853981633974483  /* pi / 4 */
+int crt_sh_eval_async(int device, const double* d_coeff, size_t num_probes, const uint32_t* d_index,
+                      const double* d_dirs, size_t m, uint32_t what, double* d_rgb, void* stream);
+
 /* The integers Image::send_as_ppm prints (image.h:38-56; RGB::as_string rgb.h:99-115 with its
  * defaults: Reinhard tone map by luminance, gamma 2, static_cast<int>(255.999999 * v)) for the
  * n-pixel frame d_rgb (device memory on `device`, row-major RGB f64, e.g. crt_render_async's
