@@ -21,7 +21,8 @@ from ._capi import (CRT_BOX, CRT_DIELECTRIC, CRT_DIFFUSE_LIGHT, CRT_LAMBERTIAN, 
                     OBJECT_DTYPE, CRT_BLOCK_STOPPED, FEATURE_DTYPE, BVHParams, Camera, CameraSettings, CrtError,
                     DenoiseParams, RenderStats, SceneInfo, Tiling, TraceParams, CRT_TRACE_ANY, CRT_TRACE_PLAIN,
                     RadianceParams, CRT_RADIANCE_PLAIN, ProbeParams, CRT_PROBE_SPHERE, CRT_PROBE_HEMISPHERE,
-                    CRT_SH_RADIANCE, CRT_SH_IRRADIANCE, check, lib)
+                    CRT_SH_RADIANCE, CRT_SH_IRRADIANCE, Lens, CRT_LENS_PINHOLE, CRT_LENS_ORTHOGRAPHIC,
+                    CRT_LENS_EQUIRECT, CRT_LENS_FISHEYE, CRT_LENS_CUBE, check, lib)
 
 __all__ = [
     "SceneData", "GpuScene", "CameraSettings", "Camera", "Tiling", "RenderStats", "CrtError",
@@ -31,6 +32,8 @@ __all__ = [
     "TraceParams", "CRT_TRACE_ANY", "CRT_TRACE_PLAIN", "HIT_DTYPE",
     "RadianceParams", "CRT_RADIANCE_PLAIN",
     "ProbeParams", "CRT_PROBE_SPHERE", "CRT_PROBE_HEMISPHERE", "CRT_SH_RADIANCE", "CRT_SH_IRRADIANCE", "sh_eval",
+    "Lens", "make_lens", "CRT_LENS_PINHOLE", "CRT_LENS_ORTHOGRAPHIC", "CRT_LENS_EQUIRECT", "CRT_LENS_FISHEYE",
+    "CRT_LENS_CUBE",
     "CRT_LAMBERTIAN", "CRT_METAL", "CRT_DIELECTRIC", "CRT_DIFFUSE_LIGHT",
     "CRT_SPHERE", "CRT_PARALLELOGRAM", "CRT_BOX",
 ]
@@ -144,6 +147,40 @@ def sh_eval(coeff, index, dirs, irradiance: bool = False):
                                           C.c_void_p(out.data_ptr()),
                                           C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "crt_sh_eval_async")
         return out
+
+
+_LENS_KINDS = {"pinhole": CRT_LENS_PINHOLE, "orthographic": CRT_LENS_ORTHOGRAPHIC, "equirect": CRT_LENS_EQUIRECT,
+               "fisheye": CRT_LENS_FISHEYE, "cube": CRT_LENS_CUBE}
+
+
+def make_lens(kind, origin=(0.0, 0.0, 0.0), forward=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), extent_x: float = 0.0,
+              extent_y: float = 0.0, batch_pixels: int = 0, plain: bool = False) -> Lens:
+    """A crt_lens for GpuScene.render_lens / lens_rays: kind is a CRT_LENS_* constant or "pinhole",
+    "orthographic", "equirect", "fisheye", "cube". The basis is orthonormalised here, in numpy (the
+    library uses it as given): forward is normalised, right = normalise(forward x up), then up = right x
+    forward. With both extents 0, EQUIRECT gets the full sphere (pi, pi / 2) and FISHEYE a half-angle of
+    pi / 2 each way; ORTHOGRAPHIC needs its half width and half height. batch_pixels sizes the internal
+    batches only; plain=True passes CRT_RADIANCE_PLAIN to the radiance query: the same bits either way."""
+    if isinstance(kind, str):
+        if kind not in _LENS_KINDS:
+            raise CrtError(f"make_lens: kind must be one of {sorted(_LENS_KINDS)}")
+        kind = _LENS_KINDS[kind]
+    f = np.asarray(forward, np.float64).reshape(3)
+    u = np.asarray(up, np.float64).reshape(3)
+    f = f / np.sqrt(f.dot(f))
+    r = np.cross(f, u)
+    r = r / np.sqrt(r.dot(r))
+    u = np.cross(r, f)
+    if not (np.isfinite(f).all() and np.isfinite(r).all()):
+        raise CrtError("make_lens: forward and up must be finite, non-zero and not parallel")
+    if extent_x == 0 and extent_y == 0:
+        if kind == CRT_LENS_EQUIRECT:
+            extent_x, extent_y = float(np.pi), float(np.pi) / 2
+        elif kind == CRT_LENS_FISHEYE:
+            extent_x = extent_y = float(np.pi) / 2
+    D3 = _capi.D3
+    return Lens(kind, CRT_RADIANCE_PLAIN if plain else 0, D3(*[float(v) for v in origin]), D3(*r.tolist()),
+                D3(*u.tolist()), D3(*f.tolist()), float(extent_x), float(extent_y), int(batch_pixels))
 
 
 def device_count() -> int:
@@ -697,3 +734,56 @@ class GpuScene:
                                                   C.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
                       "crt_camera_rays_async")
             return rays, states
+
+    def lens_rays(self, cam: Camera, lens: Lens, first_sample: int = 0, num_samples: Optional[int] = None,
+                  device: int = 0):
+        """The rays a lens render of the whole frame traces and the LCG states after their draws
+        (crt_lens_rays_async), on `device` and its current stream, without synchronising: (rays (n, 6)
+        float64, states (n,) int32) for samples [first_sample, first_sample + num_samples) (None: up to
+        cam.samples_per_pixel), record (row * image_w + col) * num_samples + (sample - first_sample).
+        radiance(rays, states, cam.max_depth, cam.background, cam.t_min) is the per-sample radiance
+        that render_lens reduces."""
+        import torch
+        if not isinstance(cam, Camera) or not isinstance(lens, Lens):
+            raise CrtError("lens_rays: cam must be a resolved Camera (resolve_camera) and lens a Lens (make_lens)")
+        if num_samples is None:
+            num_samples = cam.samples_per_pixel - first_sample
+        if first_sample < 0 or num_samples < 0:
+            raise CrtError("lens_rays: first_sample and num_samples must not be negative")
+        if first_sample + num_samples > 0xFFFFFFFF:
+            raise CrtError("lens_rays: first_sample + num_samples exceeds 2^32-1")
+        n = cam.image_h * cam.image_w * num_samples
+        if n > 0x7FFFFFFF:
+            raise CrtError("lens_rays: more than 2^31-1 records")
+        with torch.cuda.device(device):
+            dev = torch.device("cuda", device)
+            rays = torch.empty((n, 6), dtype=torch.float64, device=dev)
+            states = torch.empty((n,), dtype=torch.int32, device=dev)
+            if n:
+                check(lib().crt_lens_rays_async(device, C.byref(cam), C.byref(lens), first_sample, num_samples,
+                                                C.c_void_p(rays.data_ptr()), C.c_void_p(states.data_ptr()),
+                                                C.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+                      "crt_lens_rays_async")
+            return rays, states
+
+    def render_lens_async(self, device: int, cam: Camera, lens: Lens, out_ptr: int, stream: int = 0) -> None:
+        """Enqueue a whole-frame render through `lens` (crt_render_lens_async) into the device buffer
+        at out_ptr (image_h * image_w * 3 doubles): the rays of lens_rays, traced as radiance_async
+        traces them and summed per pixel in render_async's order. The scene must be uploaded to
+        `device`."""
+        check(lib().crt_render_lens_async(self._h, device, C.byref(cam), C.byref(lens), C.c_void_p(out_ptr or None),
+                                          C.c_void_p(stream)), "crt_render_lens_async")
+
+    def render_lens(self, cam: Camera, lens: Lens, device: int = 0):
+        """Whole-frame render through `lens` (make_lens) into an (h, w, 3) float64 torch tensor on
+        `device`. Runs on that device's current stream and does not synchronise; the scene is uploaded
+        there first if it is not yet (that blocks). With kind "pinhole" the frame is render_async's,
+        bit for bit."""
+        import torch
+        if not isinstance(cam, Camera) or not isinstance(lens, Lens):
+            raise CrtError("render_lens: cam must be a resolved Camera (resolve_camera) and lens a Lens (make_lens)")
+        with torch.cuda.device(device):
+            out = torch.empty((cam.image_h, cam.image_w, 3), dtype=torch.float64, device=torch.device("cuda", device))
+            self.upload(device)
+            self.render_lens_async(device, cam, lens, out.data_ptr(), torch.cuda.current_stream(device).cuda_stream)
+            return out

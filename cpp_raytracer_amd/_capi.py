@@ -127,6 +127,15 @@ CRT_PROBE_SPHERE, CRT_PROBE_HEMISPHERE = 0, 1
 CRT_SH_RADIANCE, CRT_SH_IRRADIANCE = 0, 1
 assert C.sizeof(ProbeParams) == 56
 
+
+class Lens(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("origin", D3), ("right", D3), ("up", D3),
+                ("forward", D3), ("extent_x", C.c_double), ("extent_y", C.c_double), ("batch_pixels", C.c_uint64)]
+
+
+CRT_LENS_PINHOLE, CRT_LENS_ORTHOGRAPHIC, CRT_LENS_EQUIRECT, CRT_LENS_FISHEYE, CRT_LENS_CUBE = 0, 1, 2, 3, 4
+assert C.sizeof(Lens) == 128
+
 # numpy views of the same records (for bulk scene I/O)
 MATERIAL_DTYPE = np.dtype([("kind", "<u4"), ("reserved", "<u4"), ("color", "<f8", 3), ("param", "<f8")])
 OBJECT_DTYPE = np.dtype([("kind", "<u4"), ("material", "<u4"), ("v", "<f8", 9)])
@@ -217,6 +226,10 @@ EXPORTS = {
     "crt_probes": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, P(ProbeParams), C.c_void_p]),
     "crt_sh_eval_async": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
                                     C.c_void_p, C.c_void_p]),
+    "crt_lens_rays_async": (C.c_int, [C.c_int, P(Camera), P(Lens), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "crt_render_lens_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), C.c_void_p, C.c_void_p]),
+    "crt_render_lens": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), C.c_void_p]),
     "crt_ppm_values": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "crt_ppm_write": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "crt_render_guard": (C.c_int, [C.c_void_p, C.c_int, P(C.c_uint64), C.c_int]),

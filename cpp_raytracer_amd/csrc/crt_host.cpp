@@ -1643,6 +1643,88 @@ int crt_sh_eval_async(int device, const double* d_coeff, size_t num_probes, cons
     return device_sh_eval(device, d_coeff, num_probes, d_index, d_dirs, m, what, d_rgb, stream);
 }
 
+// ---- lens renders: the pointers, the lens (kind, flags, finiteness, extents), the frame's shape, then
+// check_radiance's rules for t_min and the background ------------------------------------------------
+static int check_lens(const std::string& who, bool need_scene, const void* s, const crt_camera* cam,
+                      const crt_lens* lens, bool need_spp) {
+    constexpr double kPi = 3.141592653589793, kHalfPi = 1.5707963267948966;
+    if (need_scene && !s) return fail(CRT_E_INVALID, who + "scene is null");
+    if (!cam) return fail(CRT_E_INVALID, who + "cam is null");
+    if (!lens) return fail(CRT_E_INVALID, who + "lens is null");
+    if (lens->kind > CRT_LENS_CUBE) return fail(CRT_E_INVALID, who + "unknown kind");
+    if (lens->flags & ~CRT_RADIANCE_PLAIN) return fail(CRT_E_INVALID, who + "unknown flags");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(lens->right[k]) || !std::isfinite(lens->up[k]) || !std::isfinite(lens->forward[k]))
+            return fail(CRT_E_INVALID, who + "the lens basis (right, up, forward) must be finite");
+    if (!std::isfinite(lens->extent_x) || !std::isfinite(lens->extent_y))
+        return fail(CRT_E_INVALID, who + "the lens extents must be finite");
+    const double ex = lens->extent_x, ey = lens->extent_y;
+    switch (lens->kind) {
+        case CRT_LENS_PINHOLE:
+        case CRT_LENS_CUBE:
+            if (ex != 0 || ey != 0) return fail(CRT_E_INVALID, who + "extent_x and extent_y must be 0 for PINHOLE and CUBE");
+            break;
+        case CRT_LENS_ORTHOGRAPHIC:
+            if (!(ex > 0 && ey > 0)) return fail(CRT_E_INVALID, who + "ORTHOGRAPHIC extents must be > 0");
+            break;
+        case CRT_LENS_EQUIRECT:
+            if (!(ex > 0 && ex <= kPi && ey > 0 && ey <= kHalfPi))
+                return fail(CRT_E_INVALID, who + "EQUIRECT extents must be in (0, pi] and (0, pi/2]");
+            break;
+        default:  // FISHEYE
+            if (!(ex > 0 && ey > 0 && ex * ex + ey * ey <= kPi * kPi))
+                return fail(CRT_E_INVALID, who + "FISHEYE extents must be > 0 with extent_x^2 + extent_y^2 <= pi^2");
+            break;
+    }
+    // the origin is not checked: a non-finite one gives rays outside the query's contract, all misses
+    if (cam->image_w == 0 || cam->image_h == 0) return fail(CRT_E_INVALID, who + "image_w and image_h must not be 0");
+    if (lens->kind == CRT_LENS_CUBE && static_cast<uint64_t>(cam->image_h) != 6ull * cam->image_w)
+        return fail(CRT_E_INVALID, who + "CUBE needs image_h == 6 * image_w");
+    if (need_spp) {
+        if (cam->samples_per_pixel == 0) return fail(CRT_E_INVALID, who + "samples_per_pixel must not be 0");
+        if (cam->samples_per_pixel > 0x7fffffffu) return fail(CRT_E_INVALID, who + "samples_per_pixel exceeds 2^31-1");
+    }
+    if (!(cam->t_min >= 0 && cam->t_min <= 0x1p100))
+        return fail(CRT_E_INVALID, who + "t_min must be finite, >= 0 and <= 2^100");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(cam->background[k])) return fail(CRT_E_INVALID, who + "background must be finite");
+    return CRT_OK;
+}
+
+int crt_lens_rays_async(int device, const crt_camera* cam, const crt_lens* lens, uint32_t first_sample,
+                        uint32_t num_samples, double* d_rays, uint32_t* d_states, void* stream) {
+    clear_error();
+    const std::string who = "crt_lens_rays_async: ";
+    const int rc = check_lens(who, false, nullptr, cam, lens, false);
+    if (rc) return rc;
+    if (!d_rays || !d_states) return fail(CRT_E_INVALID, who + "d_rays or d_states is null (the outputs are required)");
+    if (static_cast<uint64_t>(first_sample) + num_samples > 0xffffffffull)
+        return fail(CRT_E_INVALID, who + "first_sample + num_samples exceeds 2^32-1");
+    if (num_samples == 0) return CRT_OK;  // no work
+    if (static_cast<uint64_t>(cam->image_w) * cam->image_h > 0x7fffffffull / num_samples)
+        return fail(CRT_E_INVALID, who + "more than 2^31-1 records");
+    return device_lens_rays(device, cam, lens, first_sample, num_samples, d_rays, d_states, stream);
+}
+
+int crt_render_lens_async(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, double* d_rgb,
+                          void* stream) {
+    clear_error();
+    const std::string who = "crt_render_lens_async: ";
+    const int rc = check_lens(who, true, s, cam, lens, true);
+    if (rc) return rc;
+    if (!d_rgb) return fail(CRT_E_INVALID, who + "d_rgb is null (the output is required)");
+    return device_render_lens(s, device, cam, lens, d_rgb, stream);
+}
+
+int crt_render_lens(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, double* rgb) {
+    clear_error();
+    const std::string who = "crt_render_lens: ";
+    const int rc = check_lens(who, true, s, cam, lens, true);
+    if (rc) return rc;
+    if (!rgb) return fail(CRT_E_INVALID, who + "rgb is null (the output is required)");
+    return device_render_lens_host(s, device, cam, lens, rgb);
+}
+
 int crt_closest_hits(crt_scene* s, int device, const double* rays, size_t n, double t_min,
                      double t_max, crt_hit* out) {
     clear_error();

@@ -431,6 +431,14 @@ int device_probes_host(crt_scene* s, int device, const double* points, const dou
                        const crt_probe_params* prm, double* coeff);
 int device_sh_eval(int device, const double* d_coeff, size_t num_probes, const uint32_t* d_index,
                    const double* d_dirs, size_t m, uint32_t what, double* d_rgb, void* stream);
+// lens renders (crt_lens.hip; crt_host.cpp's entry points check the arguments): the generator alone
+// over the whole frame, the render on a device buffer, the same for a host array, blocking (uploads
+// the scene if needed)
+int device_lens_rays(int device, const crt_camera* cam, const crt_lens* lens, uint32_t first_sample,
+                     uint32_t num_samples, double* d_rays, uint32_t* d_states, void* stream);
+int device_render_lens(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, double* d_rgb,
+                       void* stream);
+int device_render_lens_host(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, double* rgb);
 // denoising: first-hit features and the per-pixel variance (crt_device.hip), the filter
 // (crt_denoise.hip); the callers check the arguments
 int device_render_features(const crt_scene* s, int device, const crt_camera* cam, const crt_tiling* t,

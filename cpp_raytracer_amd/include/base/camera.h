@@ -36,6 +36,66 @@ struct DenoiseOptions {
     double sigma_p = 0.05;          // plane-distance tolerance as a fraction of the hit distance
 };
 
+// Extension (not in the reference): the projection of Camera::render_lens (crt_lens, whose fields
+// these are). The factories orthonormalise the basis: forward is normalised, right = unit(forward x
+// up), then up = right x forward; the library uses the basis as given.
+struct Lens {
+    uint32_t kind = CRT_LENS_PINHOLE;
+    Point3D origin{0, 0, 0};
+    Vec3D right{1, 0, 0}, up{0, 1, 0}, forward{0, 0, -1};
+    double extent_x = 0, extent_y = 0;
+    uint64_t batch_pixels = 0;  // sizes the internal batches only
+    bool plain = false;         // CRT_RADIANCE_PLAIN: the same bits either way
+
+    // the camera's own projection: render_lens then gives render()'s picture
+    static Lens pinhole() { return Lens{}; }
+    static Lens looking(uint32_t kind, const Point3D& origin, const Vec3D& forward, const Vec3D& up, double ex, double ey) {
+        Lens l;
+        l.kind = kind;
+        l.origin = origin;
+        l.forward = forward.unit_vector();
+        l.right = cross(l.forward, up).unit_vector();
+        l.up = cross(l.right, l.forward);
+        l.extent_x = ex;
+        l.extent_y = ey;
+        return l;
+    }
+    // half_w, half_h: the half width and half height of the view in world units
+    static Lens orthographic(const Point3D& origin, const Vec3D& forward, const Vec3D& up, double half_w, double half_h) {
+        return looking(CRT_LENS_ORTHOGRAPHIC, origin, forward, up, half_w, half_h);
+    }
+    // a latitude-longitude panorama: the whole sphere by default
+    static Lens equirect(const Point3D& origin, const Vec3D& forward = Vec3D{0, 0, -1}, const Vec3D& up = Vec3D{0, 1, 0},
+                         double half_angle_x = std::numbers::pi, double half_angle_y = std::numbers::pi / 2) {
+        return looking(CRT_LENS_EQUIRECT, origin, forward, up, half_angle_x, half_angle_y);
+    }
+    // equidistant fisheye: the angles from the axis at the frame's left-right and top-bottom edges
+    static Lens fisheye(const Point3D& origin, const Vec3D& forward = Vec3D{0, 0, -1}, const Vec3D& up = Vec3D{0, 1, 0},
+                        double edge_angle_x = std::numbers::pi / 2, double edge_angle_y = std::numbers::pi / 2) {
+        return looking(CRT_LENS_FISHEYE, origin, forward, up, edge_angle_x, edge_angle_y);
+    }
+    // six 90-degree faces +X -X +Y -Y +Z -Z stacked top to bottom: the image must be w x 6w
+    static Lens cube(const Point3D& origin, const Vec3D& forward = Vec3D{0, 0, -1}, const Vec3D& up = Vec3D{0, 1, 0}) {
+        return looking(CRT_LENS_CUBE, origin, forward, up, 0, 0);
+    }
+
+    crt_lens as_crt() const {
+        crt_lens l{};
+        l.kind = kind;
+        l.flags = plain ? CRT_RADIANCE_PLAIN : 0u;
+        for (size_t k = 0; k < 3; ++k) {
+            l.origin[k] = origin[k];
+            l.right[k] = right[k];
+            l.up[k] = up[k];
+            l.forward[k] = forward[k];
+        }
+        l.extent_x = extent_x;
+        l.extent_y = extent_y;
+        l.batch_pixels = batch_pixels;
+        return l;
+    }
+};
+
 class Camera {
     size_t image_w = 1280, image_h = 720;
     double viewport_w = 0, viewport_h = 0;
@@ -315,6 +375,21 @@ class Camera {
         return img;
     }
 
+    Image render_scene_lens(const crt_api::GpuScene& g, const Lens& lens) {
+        init();
+        resolved.base_seed = SeedSeqGenerator::get_instance().next_seed();
+        const crt_lens l = lens.as_crt();
+        std::vector<double> rgb(image_w * image_h * 3);
+        if (crt_render_lens(g.get(), 0, &resolved, &l, rgb.data())) crt_api::die("crt_render_lens");
+        auto img = Image::with_dimensions(image_w, image_h);
+        for (size_t r = 0; r < image_h; ++r)
+            for (size_t c = 0; c < image_w; ++c) {
+                const double* p = &rgb[(r * image_w + c) * 3];
+                img[r][c] = RGB::from_mag(p[0], p[1], p[2]);
+            }
+        return img;
+    }
+
 public:
     // Extension (not in the reference): render (adaptive_threshold < 0: every sample) or
     // render_adaptive (blocks stop at that threshold, default pass length and sample floor), then
@@ -447,6 +522,23 @@ public:
         out.reserve(n * K);
         for (size_t i = 0; i < n * K; ++i) out.push_back(RGB::from_mag(coeff[3 * i], coeff[3 * i + 1], coeff[3 * i + 2]));
         return out;
+    }
+
+    // Extension (not in the reference): a whole frame through `lens` (crt_render_lens: one upload,
+    // the render, one copy back) with this camera's image size, samples, max_depth, background and
+    // t_min, seeded with the next seed of the SeedSeqGenerator. Panoramic, fisheye, cube-map and
+    // orthographic frames; with Lens::pinhole() the picture is render()'s. A cube map needs an image
+    // of w x 6w.
+    Image render_lens(const BVH& world, const Lens& lens) { return render_scene_lens(world.gpu_scene(), lens); }
+    template <typename T>
+    requires std::is_base_of_v<Hittable, T>
+    Image render_lens(const T& world, const Lens& lens) {
+        if constexpr (std::is_same_v<T, Scene>) {
+            return render_lens(BVH(world), lens);
+        } else {
+            crt_api::GpuScene s(world, 32, 12, true);
+            return render_scene_lens(s, lens);
+        }
     }
 
     Camera& set_camera_center(const Point3D& p) { camera.origin = p; return *this; }

@@ -715,6 +715,98 @@ int crt_probes(crt_scene* scene, int device, const double* points, const double*
 int crt_sh_eval_async(int device, const double* d_coeff, size_t num_probes, const uint32_t* d_index,
                       const double* d_dirs, size_t m, uint32_t what, double* d_rgb, void* stream);
 
+/* Lens renders: a whole frame through a caller-chosen projection. The rays are generated on the
+ * device, traced by crt_radiance_async's integrator unchanged and summed per pixel in
+ * crt_render_async's order. Every output bit is specified below (up to the device library's sin and
+ * cos for EQUIRECT and FISHEYE); it depends on neither the grid nor the batch size nor the radiance
+ * route. */
+#define CRT_LENS_PINHOLE       0u  /* the reference camera: cam's own origin, pixel00, deltas, defocus disk */
+#define CRT_LENS_ORTHOGRAPHIC  1u
+#define CRT_LENS_EQUIRECT      2u
+#define CRT_LENS_FISHEYE       3u  /* equidistant */
+#define CRT_LENS_CUBE          4u  /* six 90-degree faces stacked top to bottom: image_h == 6 * image_w */
+typedef struct crt_lens {
+    uint32_t kind, flags;        /* flags: CRT_RADIANCE_PLAIN only; anything else CRT_E_INVALID */
+    double origin[3];
+    double right[3], up[3], forward[3];  /* the caller's basis, used as given, never normalised */
+    double extent_x, extent_y;   /* ORTHOGRAPHIC: half width / half height in world units, > 0;
+                                    EQUIRECT: half horizontal / half vertical angle, (0, pi] / (0, pi/2];
+                                    FISHEYE: angle from the axis at the frame's left-right / top-bottom edge,
+                                    > 0, extent_x^2 + extent_y^2 <= pi^2; PINHOLE, CUBE: must be 0 */
+    uint64_t batch_pixels;       /* 0: the most whole pixels whose scratch (76 B a record) stays <= 256 MiB.
+                                    Sizes only: any value gives the same bits */
+} crt_lens;                      /* 128 bytes */
+
+/* The render's first stage, also callable on its own: the rays and LCG states of the whole frame,
+ * num_samples records a pixel, record r = (row * image_w + col) * num_samples + (s - first_sample)
+ * for sample s in [first_sample, first_sample + num_samples). Of cam, image_w, image_h and base_seed
+ * are used for every kind (PINHOLE also reads origin, pixel00, the deltas and the defocus disk); the
+ * rest is checked as in crt_render_lens_async. pi below is the double 3.141592653589793.
+ *   The state starts as crt_sample_seed(base_seed, row * image_w + col, s).
+ *   PINHOLE: the record of crt_camera_rays_async, byte for byte: with defocus_angle > 0, vx, vy =
+ *     crt_rand_double(state, -1, 1) in that order until vx*vx + vy*vy + 0.0*0.0 < 1, then
+ *     o = (origin + defocus_disk_x * vx) + defocus_disk_y * vy, else o = origin;
+ *     uy = crt_rand_double(state, -0.5, 0.5), then ux likewise; per component
+ *     centre = (pixel00 + pixel_delta_y * (double)row) + pixel_delta_x * (double)col,
+ *     sample = (centre + pixel_delta_x * ux) + pixel_delta_y * uy,  d = sample - o.
+ *     lens->origin, the basis and the extents are not used.
+ *   Every other kind draws no defocus: uy = crt_rand_double(state, -0.5, 0.5), then ux likewise (the
+ *     pixel_delta_y draw first, as above). With h_face = image_h and row_in_face = row, except for
+ *     CUBE, where h_face = image_w, face = row / image_w and row_in_face = row % image_w:
+ *       fx = ((double)col + 0.5) + ux,          fy = ((double)row_in_face + 0.5) + uy,
+ *       a = fx * (2.0 / (double)image_w) - 1.0,  b = 1.0 - fy * (2.0 / (double)h_face).
+ *     With R = right, U = up, F = forward, O = origin, per component:
+ *     ORTHOGRAPHIC: o = (O + R * (a * extent_x)) + U * (b * extent_y),  d = F.
+ *     EQUIRECT: phi = a * extent_x, theta = b * extent_y, o = O,
+ *       d = (R * (cos(theta) * sin(phi)) + U * sin(theta)) + F * (cos(theta) * cos(phi)).
+ *     FISHEYE: px = a * extent_x, py = b * extent_y, psi = sqrt(px * px + py * py),
+ *       k = psi == 0 ? 1.0 : sin(psi) / psi, o = O,
+ *       d = (R * (px * k) + U * (py * k)) + F * cos(psi).
+ *     CUBE: u = a, v = -b; the local direction (x, y, z) of face 0..5 (the usual cube-map table, v
+ *       pointing down the image):
+ *         0 +X (1, -v, -u)   1 -X (-1, -v, u)   2 +Y (u, 1, v)
+ *         3 -Y (u, -1, -v)   4 +Z (u, -v, 1)    5 -Z (-u, -v, -1)
+ *       o = O,  d = (R * x + U * y) + F * z.
+ *   sin, cos and sqrt are the device library's f64 functions (sqrt and the division IEEE); d is not
+ *   normalised. d_rays[6r .. 6r + 5] (DEVICE) = {o, d}; d_states[r] (DEVICE) = the state after the
+ *   draws: the path's state.
+ * A generated ray outside crt_trace_async's contract (a non-finite component, e.g. from a NaN origin)
+ * is a miss under crt_radiance_async's rule and sees the background.
+ * CRT_E_INVALID as crt_render_lens_async's (samples_per_pixel is not read), and for
+ * first_sample + num_samples > 2^32 - 1, more than 2^31 - 1 records, d_rays or d_states NULL.
+ * num_samples == 0 is CRT_OK with no work. Enqueues on `stream`. */
+int crt_lens_rays_async(int device, const crt_camera* cam, const crt_lens* lens, uint32_t first_sample,
+                        uint32_t num_samples, double* d_rays, uint32_t* d_states, void* stream);
+
+/* d_rgb: DEVICE memory on `device`, image_h * image_w * 3 doubles, the whole frame, row-major.
+ * Of cam, image_w, image_h, samples_per_pixel, max_depth, background, t_min and base_seed are used
+ * for every kind.
+ * Paths: L_s = crt_radiance_async's output (cam's max_depth, background, t_min; lens->flags) for the
+ * ray and state of crt_lens_rays_async(first_sample = 0, num_samples = samples_per_pixel).
+ * Reduction, per pixel and channel, crt_render_async's: with L = crt_sample_chunk_len(spp), chunk c
+ * is the sum of L_s for s = c * L .. min(spp, (c + 1) * L) - 1 in that order, starting from 0.0; the
+ * chunk sums are added in chunk order; the result is multiplied by 1 / (double)spp. No
+ * floating-point atomics are used. With kind PINHOLE the frame is crt_render_async's, bit for bit.
+ * Batches: consecutive whole pixels in row-major order, batch_pixels of them (0: the most whose
+ * scratch of 76 bytes a record stays at or under 256 MiB; never fewer than one pixel, never more than
+ * 2^31 - 1 records), each generated, traced, reduced and freed in order on `stream`, scratch from the
+ * pass pool. Nothing is carried between batches.
+ * max_depth == 0 writes +0 everywhere with a memset and launches nothing. The scene must be resident
+ * on `device` (CRT_E_NOT_UPLOADED). CRT_E_INVALID, checked before any device work (the message names
+ * the rule): scene, cam, lens or d_rgb NULL; unknown kind; unknown flags; a component of right, up
+ * or forward or an extent not finite (for PINHOLE too; the origin is not checked: a non-finite one
+ * gives rays outside the query's contract, a frame of the background); an extent outside its range for the kind (see crt_lens); image_h != 6 * image_w for CUBE; image_w,
+ * image_h or samples_per_pixel equal to 0; samples_per_pixel > 2^31 - 1; t_min outside [0, 2^100] or
+ * NaN; a background component not finite. Dielectric decisions count into the scene's parity guard
+ * as crt_radiance_async's do. One device a call, no defocus for the kinds other than PINHOLE. */
+int crt_render_lens_async(const crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens,
+                          double* d_rgb, void* stream);
+
+/* crt_render_lens_async for a HOST array, blocking: uploads the scene to `device` if it is not
+ * resident, then the render on a stream of its own and one copy back. Same rules, same results
+ * (the C++ drop-in's Camera::render_lens). */
+int crt_render_lens(crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens, double* rgb);
+
 /* The integers Image::send_as_ppm prints (image.h:38-56; RGB::as_string rgb.h:99-115 with its
  * defaults: Reinhard tone map by luminance, gamma 2, static_cast<int>(255.999999 * v)) for the
  * n-pixel frame d_rgb (device memory on `device`, row-major RGB f64, e.g. crt_render_async's
