@@ -33,7 +33,7 @@ __all__ = [
     "RadianceParams", "CRT_RADIANCE_PLAIN",
     "ProbeParams", "CRT_PROBE_SPHERE", "CRT_PROBE_HEMISPHERE", "CRT_SH_RADIANCE", "CRT_SH_IRRADIANCE", "sh_eval",
     "Lens", "make_lens", "CRT_LENS_PINHOLE", "CRT_LENS_ORTHOGRAPHIC", "CRT_LENS_EQUIRECT", "CRT_LENS_FISHEYE",
-    "CRT_LENS_CUBE",
+    "CRT_LENS_CUBE", "LensRender",
     "CRT_LAMBERTIAN", "CRT_METAL", "CRT_DIELECTRIC", "CRT_DIFFUSE_LIGHT",
     "CRT_SPHERE", "CRT_PARALLELOGRAM", "CRT_BOX",
 ]
@@ -787,3 +787,95 @@ class GpuScene:
             self.upload(device)
             self.render_lens_async(device, cam, lens, out.data_ptr(), torch.cuda.current_stream(device).cuda_stream)
             return out
+
+    def render_lens_pass(self, device: int, cam: Camera, lens: Lens, first: int, count: int, sum_ptr: int,
+                         noise_ptr: int = 0, out_ptr: int = 0, blocks_ptr: int = 0, active_hint: int = 0,
+                         stream: int = 0) -> None:
+        """Samples [first, first + count) of a cam.samples_per_pixel lens render of the whole frame into
+        the running sums at sum_ptr (crt_render_lens_pass_async; render_pass's buffers and boundaries).
+        With blocks_ptr (one uint32 per 16 x 4 block of the frame) only the blocks whose word equals
+        `first` are generated and traced, and the call waits for the stream once to read how many
+        pixels that is; without it the call only enqueues. active_hint never changes the result."""
+        check(lib().crt_render_lens_pass_async(self._h, device, C.byref(cam), C.byref(lens), first, count,
+                                               C.c_void_p(sum_ptr or None), C.c_void_p(noise_ptr or None),
+                                               C.c_void_p(out_ptr or None), C.c_void_p(blocks_ptr or None),
+                                               min(active_hint, 0xFFFFFFFF), C.c_void_p(stream)),
+              "crt_render_lens_pass_async")
+
+    def lens_centre_rays(self, cam: Camera, lens: Lens, device: int = 0):
+        """The rays through the pixel centres of a lens frame (crt_lens_centre_rays_async), the rays
+        lens_features traces: an (h * w, 6) float64 torch tensor on `device`, record row * w + col.
+        Runs on the device's current stream and does not synchronise."""
+        import torch
+        if not isinstance(cam, Camera) or not isinstance(lens, Lens):
+            raise CrtError("lens_centre_rays: cam must be a resolved Camera (resolve_camera) and lens a Lens (make_lens)")
+        with torch.cuda.device(device):
+            rays = torch.empty((cam.image_h * cam.image_w, 6), dtype=torch.float64, device=torch.device("cuda", device))
+            check(lib().crt_lens_centre_rays_async(device, C.byref(cam), C.byref(lens), C.c_void_p(rays.data_ptr() or None),
+                                                   C.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+                  "crt_lens_centre_rays_async")
+            return rays
+
+    def lens_features(self, device: int, cam: Camera, lens: Lens, feat_ptr: int, stream: int = 0) -> None:
+        """Enqueue the first-hit features of a lens frame (crt_lens_features_async) into the device
+        buffer at feat_ptr: one 88-byte crt_feature (FEATURE_DTYPE) per pixel, row-major."""
+        check(lib().crt_lens_features_async(self._h, device, C.byref(cam), C.byref(lens), C.c_void_p(feat_ptr or None),
+                                            C.c_void_p(stream)), "crt_lens_features_async")
+
+    def render_lens_passes(self, cam: Camera, lens: Lens, threshold: Optional[float] = None, min_samples: int = 0,
+                           samples_per_pass: int = 0, params: Optional[DenoiseParams] = None, denoise: bool = False,
+                           callback=None, preview: bool = False, noisy: bool = False, counts: bool = False,
+                           device: int = 0):
+        """Blocking lens render in passes on `device` (crt_render_lens_passes): plain passes, or with
+        `threshold` adaptive ones (render_adaptive's rule); with denoise=True (or `params`) the frame is
+        filtered (a cube map one face at a time). Returns render_denoised's shape: (frame, unfiltered
+        frame or None, samples rendered over all pixels), with counts=True also the blocks' sample
+        counts. The frame is the denoised one with denoise, else the unfiltered one (noisy=True then
+        needs denoise). callback(samples_done, samples_total, active_blocks, total_blocks, noisy,
+        frame) runs after every pass; a true return stops the render. preview=True (needs
+        `threshold`; min_samples >= the job's samples renders plain passes) hands every call the
+        frames of the state so far (views of the returned arrays), else both are None."""
+        denoise = denoise or params is not None
+        if preview and threshold is None:
+            raise CrtError("render_lens_passes: preview needs an adaptive render (threshold; min_samples >= the job's "
+                           "samples renders plain passes)")
+        if noisy and not denoise:
+            raise CrtError("render_lens_passes: noisy=True needs denoise (without it the frame is the unfiltered one)")
+        out = np.empty((cam.image_h, cam.image_w, 3), np.float64)
+        raw = np.empty_like(out) if noisy else None
+        prm = (params if params is not None else denoise_params()) if denoise else None
+        ad = None
+        if threshold is not None:
+            ad = _capi.AdaptiveParams(threshold, min_samples, samples_per_pass,
+                                      _capi.CRT_PROGRESS_PREVIEW if preview else 0, 0)
+        elif samples_per_pass or min_samples:
+            raise CrtError("render_lens_passes: samples_per_pass and min_samples need `threshold`")
+        blocks = np.zeros(((cam.image_h + 3) // 4, (cam.image_w + 15) // 16), np.uint32)
+        rendered = C.c_uint64(0)
+        raised = []
+
+        def trampoline(_user, done, total, active, nblocks, h_noisy, h_rgb):
+            try:
+                return 1 if callback(done, total, active, nblocks, raw if h_noisy else None, out if h_rgb else None) else 0
+            except BaseException as e:  # not through the C frames: stop, raise after the call
+                raised.append(e)
+                return 1
+
+        fn = _capi.DENOISED_FN(trampoline) if callback is not None else _capi.DENOISED_FN()
+        rc = lib().crt_render_lens_passes(self._h, device, C.byref(cam), C.byref(lens),
+                                          C.byref(ad) if ad is not None else None,
+                                          C.byref(prm) if prm is not None else None, fn, None,
+                                          raw.ctypes.data if noisy else None, out.ctypes.data, blocks.ctypes.data,
+                                          C.byref(rendered))
+        if raised:
+            raise raised[0]
+        check(rc, "crt_render_lens_passes")
+        return (out, raw, int(rendered.value), blocks) if counts else (out, raw, int(rendered.value))
+
+
+def __getattr__(name):
+    # LensRender lives in lens_passes.py, which imports this module: resolved on first use
+    if name == "LensRender":
+        from .lens_passes import LensRender
+        return LensRender
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

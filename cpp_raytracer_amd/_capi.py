@@ -230,6 +230,12 @@ EXPORTS = {
                                       C.c_void_p]),
     "crt_render_lens_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), C.c_void_p, C.c_void_p]),
     "crt_render_lens": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), C.c_void_p]),
+    "crt_render_lens_pass_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), C.c_uint32, C.c_uint32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "crt_lens_centre_rays_async": (C.c_int, [C.c_int, P(Camera), P(Lens), C.c_void_p, C.c_void_p]),
+    "crt_lens_features_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), C.c_void_p, C.c_void_p]),
+    "crt_render_lens_passes": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), P(AdaptiveParams), P(DenoiseParams),
+                                         DENOISED_FN, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint64)]),
     "crt_ppm_values": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "crt_ppm_write": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "crt_render_guard": (C.c_int, [C.c_void_p, C.c_int, P(C.c_uint64), C.c_int]),

@@ -1,6 +1,6 @@
 // The blocking render drivers: crt_render / crt_render_ppm (render_multi_impl),
-// crt_render_progressive, crt_render_adaptive, crt_render_denoised and
-// crt_render_denoised_devices. Host code only: no kernel
+// crt_render_progressive, crt_render_adaptive, crt_render_denoised,
+// crt_render_denoised_devices and crt_render_lens_passes. Host code only: no kernel
 // is defined here; the drivers go through the device_* functions of crt_device.hip and
 // crt_denoise.hip. What the drivers share is defined once, above them: the device set with its
 // concurrent upload, the per-device lane, the gather, the adaptive step and the block counts.
@@ -757,6 +757,91 @@ int render_denoised_devices(crt_scene* s, const crt_camera* cam, int num_devices
     } else if (rc == CRT_OK) {
         rendered = static_cast<uint64_t>(done) * px;
         if (h_block_samples) std::fill(h_block_samples, h_block_samples + total_blocks, done);
+    }
+    if (samples_rendered) *samples_rendered = rendered;
+    return rc;
+}
+
+// crt_render_lens_passes: render_adaptive's loop on one device and one stream, over the whole frame,
+// with the lens pass (crt_lens.hip) in place of the masked pass; the update, the variance and the
+// filter are the reference camera's, unchanged. Every pass writes the lane's frame (a skipped block's
+// pixels included), so the frame is current whenever the loop ends. With `denoise` the features are
+// taken once, before the first pass, and a CUBE frame is filtered one face at a time.
+int render_lens_passes(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens,
+                       const crt_adaptive_params* adaptive, const crt_denoise_params* denoise, crt_denoised_fn fn,
+                       void* user, double* h_noisy, double* h_rgb, uint32_t* h_block_samples, uint64_t* samples_rendered) {
+    const std::string who = "lens passes";
+    int rc = device_upload(s, device);
+    if (rc) return rc;
+    DeviceGuard g(device);
+    const uint32_t N = cam->samples_per_pixel, W = cam->image_w, H = cam->image_h;
+    const uint64_t per_pass = pass_len(N, sample_chunk_len(N), adaptive ? adaptive->samples_per_pass : 0);
+    const bool want_preview = adaptive && (adaptive->flags & CRT_PROGRESS_PREVIEW) != 0 && fn;
+    Lane l;  // the whole frame: no tiling
+    l.rows = H;
+    l.nblk = static_cast<uint32_t>(crt_block_count(W, H));
+    const size_t px = l.px = static_cast<size_t>(W) * H;
+    double *var = nullptr, *out = nullptr;
+    crt_feature* feat = nullptr;
+    l.open(device);
+    l.alloc(l.sum, px * 3 * sizeof(double));
+    l.alloc(l.noise, px * 2 * sizeof(double));
+    l.alloc(l.rgb, px * 3 * sizeof(double));
+    if (denoise) {
+        l.alloc(var, px * sizeof(double));
+        l.alloc(out, px * 3 * sizeof(double));
+        l.alloc(feat, px * sizeof(crt_feature));
+    }
+    if (adaptive) {
+        l.alloc(l.blocks, l.nblk * sizeof(uint32_t));
+        l.ok = l.ok && hipMemsetAsync(l.blocks, 0, l.nblk * sizeof(uint32_t), l.stream) == hipSuccess;
+    }
+    if (!l.ok) return setup_failed(who, l);
+    if (denoise) rc = device_lens_features(s, device, cam, lens, feat, l.stream);
+    // the frames of the state after `done` samples on the host when it returns
+    auto frames = [&](uint32_t done) -> int {
+        const double* final_rgb = l.rgb;
+        if (denoise) {
+            int r = device_pixel_variance(device, cam, nullptr, l.noise, l.blocks, done, var, l.stream);
+            const uint32_t faces = lens->kind == CRT_LENS_CUBE ? 6 : 1, fh = H / faces;
+            const size_t fpx = static_cast<size_t>(W) * fh;
+            for (uint32_t f = 0; f < faces && r == CRT_OK; ++f)
+                r = device_denoise(device, W, fh, l.rgb + f * fpx * 3, var + f * fpx, feat + f * fpx, denoise,
+                                   out + f * fpx * 3, nullptr, l.stream);
+            if (r) return r;
+            final_rgb = out;
+        }
+        hipError_t e = hipMemcpyAsync(h_rgb, final_rgb, px * 3 * sizeof(double), hipMemcpyDeviceToHost, l.stream);
+        if (e == hipSuccess && h_noisy) e = hipMemcpyAsync(h_noisy, l.rgb, px * 3 * sizeof(double), hipMemcpyDeviceToHost, l.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(l.stream);
+        if (e != hipSuccess) return fail(CRT_E_HIP, who + ": " + hipGetErrorString(e));
+        return CRT_OK;
+    };
+    uint32_t done = 0, active = l.nblk;
+    bool have_frames = false;
+    while (rc == CRT_OK && done < N) {
+        const uint32_t count = static_cast<uint32_t>(std::min<uint64_t>(per_pass, N - done));
+        rc = device_render_lens_pass(s, device, cam, lens, done, count, l.sum, l.noise, l.rgb, l.blocks, l.stream);
+        if (rc != CRT_OK) break;
+        done += count;
+        if (adaptive)
+            rc = device_adaptive_update(device, cam, nullptr, l.noise, l.blocks, done, adaptive->threshold,
+                                        adaptive->min_samples, &active, l.stream);
+        else
+            active = done < N ? l.nblk : 0;
+        have_frames = want_preview;
+        if (rc == CRT_OK) rc = have_frames ? frames(done) : sync_lane(l);
+        if (rc != CRT_OK) break;
+        if (fn && fn(user, done, N, active, l.nblk, have_frames ? h_noisy : nullptr, have_frames ? h_rgb : nullptr) != 0) break;
+        if (active == 0) break;
+    }
+    if (rc == CRT_OK && !have_frames) rc = frames(done);
+    uint64_t rendered = 0;
+    if (rc == CRT_OK && adaptive) {
+        rc = block_samples(who, &l, 1, W, true, h_block_samples, &rendered);
+    } else if (rc == CRT_OK) {
+        rendered = static_cast<uint64_t>(done) * px;
+        if (h_block_samples) std::fill(h_block_samples, h_block_samples + l.nblk, done);
     }
     if (samples_rendered) *samples_rendered = rendered;
     return rc;

@@ -1725,6 +1725,77 @@ int crt_render_lens(crt_scene* s, int device, const crt_camera* cam, const crt_l
     return device_render_lens_host(s, device, cam, lens, rgb);
 }
 
+// ---- lens renders in passes: check_lens's rules, then the pass's (check_pass), the adaptive
+// parameters' and the denoiser's, all before any device work ------------------------------------
+int crt_render_lens_pass_async(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens,
+                               uint32_t first_sample, uint32_t num_samples, double* d_sum, double* d_noise,
+                               double* d_rgb, uint32_t* d_blocks, uint32_t active_hint, void* stream) {
+    clear_error();
+    const char* fn = "crt_render_lens_pass_async";
+    int rc = check_lens(std::string(fn) + ": ", true, s, cam, lens, true);
+    if (rc) return rc;
+    rc = check_pass(fn, s, cam, first_sample, num_samples, d_sum);
+    if (rc) return rc;
+    if (static_cast<uint64_t>(cam->image_w) * cam->image_h > 0x7fffffffull)
+        return fail(CRT_E_INVALID, std::string(fn) + ": frame has more than 2^31-1 pixels");
+    if (d_blocks && first_sample + num_samples >= CRT_BLOCK_STOPPED)
+        return fail(CRT_E_INVALID, std::string(fn) + ": sample counts must stay below 2^31");
+    (void)active_hint;  // the active pixels are counted on the device: nothing is sized by the hint
+    return device_render_lens_pass(s, device, cam, lens, first_sample, num_samples, d_sum, d_noise, d_rgb, d_blocks, stream);
+}
+
+int crt_lens_centre_rays_async(int device, const crt_camera* cam, const crt_lens* lens, double* d_rays, void* stream) {
+    clear_error();
+    const std::string who = "crt_lens_centre_rays_async: ";
+    const int rc = check_lens(who, false, nullptr, cam, lens, false);
+    if (rc) return rc;
+    if (!d_rays) return fail(CRT_E_INVALID, who + "d_rays is null (the output is required)");
+    if (static_cast<uint64_t>(cam->image_w) * cam->image_h > 0x7fffffffull)
+        return fail(CRT_E_INVALID, who + "frame has more than 2^31-1 pixels");
+    return device_lens_centre_rays(device, cam, lens, d_rays, stream);
+}
+
+int crt_lens_features_async(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens,
+                            crt_feature* d_feat, void* stream) {
+    clear_error();
+    const std::string who = "crt_lens_features_async: ";
+    const int rc = check_lens(who, true, s, cam, lens, false);
+    if (rc) return rc;
+    if (!d_feat) return fail(CRT_E_INVALID, who + "d_feat is null (the output is required)");
+    if (static_cast<uint64_t>(cam->image_w) * cam->image_h > 0x7fffffffull)
+        return fail(CRT_E_INVALID, who + "frame has more than 2^31-1 pixels");
+    return device_lens_features(s, device, cam, lens, d_feat, stream);
+}
+
+int crt_render_lens_passes(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens,
+                           const crt_adaptive_params* adaptive, const crt_denoise_params* denoise, crt_denoised_fn fn,
+                           void* user, double* h_noisy, double* h_rgb, uint32_t* h_block_samples,
+                           uint64_t* samples_rendered) {
+    clear_error();
+    if (samples_rendered) *samples_rendered = 0;
+    const std::string who = "crt_render_lens_passes: ";
+    int rc = check_lens(who, true, s, cam, lens, true);
+    if (rc) return rc;
+    if (!h_rgb) return fail(CRT_E_INVALID, who + "h_rgb is null (the output is required)");
+    if (denoise) {
+        rc = check_denoise_params("crt_render_lens_passes", denoise);
+        if (rc) return rc;
+    } else if (h_noisy) {
+        return fail(CRT_E_INVALID, who + "h_noisy must be null without denoise (h_rgb is the unfiltered frame)");
+    }
+    if (adaptive) {
+        if (adaptive->flags & ~CRT_PROGRESS_PREVIEW)
+            return fail(CRT_E_INVALID, who + "unknown adaptive flags (CRT_PROGRESS_PREVIEW or 0)");
+        if (adaptive->reserved != 0) return fail(CRT_E_INVALID, who + "adaptive reserved must be 0");
+        if (!(adaptive->threshold >= 0) || !std::isfinite(adaptive->threshold))
+            return fail(CRT_E_INVALID, who + "threshold must be finite and >= 0");
+    }
+    if (static_cast<uint64_t>(cam->image_w) * cam->image_h > 0x7fffffffull)
+        return fail(CRT_E_INVALID, who + "frame has more than 2^31-1 pixels");
+    return render_lens_passes(s, device, cam, lens, adaptive, denoise, fn, user, h_noisy, h_rgb, h_block_samples,
+                              samples_rendered);
+}
+
 int crt_closest_hits(crt_scene* s, int device, const double* rays, size_t n, double t_min,
                      double t_max, crt_hit* out) {
     clear_error();

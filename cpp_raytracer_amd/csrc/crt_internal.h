@@ -439,6 +439,14 @@ int device_lens_rays(int device, const crt_camera* cam, const crt_lens* lens, ui
 int device_render_lens(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, double* d_rgb,
                        void* stream);
 int device_render_lens_host(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, double* rgb);
+// lens renders in passes: one pass into running sums (blocks != null: the blocks at `first` only; it
+// then waits for the stream once), the rays through the pixel centres, and the first-hit features
+int device_render_lens_pass(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, uint32_t first,
+                            uint32_t count, double* d_sum, double* d_noise, double* d_rgb, uint32_t* d_blocks,
+                            void* stream);
+int device_lens_centre_rays(int device, const crt_camera* cam, const crt_lens* lens, double* d_rays, void* stream);
+int device_lens_features(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, crt_feature* d_feat,
+                         void* stream);
 // denoising: first-hit features and the per-pixel variance (crt_device.hip), the filter
 // (crt_denoise.hip); the callers check the arguments
 int device_render_features(const crt_scene* s, int device, const crt_camera* cam, const crt_tiling* t,
@@ -510,4 +518,7 @@ int render_denoised(crt_scene* s, int device, const crt_camera* cam, const crt_a
 int render_denoised_devices(crt_scene* s, const crt_camera* cam, int num_devices, const crt_adaptive_params* adaptive,
                             const crt_denoise_params* denoise, crt_denoised_fn fn, void* user, double* h_noisy,
                             double* h_rgb, uint32_t* h_block_samples, uint64_t* samples_rendered);
+int render_lens_passes(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens,
+                       const crt_adaptive_params* adaptive, const crt_denoise_params* denoise, crt_denoised_fn fn,
+                       void* user, double* h_noisy, double* h_rgb, uint32_t* h_block_samples, uint64_t* samples_rendered);
 }  // namespace crt

@@ -390,6 +390,70 @@ class Camera {
         return img;
     }
 
+    // render_scene_lens in passes (crt_render_lens_passes): the callback ticks the bar and asks on_pass
+    struct LensPassCtx {
+        ProgressBar<>* bar;
+        const std::function<bool(size_t, size_t)>* on_pass;
+    };
+    static int lens_pass(void* user, uint32_t done, uint32_t total, uint32_t, uint32_t, const double*, const double*) {
+        auto* ctx = static_cast<LensPassCtx*>(user);
+        if (ctx->bar) ctx->bar->complete_iteration();
+        return (ctx->on_pass && *ctx->on_pass && !(*ctx->on_pass)(done, total)) ? 1 : 0;
+    }
+
+    // progressive: plain passes of samples_per_pass samples (no block ever stops); else every sample, or
+    // with adaptive_threshold >= 0 an adaptive render, then the denoiser (a cube map one face at a time)
+    Image render_scene_lens_passes(const crt_api::GpuScene& g, const Lens& lens, bool progressive, size_t samples_per_pass,
+                                   const std::function<bool(size_t, size_t)>& on_pass, const DenoiseOptions& opt,
+                                   double adaptive_threshold) {
+        init();
+        resolved.base_seed = SeedSeqGenerator::get_instance().next_seed();
+        const crt_lens l = lens.as_crt();
+        const size_t chunk = crt_sample_chunk_len(resolved.samples_per_pixel);
+        if (samples_per_pass > UINT32_MAX) samples_per_pass = UINT32_MAX;
+        size_t per_pass = samples_per_pass ? samples_per_pass : std::max<size_t>(1, samples_per_pixel / 10);
+        per_pass = (per_pass + chunk - 1) / chunk * chunk;
+        const bool adaptive = !progressive && adaptive_threshold >= 0;
+        crt_adaptive_params ap{};
+        ap.threshold = adaptive ? adaptive_threshold : 0;
+        // progressive: min_samples >= samples_per_pixel never stops a block; adaptive: render_adaptive's
+        // floor of two passes
+        ap.min_samples = adaptive ? static_cast<uint32_t>(std::min<size_t>(2 * per_pass, UINT32_MAX)) : UINT32_MAX;
+        ap.samples_per_pass = static_cast<uint32_t>(samples_per_pass);
+        crt_denoise_params dp{};
+        dp.iterations = opt.iterations;
+        dp.normal_squarings = opt.normal_squarings;
+        dp.sigma_l = opt.sigma_l;
+        dp.sigma_p = opt.sigma_p;
+        std::vector<double> rgb(image_w * image_h * 3);
+        uint64_t rendered = 0;
+        int rc;
+        if (progressive) {
+            ProgressBar<> bar((samples_per_pixel + per_pass - 1) / per_pass,
+                              "Rendering " + std::to_string(image_w) + " x " + std::to_string(image_h) + " lens image (" +
+                                  std::to_string(samples_per_pixel) + " spp) in passes");
+            LensPassCtx ctx{&bar, &on_pass};
+            rc = crt_render_lens_passes(g.get(), 0, &resolved, &l, &ap, nullptr, lens_pass, &ctx, nullptr, rgb.data(),
+                                        nullptr, &rendered);
+        } else {
+            std::cout << "Rendering " << image_w << " x " << image_h << " lens image (" << (adaptive ? "up to " : "")
+                      << samples_per_pixel << " spp" << (adaptive ? ", adaptive" : "") << ", denoised)" << std::endl;
+            rc = crt_render_lens_passes(g.get(), 0, &resolved, &l, adaptive ? &ap : nullptr, &dp, nullptr, nullptr, nullptr,
+                                        rgb.data(), nullptr, &rendered);
+        }
+        if (rc) crt_api::die("Camera::render_lens passes");
+        const double mean = static_cast<double>(rendered) / static_cast<double>(image_w * image_h);
+        if (!progressive || mean < static_cast<double>(samples_per_pixel))
+            std::cout << "Rendered " << mean << " spp on average (of " << samples_per_pixel << ")\n" << std::endl;
+        auto img = Image::with_dimensions(image_w, image_h);
+        for (size_t r = 0; r < image_h; ++r)
+            for (size_t c = 0; c < image_w; ++c) {
+                const double* p = &rgb[(r * image_w + c) * 3];
+                img[r][c] = RGB::from_mag(p[0], p[1], p[2]);
+            }
+        return img;
+    }
+
 public:
     // Extension (not in the reference): render (adaptive_threshold < 0: every sample) or
     // render_adaptive (blocks stop at that threshold, default pass length and sample floor), then
@@ -538,6 +602,45 @@ public:
         } else {
             crt_api::GpuScene s(world, 32, 12, true);
             return render_scene_lens(s, lens);
+        }
+    }
+
+    // Extension (not in the reference): render_lens in passes of samples_per_pass samples per pixel (0 = a
+    // tenth of them; rounded up to whole sample chunks) over crt_render_lens_passes, ticking a ProgressBar
+    // once a pass. on_pass(samples done, samples in all) returning false stops the render and returns
+    // the image of the samples rendered so far. Rendered to the end, the image is render_lens' bit for bit.
+    Image render_lens_progressive(const BVH& world, const Lens& lens, size_t samples_per_pass = 0,
+                                  std::function<bool(size_t done, size_t total)> on_pass = {}) {
+        return render_scene_lens_passes(world.gpu_scene(), lens, true, samples_per_pass, on_pass, {}, -1);
+    }
+    template <typename T>
+    requires std::is_base_of_v<Hittable, T>
+    Image render_lens_progressive(const T& world, const Lens& lens, size_t samples_per_pass = 0,
+                                  std::function<bool(size_t done, size_t total)> on_pass = {}) {
+        if constexpr (std::is_same_v<T, Scene>) {
+            return render_lens_progressive(BVH(world), lens, samples_per_pass, on_pass);
+        } else {
+            crt_api::GpuScene s(world, 32, 12, true);
+            return render_scene_lens_passes(s, lens, true, samples_per_pass, on_pass, {}, -1);
+        }
+    }
+
+    // Extension (not in the reference): render_lens (adaptive_threshold < 0: every sample) or an adaptive
+    // lens render (blocks stop at that threshold, render_adaptive's pass length and sample floor), then
+    // render_denoised's filter guided by the first hits seen through the lens; a cube map is filtered one
+    // face at a time. With Lens::pinhole() the picture is render_denoised's on one GPU. Panorama taps do not
+    // wrap at the left-right seam.
+    Image render_lens_denoised(const BVH& world, const Lens& lens, DenoiseOptions options = {}, double adaptive_threshold = -1) {
+        return render_scene_lens_passes(world.gpu_scene(), lens, false, 0, {}, options, adaptive_threshold);
+    }
+    template <typename T>
+    requires std::is_base_of_v<Hittable, T>
+    Image render_lens_denoised(const T& world, const Lens& lens, DenoiseOptions options = {}, double adaptive_threshold = -1) {
+        if constexpr (std::is_same_v<T, Scene>) {
+            return render_lens_denoised(BVH(world), lens, options, adaptive_threshold);
+        } else {
+            crt_api::GpuScene s(world, 32, 12, true);
+            return render_scene_lens_passes(s, lens, false, 0, {}, options, adaptive_threshold);
         }
     }
 

@@ -807,6 +807,97 @@ int crt_render_lens_async(const crt_scene* scene, int device, const crt_camera* 
  * (the C++ drop-in's Camera::render_lens). */
 int crt_render_lens(crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens, double* rgb);
 
+/* ---- lens renders in passes ------------------------------------------------------------------
+ * A lens render cut into passes, with the state the camera-agnostic calls read: crt_noise_estimate,
+ * crt_adaptive_update, crt_pixel_variance_async and crt_denoise_async take d_sum, d_noise, block
+ * words and crt_feature records from these calls exactly as from the reference camera's.
+ *
+ * One pass: samples [first_sample, first_sample + num_samples) of a job of cam->samples_per_pixel
+ * samples (that total fixes L = crt_sample_chunk_len(spp) and the seeds), over the whole frame; no
+ * tiling. d_sum (image_h * image_w * 3), d_noise (image_h * image_w * 2, or NULL) and d_rgb (as
+ * d_sum, or NULL) are DEVICE buffers of the whole frame, row-major.
+ * Rules: crt_render_lens_async's on scene, cam and lens, then crt_render_pass_async's on
+ * first_sample, num_samples and d_sum; at most 2^31 - 1 pixels; with d_blocks, first_sample +
+ * num_samples < 2^31. All are checked before any device work (CRT_E_INVALID, the message names the
+ * rule).
+ * Paths: the ray and state of sample s of pixel p are crt_lens_rays_async's; L_s is
+ * crt_radiance_async's output for them, as in crt_render_lens_async.
+ * Accumulation, per pixel and channel, crt_render_pass_async's: chunk c of the pass is the sum of
+ * its L_s (s = first_sample + c * L .. min(first_sample + num_samples, first_sample + (c + 1) * L) - 1)
+ * in sample order, starting from 0.0. A pass with first_sample == 0 starts the running sum from
+ * chunk 0's sum (not from 0.0 plus it) and overwrites d_sum and d_noise; any other pass starts from
+ * the stored d_sum. The chunk sums are added in chunk order. With d_noise: for every chunk of the
+ * pass that has L samples, in chunk order, y = (r + g) + b of the chunk's sum, t = t + y and
+ * q = q + y * y, where t and q start from 0 in a pass with first_sample == 0 and from the stored
+ * values otherwise; a ragged last chunk is left out. With d_rgb: the frame so far, sum *
+ * (1 / (double)(first_sample + num_samples)). No floating-point atomics are used; the bits depend
+ * on neither the grid nor lens->batch_pixels nor the radiance route (CRT_RADIANCE_PLAIN in
+ * lens->flags) nor active_hint. Passes issued once each, in increasing order, end in
+ * crt_render_lens_async's frame bit for bit; with kind PINHOLE every pass leaves
+ * crt_render_pass_async's d_sum, d_noise and d_rgb.
+ * d_blocks (DEVICE, crt_block_count(image_w, image_h) words, or NULL: every pixel) makes it a masked
+ * pass over the frame's 16 x 4 blocks: only the blocks with d_blocks[b] == first_sample are
+ * generated, traced and accumulated, and their words become first_sample + num_samples. A skipped
+ * block gets what crt_render_pass_masked_async gives a skipped block: with first_sample > 0, d_sum
+ * and d_noise are left alone and d_rgb gets sum * (1 / (double)n) for the block's own count n (0
+ * when n = 0); with first_sample == 0 its pixels' d_sum, d_noise and d_rgb are written 0.
+ * Stopped blocks cost no rays: the active blocks' pixels are compacted into a list on the device
+ * (its order affects no bit) and only they are generated and traced. The radiance query needs its
+ * record count on the host, so WITH d_blocks THE CALL WAITS FOR `stream` ONCE to read the number of
+ * active pixels (4 bytes); active_hint is accepted for symmetry with crt_render_pass_masked_async
+ * and sizes nothing. Without d_blocks the call only enqueues on `stream`.
+ * Batches: whole pixels, lens->batch_pixels of them (0: as crt_render_lens_async's, for num_samples
+ * records a pixel), each generated, traced, accumulated and freed in order; scratch from the pass
+ * pool. max_depth == 0: every L_s is +0; the pass makes the additions above with +0 and launches
+ * no trace. The scene must be resident on `device` (CRT_E_NOT_UPLOADED). */
+int crt_render_lens_pass_async(const crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens,
+                               uint32_t first_sample, uint32_t num_samples, double* d_sum, double* d_noise,
+                               double* d_rgb, uint32_t* d_blocks, uint32_t active_hint, void* stream);
+
+/* The ray through the centre of every pixel, no draws: d_rays (DEVICE, image_h * image_w * 6
+ * doubles) record row * image_w + col = {o, d}.
+ *   PINHOLE: crt_render_features_async's ray: centre = (pixel00 + pixel_delta_y * (double)row) +
+ *     pixel_delta_x * (double)col, o = origin, d = centre - origin (the random terms left out, not
+ *     multiplied by zero).
+ *   Every other kind: crt_lens_rays_async's expressions with fx = (double)col + 0.5 and
+ *     fy = (double)row_in_face + 0.5 (ux and uy left out), a and b and the kind's o and d unchanged.
+ * crt_lens_rays_async's rules on cam and lens; d_rays not NULL; at most 2^31 - 1 pixels. Enqueued. */
+int crt_lens_centre_rays_async(int device, const crt_camera* cam, const crt_lens* lens, double* d_rays, void* stream);
+
+/* First-hit features through a lens: d_feat (DEVICE, image_h * image_w records, row-major). The
+ * centre ray of crt_lens_centre_rays_async is traced over (cam->t_min, +inf) as crt_trace_async
+ * traces it; t, point, normal, prim and material are the crt_hit's, albedo and the miss record are as
+ * crt_feature defines them. For PINHOLE the records equal crt_render_features_async's byte for byte.
+ * ORTHOGRAPHIC's d = forward is not normalised, so its t is in units of |forward|. The parity guard
+ * is not touched. Rays and hits (120 bytes a pixel) come from the pass pool; the first closest-hit
+ * query for a scene and device uploads a table, blocking, after that the call only enqueues. */
+int crt_lens_features_async(const crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens,
+                            crt_feature* d_feat, void* stream);
+
+/* Blocking lens render in passes on one device: crt_render_adaptive's loop with the lens pass in
+ * place of the masked pass. Uploads the scene if it is not resident.
+ *   adaptive == NULL: plain passes of a tenth of the job each (at least one chunk), no previews; fn
+ *     gets active_blocks = total_blocks while samples remain, 0 after the last pass.
+ *   adaptive != NULL: crt_render_adaptive's rules for *adaptive (flags 0 or CRT_PROGRESS_PREVIEW);
+ *     after every masked pass crt_adaptive_update, unchanged.
+ *   The loop ends when no block is active, all samples are done, or fn (may be NULL) returns non-zero.
+ *   denoise != NULL (crt_denoise_async's rules): crt_lens_features_async once, then
+ *     crt_pixel_variance_async (with the block words when adaptive) and crt_denoise_async, unchanged;
+ *     h_rgb is the denoised frame and h_noisy (HOST, or NULL) the unfiltered one. A CUBE frame's six
+ *     faces are contiguous image_w x image_w sub-frames and are filtered one at a time (six
+ *     crt_denoise_async calls), so no tap crosses from a face into an unrelated one.
+ *   denoise == NULL: h_rgb is the unfiltered frame: every pixel's sum times 1 / its block's own
+ *     count; h_noisy must be NULL (CRT_E_INVALID).
+ *   With CRT_PROGRESS_PREVIEW and fn the frames are produced (and filtered) before every call of fn,
+ *   which receives the caller's h_noisy and h_rgb; else once at the end, and fn receives NULL for both.
+ *   h_block_samples (or NULL) and *samples_rendered (or NULL) as crt_render_denoised_devices'.
+ * Limits: EQUIRECT taps do not wrap at the +-extent_x seam; ORTHOGRAPHIC's t is in units of |forward|.
+ * Every rule is checked before any device work. */
+int crt_render_lens_passes(crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens,
+                           const crt_adaptive_params* adaptive, const crt_denoise_params* denoise,
+                           crt_denoised_fn fn, void* user, double* h_noisy, double* h_rgb,
+                           uint32_t* h_block_samples, uint64_t* samples_rendered);
+
 /* The integers Image::send_as_ppm prints (image.h:38-56; RGB::as_string rgb.h:99-115 with its
  * defaults: Reinhard tone map by luminance, gamma 2, static_cast<int>(255.999999 * v)) for the
  * n-pixel frame d_rgb (device memory on `device`, row-major RGB f64, e.g. crt_render_async's
