@@ -325,6 +325,14 @@ class GpuScene:
               "crt_scene_export_bvh")
         return nodes, order
 
+    def launch_plan(self, kernel="render") -> _capi.LaunchPlan:
+        """What a launch of `kernel` ("render", "trace", "radiance") would decide for this scene: class,
+        entry width, instance and LDS layout (crt_launch_plan). Host only; reads the CRT_* switches now."""
+        k = {"render": _capi.CRT_PLAN_RENDER, "trace": _capi.CRT_PLAN_TRACE, "radiance": _capi.CRT_PLAN_RADIANCE}.get(kernel, kernel)
+        p = _capi.LaunchPlan()
+        check(lib().crt_launch_plan(self._h, int(k), C.byref(p)), "crt_launch_plan")
+        return p
+
     def upload(self, device: int = 0) -> None:
         check(lib().crt_scene_upload(self._h, device), f"crt_scene_upload(device={device})")
 

@@ -136,6 +136,24 @@ class Lens(C.Structure):
 CRT_LENS_PINHOLE, CRT_LENS_ORTHOGRAPHIC, CRT_LENS_EQUIRECT, CRT_LENS_FISHEYE, CRT_LENS_CUBE = 0, 1, 2, 3, 4
 assert C.sizeof(Lens) == 128
 
+
+class LaunchPlan(C.Structure):
+    _fields_ = ([(n, C.c_uint32) for n in ("kernel", "klass", "entry_bytes", "five_waves", "prim_mode", "plain_route",
+                                           "depth", "block")] + [("num_nodes", C.c_uint64)] +
+                [(n, C.c_uint32) for n in (
+                    "stack_bytes", "level", "sentinel", "hbm_stack_levels",
+                    "lds_nodes", "lds_refs", "lds_spheres", "lds_quads", "lds_quadf", "lds_sph64", "lds_stack",
+                    "bytes_nodes", "bytes_refs", "bytes_spheres", "bytes_quads", "bytes_quadf", "bytes_sph64",
+                    "ntop", "all_nodes", "lds_cam", "lds_acc", "lds_inv64", "bytes_cam", "bytes_acc", "bytes_inv64",
+                    "total_lds", "budget", "spheres_f32", "quads_f32", "quads_flat", "f32_ok")] +
+                [("reserved", C.c_uint32 * 9)])
+
+
+CRT_PLAN_RENDER, CRT_PLAN_TRACE, CRT_PLAN_RADIANCE = 0, 1, 2
+CRT_PLAN_LDS_SCENE, CRT_PLAN_LDS_STACK, CRT_PLAN_HBM_STACK = 0, 1, 2
+CRT_PLAN_ABSENT = 0xFFFFFFFF
+assert C.sizeof(LaunchPlan) == 200
+
 # numpy views of the same records (for bulk scene I/O)
 MATERIAL_DTYPE = np.dtype([("kind", "<u4"), ("reserved", "<u4"), ("color", "<f8", 3), ("param", "<f8")])
 OBJECT_DTYPE = np.dtype([("kind", "<u4"), ("material", "<u4"), ("v", "<f8", 9)])
@@ -239,6 +257,7 @@ EXPORTS = {
     "crt_ppm_values": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "crt_ppm_write": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "crt_render_guard": (C.c_int, [C.c_void_p, C.c_int, P(C.c_uint64), C.c_int]),
+    "crt_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, P(LaunchPlan)]),
 }
 
 

@@ -1283,7 +1283,7 @@ __device__ __forceinline__ uint32_t vsel(uint64_t m, uint32_t a, uint32_t b) {
 }
 
 // The step's two f32 nodes: f (the first) and g = f ^ 32, read from the LDS treelet or from HBM
-// (the treelet holds whole sibling pairs, dispatch_render, so f and g are on the same side),
+// (the treelet holds whole sibling pairs, render_layout, so f and g are on the same side),
 // both sides in flight together as in fetch_nodef.
 template <bool TOP>
 __device__ __forceinline__ void fetch_two(const SceneView& S, uint32_t f, uint32_t g, Uvec4& a0, Uvec4& a1, Uvec4& b0,
@@ -1822,7 +1822,7 @@ __device__ __forceinline__ void set_prio() {
 // 2 parallelogram-only scenes of axis-aligned parallelograms (LDS scenes: the flat-box filter
 // only, no sphere paths)
 // W5: 5 waves per SIMD (96 VGPRs, ~40-48 of them spilled), launched for sphere-only and
-// flat-parallelogram LDS scenes whose LDS copy leaves room for five blocks per CU (dispatch_render)
+// flat-parallelogram LDS scenes whose LDS copy leaves room for five blocks per CU (render_layout)
 // MASK: the masked pass of an adaptive render (crt_render_pass_masked_async). The queues run over
 // the band's active tiles only: active[0] = their number, active[1 + i] = the band tile of list
 // entry i, in tile-major order (active_list_kernel). A separate instance: the unmasked instances
@@ -3290,28 +3290,46 @@ static void stage_image(crt_scene* s) {
     s->staged = true;
 }
 
+// The f32 flags of a scene copy: the staged image's, less what the switches turn off (read when the
+// copy is bound, device_bind_copy, and by crt_launch_plan when it is asked)
+struct CopyFlags {
+    bool f32_ok, spheres_f32_ok, quads_f32_ok, quads_flat_ok;
+};
+static CopyFlags copy_flags(const crt_scene* s) {
+    CopyFlags f;
+    f.f32_ok = s->image_f32_ok && std::getenv("CRT_F64_NODES") == nullptr;
+    f.spheres_f32_ok = s->image_spheres_f32_ok && std::getenv("CRT_F64_SPHERES") == nullptr;
+    f.quads_f32_ok = s->image_quads_f32_ok && std::getenv("CRT_F64_QUADS") == nullptr;
+    // CRT_GENERIC_QUADS=1: the generic parallelogram filter even for axis-aligned ones
+    f.quads_flat_ok = s->image_quads_flat_ok && std::getenv("CRT_GENERIC_QUADS") == nullptr;
+    return f;
+}
+static CopyFlags flags_of(const DeviceCopy& c) {
+    return CopyFlags{c.f32_ok, c.spheres_f32_ok, c.quads_f32_ok, c.quads_flat_ok};
+}
+
 // The pointers of a scene copy at `base` (device_layout's arrays at their offsets).
 void device_bind_copy(crt_scene* s, int device, void* base, size_t total) {
     size_t off[kArrCount + 1];
     (void)device_layout(s, off);
     DeviceCopy& c = s->dev[device];
+    const CopyFlags f = copy_flags(s);
     char* b = static_cast<char*>(base);
     c.base = base;
     c.bytes = total;
     c.nodes = reinterpret_cast<DevNode*>(b + off[kArrNodes]);
     c.fnodes = reinterpret_cast<DevNodeF*>(b + off[kArrFNodes]);
-    c.f32_ok = s->image_f32_ok && std::getenv("CRT_F64_NODES") == nullptr;
+    c.f32_ok = f.f32_ok;
     c.refs = reinterpret_cast<uint32_t*>(b + off[kArrRefs]);
     c.spheres = reinterpret_cast<DevSphere*>(b + off[kArrSpheres]);
     c.spair = reinterpret_cast<DevSpherePair*>(b + off[kArrSpherePairs]);
-    c.spheres_f32_ok = s->image_spheres_f32_ok && std::getenv("CRT_F64_SPHERES") == nullptr;
+    c.spheres_f32_ok = f.spheres_f32_ok;
     c.sphere_mat = reinterpret_cast<uint32_t*>(b + off[kArrSphereMat]);
     c.quads = reinterpret_cast<DevQuad*>(b + off[kArrQuads]);
     c.quadf = reinterpret_cast<DevQuadF*>(b + off[kArrQuadF]);
-    c.quads_f32_ok = s->image_quads_f32_ok && std::getenv("CRT_F64_QUADS") == nullptr;
+    c.quads_f32_ok = f.quads_f32_ok;
     c.quadbox = reinterpret_cast<DevQuadBox*>(b + off[kArrQuadBox]);
-    // CRT_GENERIC_QUADS=1: the generic parallelogram filter even for axis-aligned ones
-    c.quads_flat_ok = s->image_quads_flat_ok && std::getenv("CRT_GENERIC_QUADS") == nullptr;
+    c.quads_flat_ok = f.quads_flat_ok;
     c.quad_mat = reinterpret_cast<uint32_t*>(b + off[kArrQuadMat]);
     c.mats = reinterpret_cast<DevMaterial*>(b + off[kArrMats]);
     c.sphere_mrec = reinterpret_cast<DevMaterial*>(b + off[kArrSphereMrec]);
@@ -3426,6 +3444,80 @@ constexpr size_t kLdsSceneBudget = 40 * 1024 * dev::kBlock / 256;  // scene + st
 // still fits 40 KB: rtow 40.6 KB, 84.7 vs 85.4 ms with them in HBM / L1 (v12; round 1's layout,
 // with even-aligned filter records to make room, had measured the opposite)
 constexpr size_t kLdsStackBudget = 32 * 1024 * dev::kBlock / 256;
+constexpr size_t kLdsBudget5 = 160 * 1024 * dev::kBlock / (64 * dev::kManyWaves * 4);  // LDS a block at five waves a SIMD
+constexpr size_t kLdsPerBlock = 160 * 1024 * dev::kBlock / (256 * CRT_WAVES_PER_EU);  // LDS per block at the VGPR occupancy
+
+// The class of a launch and what its layout step decided (render_layout, query_layout); the launch
+// steps (dispatch_*) and crt_launch_plan read it.
+enum QueryClass { kQueryLdsScene, kQueryLdsStack, kQueryHbmStack };
+struct Layout {
+    QueryClass cls = kQueryLdsScene;
+    bool w5 = false;         // render: five waves per SIMD
+    size_t lds = 0;          // bytes laid out so far (the launchers add theirs: *_lds_tail)
+    size_t stack_bytes = 0;  // levels 0..depth
+    size_t level = 0;        // one stack level
+    size_t all_nodes = 0;    // the f32 node array
+    size_t budget = 0;       // the budget the class was admitted under
+};
+
+// the instance's primitive mode: sphere-only, general, or (render, LDS scenes) flat parallelograms
+static int render_prim_mode(const dev::Work& W, QueryClass cls) {
+    return W.sphere_only ? 0 : (cls == kQueryLdsScene && W.quads_flat) ? 2 : 1;
+}
+static int query_prim_mode(const dev::Work& W) { return W.sphere_only ? 0 : 1; }
+
+// What a launcher keeps behind the layout's `lds` bytes, for its instance; returns the dynamic LDS
+// the launch requests.
+static size_t render_lds_tail(dev::Work& W, size_t lds, bool gstack, bool lscene, int pm, bool w5) {
+    W.lds_cam = static_cast<uint32_t>(align16(lds));  // the camera copy after the rest
+    lds = W.lds_cam + align16(sizeof(dev::CamView));
+    if (w5 && pm == 0) {  // then the pixel sums (render_kernel: kAccLds)
+        W.lds_acc = static_cast<uint32_t>(align16(lds));
+        lds = W.lds_acc + kAccBytes;
+    }
+    if ((lscene && pm == 2 && w5) || (!lscene && !gstack)) {  // or the rays' f64 1 / d (render_kernel: kInvLds)
+        W.lds_inv64 = static_cast<uint32_t>(align16(lds));
+        lds = W.lds_inv64 + kInvBytes;
+    }
+    return lds;
+}
+static size_t trace_lds_tail(dev::Work& W, size_t lds, bool gstack, bool lscene) {
+    // a treelet alone (HBM stack) that holds the whole node array ends with the sentinel, whose
+    // sibling slot fetch_two reads too (and never tests): keep it inside the request. A cut treelet
+    // is whole pairs, and every other instance has a region behind the nodes.
+    if (gstack && lds % (2 * sizeof(DevNodeF))) lds += sizeof(DevNodeF);
+    if (!lscene && !gstack) {  // the rays' f64 1 / d (query_kernel: kInvLds)
+        W.lds_inv64 = static_cast<uint32_t>(align16(lds));
+        lds = W.lds_inv64 + kInvBytes;
+    }
+    return lds;
+}
+static size_t radiance_lds_tail(dev::Work& W, size_t lds, bool gstack, bool lscene) {
+    W.lds_cam = static_cast<uint32_t>(align16(lds));  // launch_render's place for the camera copy
+    lds = W.lds_cam + align16(sizeof(dev::CamView));
+    if (!lscene && !gstack) {  // the rays' f64 1 / d (radiance_kernel: kInvLds)
+        W.lds_inv64 = static_cast<uint32_t>(align16(lds));
+        lds = W.lds_inv64 + kInvBytes;
+    }
+    return lds;
+}
+// an HBM stack's levels: 0..depth, two guard levels and the level below them
+static size_t gstack_levels(const crt_scene* s) { return static_cast<size_t>(s->depth) + 4; }
+
+// Which instance family a scene gets, from its copy's f32 flags: `f32_ok` = the walk decides in f32,
+// `filters` = the two-pass leaf filters' interval rule holds (t_min >= 0)
+static void class_flags(const crt_scene* s, const CopyFlags& c, bool f32_ok, bool filters, dev::Work& W) {
+    W.f32_ok = f32_ok ? 1u : 0u;
+    W.sphere_only = (s->num_quads == 0 && s->num_spheres != 0) ? 1u : 0u;
+    W.spheres_f32 = (W.sphere_only && c.spheres_f32_ok && filters) ? 1u : 0u;
+    W.quads_f32 = (s->num_spheres == 0 && s->num_quads != 0 && c.quads_f32_ok && filters) ? 1u : 0u;
+    // the flat-box filter is the walk's f32 node test: it needs the walk's f32 range (f32_ok)
+    W.quads_flat = (W.quads_f32 && c.quads_flat_ok && W.f32_ok) ? 1u : 0u;
+    W.exact_slab = (s->exact_slab || std::getenv("CRT_EXACT_SLAB") != nullptr) ? 1u : 0u;
+    W.pair_walk = (CRT_PAIR_WALK && !W.exact_slab && std::getenv("CRT_NO_PAIR_WALK") == nullptr) ? 1u : 0u;
+}
+// every ref fits a u16 stack entry
+static bool u16_entries(const crt_scene* s) { return (s->num_dnodes << kNodeFShift) <= 65536; }
 
 // Partial-sum budget per launch (bytes): the owned frame is rendered in bands whose partial sums
 // fit it (CRT_PARTIAL_MB overrides; tests force many small bands). 4 GiB holds a whole config-2
@@ -3491,16 +3583,7 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
                          const RenderPass* pass) {
     const DeviceCopy& c = s->dev[device];
     dev::Work W = w0;
-    W.lds_cam = static_cast<uint32_t>(align16(lds));  // the camera copy after the rest
-    lds = W.lds_cam + align16(sizeof(dev::CamView));
-    if (W5 && PM == 0) {  // then the pixel sums (render_kernel: kAccLds)
-        W.lds_acc = static_cast<uint32_t>(align16(lds));
-        lds = W.lds_acc + kAccBytes;
-    }
-    if ((LSCENE && PM == 2 && W5) || (!LSCENE && !GSTACK)) {  // or the rays' f64 1 / d (render_kernel: kInvLds)
-        W.lds_inv64 = static_cast<uint32_t>(align16(lds));
-        lds = W.lds_inv64 + kInvBytes;
-    }
+    lds = render_lds_tail(W, lds, GSTACK, LSCENE, PM, W5);
     constexpr int kThreads = dev::kBlock;
     // a masked pass (adaptive sampling) launches the MASK instance over the active tiles' list
     const bool masked = pass && pass->blocks;
@@ -3569,7 +3652,7 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
     if (!count)
         HIP_TRY(scratch(reinterpret_cast<void**>(&partial), band_px * 3 * W.chunks * sizeof(double)));
     if (GSTACK) {
-        size_t bytes = static_cast<size_t>(s->depth + 4) * resident * dev::kBlock * sizeof(SE);  // + 3 levels below
+        size_t bytes = gstack_levels(s) * resident * dev::kBlock * sizeof(SE);  // + 3 levels below
         HIP_TRY(scratch(reinterpret_cast<void**>(&gstack), bytes));
     }
     if (count) {
@@ -3723,9 +3806,11 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
 
 // Kernel variant per scene: u16 stack entries below 65536 nodes; the scene itself in LDS when it
 // and the stack fit the LDS budget, else the stack alone in LDS, else everything in HBM.
+// render_layout fills W's LDS layout for the class it returns (W's class flags and tmin32 are the
+// caller's: class_flags); dispatch_render launches that class's instance.
 template <typename SE>
-static int dispatch_render(const crt_scene* s, int device, const crt_camera* cam, dev::Work W,
-                           double* d_rgb, hipStream_t st, crt_render_stats* count_stats, const RenderPass* pass) {
+static Layout render_layout(const crt_scene* s, dev::Work& W) {
+    Layout L;
     // depth + 1 levels: walk_step stores the far child at level sp unconditionally
     const size_t stack_bytes = align16(static_cast<size_t>(s->depth + 1) * dev::kBlock * sizeof(SE));
     W.bytes_nodes = static_cast<uint32_t>(align16(s->num_dnodes * sizeof(DevNodeF)));
@@ -3741,8 +3826,9 @@ static int dispatch_render(const crt_scene* s, int device, const crt_camera* cam
     const uint32_t level = static_cast<uint32_t>(dev::kBlock * sizeof(SE));  // one stack level
     // the sentinel is the last node; refs are byte offsets into the f32 node array
     W.sentinel = static_cast<uint32_t>(s->num_dnodes - 1) << kNodeFShift;
-    W.f32_ok = s->dev[device].f32_ok ? 1u : 0u;
-    W.tmin32 = static_cast<float>(cam->t_min);
+    L.stack_bytes = stack_bytes;
+    L.level = level;
+    L.all_nodes = s->num_dnodes * sizeof(DevNodeF);
     const bool force_global = std::getenv("CRT_NO_LDS_SCENE") != nullptr;
     // LDS stacks: [data][second guard: sentinel][guard level: sentinel][levels 0..depth]. A lane
     // that reaches the sentinel with no leaf recorded pops the second guard (round 6: it holds the
@@ -3754,20 +3840,22 @@ static int dispatch_render(const crt_scene* s, int device, const crt_camera* cam
     // garbage stack forever: the round-4 hang, found with -DCRT_WATCHDOG=1. Power-of-two blocks
     // had wrapped back onto the right level by the modular arithmetic alone.)
     auto stack_at = [&](size_t data_bytes) { return static_cast<uint32_t>(std::max<size_t>(data_bytes, 2 * level) + 2 * level); };
-    if (!force_global && stack_at(scene_bytes) + stack_bytes <= kLdsSceneBudget) {
+    // every admission counts what the launcher keeps behind the layout too (render_lds_tail): a
+    // request above the class's budget costs a resident block
+    const size_t cam_bytes = align16(sizeof(dev::CamView));
+    if (!force_global && stack_at(scene_bytes) + stack_bytes + cam_bytes <= kLdsSceneBudget) {
         W.lds_nodes = 0;
         W.lds_refs = W.lds_nodes + W.bytes_nodes;
         W.lds_spheres = W.lds_refs + W.bytes_refs;
         W.lds_quads = W.lds_spheres + W.bytes_spheres;
         W.lds_quadf = W.lds_quads + W.bytes_quads;
         W.lds_sph64 = W.lds_quadf + W.bytes_quadf;
-        const size_t cam_bytes = align16(sizeof(dev::CamView));
         // Sphere-only scenes and scenes of axis-aligned parallelograms run five waves per SIMD when
         // five blocks fit a CU's LDS (32 KB each), staging the f64 spheres only if they fit that
         // too (config 2: 73.7 ms at five waves without them vs 75.8 at four with them; config 3:
         // 89.8 vs 92.6); the others four, with up to 40 KB (the general instance at five: config
         // 3 116.5 vs 100.6 ms).
-        const size_t budget5 = 160 * 1024 * dev::kBlock / (64 * dev::kManyWaves * 4);  // LDS a block at five waves a SIMD
+        const size_t budget5 = kLdsBudget5;
         const bool w5 = (64 * dev::kManyWaves * 4) % dev::kBlock == 0 && (W.sphere_only || W.quads_flat) && std::getenv("CRT_FOUR_WAVES") == nullptr &&
                         stack_at(scene_bytes) + stack_bytes + cam_bytes + (W.sphere_only ? kAccBytes : 0) +
                             (W.quads_flat ? kInvBytes : 0) <= budget5;
@@ -3776,39 +3864,66 @@ static int dispatch_render(const crt_scene* s, int device, const crt_camera* cam
         if (W.spheres_f32 && stack_at(scene_bytes + sph64) + stack_bytes + cam_bytes + (w5 ? kAccBytes : 0) <= budget)
             W.bytes_sph64 = sph64;
         W.lds_stack = stack_at(scene_bytes + W.bytes_sph64);
-        const size_t lds = W.lds_stack + stack_bytes;
-        if (W.sphere_only)
-            return w5 ? launch_render<SE, false, true, 0, true>(s, device, cam, W, lds, d_rgb, st, count_stats, pass)
-                      : launch_render<SE, false, true, 0, false>(s, device, cam, W, lds, d_rgb, st, count_stats, pass);
-        if (W.quads_flat)
-            return w5 ? launch_render<SE, false, true, 2, true>(s, device, cam, W, lds, d_rgb, st, count_stats, pass)
-                      : launch_render<SE, false, true, 2, false>(s, device, cam, W, lds, d_rgb, st, count_stats, pass);
-        return launch_render<SE, false, true, 1>(s, device, cam, W, W.lds_stack + stack_bytes, d_rgb, st, count_stats, pass);
+        L.cls = kQueryLdsScene;
+        L.w5 = w5;
+        L.lds = W.lds_stack + stack_bytes;
+        L.budget = budget;
+        return L;
     }
     // HBM scene: the top of the (breadth-first) node array goes to LDS as far as it fits beside
     // the stack without costing resident blocks (CRT_WAVES_PER_EU blocks of 4 waves, the VGPR
     // limit); W.ntop counts bytes of f32 nodes
-    const size_t per_block = 160 * 1024 * dev::kBlock / (256 * CRT_WAVES_PER_EU);  // LDS per block at the VGPR occupancy
+    const size_t per_block = kLdsPerBlock;
+    L.budget = per_block;
     const bool no_top = std::getenv("CRT_NO_LDS_TOP") != nullptr;
-    const size_t all_nodes = s->num_dnodes * sizeof(DevNodeF);
+    const size_t all_nodes = L.all_nodes;
     auto top_bytes = [&](size_t room) {
         // whole 64-byte sibling pairs (walk_pairs reads a pair from LDS or from HBM, not both)
         return no_top ? 0u : static_cast<uint32_t>(std::min(all_nodes, room / (2 * sizeof(DevNodeF)) * (2 * sizeof(DevNodeF))));
     };
-    if (stack_bytes <= kLdsStackBudget && std::getenv("CRT_FORCE_GSTACK") == nullptr) {
-        const size_t taken = stack_bytes + 3 * level + kInvBytes;
-        const size_t room = per_block > taken ? per_block - taken : 0;
-        W.ntop = top_bytes(room);
+    // An LDS stack needs the levels stack_at keeps below it (four without a treelet), the rays' 1 / d
+    // and the camera copy beside it: a stack within kLdsStackBudget that does not fit per_block with
+    // them (u16 entries: 64 levels; u32: 30 and more) goes to HBM like a larger one.
+    if (stack_bytes <= kLdsStackBudget && stack_at(0) + stack_bytes + kInvBytes + cam_bytes <= per_block &&
+        std::getenv("CRT_FORCE_GSTACK") == nullptr) {
+        // beside the treelet: the stack, the two guard levels stack_at puts above the data, the rays'
+        // 1 / d and the camera copy (the admission leaves at least two levels of room)
+        const size_t taken = stack_bytes + 2 * level + kInvBytes + cam_bytes;
+        W.ntop = top_bytes(per_block - taken);
         W.lds_nodes = 0;
         W.lds_stack = stack_at(align16(W.ntop));
-        if (W.sphere_only)
-            return launch_render<SE, false, false, 0>(s, device, cam, W, W.lds_stack + stack_bytes, d_rgb, st, count_stats, pass);
-        return launch_render<SE, false, false, 1>(s, device, cam, W, W.lds_stack + stack_bytes, d_rgb, st, count_stats, pass);
+        L.cls = kQueryLdsStack;
+        L.lds = W.lds_stack + stack_bytes;
+        return L;
     }
-    W.ntop = top_bytes(per_block);
+    W.ntop = top_bytes(per_block - cam_bytes);
     W.lds_nodes = 0;
-    if (W.sphere_only) return launch_render<SE, true, false, 0>(s, device, cam, W, W.ntop, d_rgb, st, count_stats, pass);
-    return launch_render<SE, true, false, 1>(s, device, cam, W, W.ntop, d_rgb, st, count_stats, pass);
+    L.cls = kQueryHbmStack;
+    L.lds = W.ntop;
+    return L;
+}
+
+template <typename SE>
+static int dispatch_render(const crt_scene* s, int device, const crt_camera* cam, dev::Work W,
+                           double* d_rgb, hipStream_t st, crt_render_stats* count_stats, const RenderPass* pass) {
+    const Layout L = render_layout<SE>(s, W);
+    const int pm = render_prim_mode(W, L.cls);
+    switch (L.cls) {
+    case kQueryLdsScene:
+        if (pm == 0)
+            return L.w5 ? launch_render<SE, false, true, 0, true>(s, device, cam, W, L.lds, d_rgb, st, count_stats, pass)
+                        : launch_render<SE, false, true, 0, false>(s, device, cam, W, L.lds, d_rgb, st, count_stats, pass);
+        if (pm == 2)
+            return L.w5 ? launch_render<SE, false, true, 2, true>(s, device, cam, W, L.lds, d_rgb, st, count_stats, pass)
+                        : launch_render<SE, false, true, 2, false>(s, device, cam, W, L.lds, d_rgb, st, count_stats, pass);
+        return launch_render<SE, false, true, 1>(s, device, cam, W, L.lds, d_rgb, st, count_stats, pass);
+    case kQueryLdsStack:
+        if (pm == 0) return launch_render<SE, false, false, 0>(s, device, cam, W, L.lds, d_rgb, st, count_stats, pass);
+        return launch_render<SE, false, false, 1>(s, device, cam, W, L.lds, d_rgb, st, count_stats, pass);
+    default:
+        if (pm == 0) return launch_render<SE, true, false, 0>(s, device, cam, W, L.lds, d_rgb, st, count_stats, pass);
+        return launch_render<SE, true, false, 1>(s, device, cam, W, L.lds, d_rgb, st, count_stats, pass);
+    }
 }
 
 // The tiling checked (null: the whole frame as one tile) and W cleared but for its tiling part:
@@ -3860,19 +3975,14 @@ int device_render(const crt_scene* s, int device, const crt_camera* cam, const c
         }
         return CRT_OK;
     }
-    W.sphere_only = (s->num_quads == 0 && s->num_spheres != 0) ? 1u : 0u;
-    W.spheres_f32 = (W.sphere_only && s->dev[device].spheres_f32_ok) ? 1u : 0u;
-    W.quads_f32 = (s->num_spheres == 0 && s->num_quads != 0 && s->dev[device].quads_f32_ok) ? 1u : 0u;
-    // the flat-box filter is the walk's f32 node test: it needs the walk's f32 range (f32_ok)
-    W.quads_flat = (W.quads_f32 && s->dev[device].quads_flat_ok && s->dev[device].f32_ok) ? 1u : 0u;
-    W.exact_slab = (s->exact_slab || std::getenv("CRT_EXACT_SLAB") != nullptr) ? 1u : 0u;
-    W.pair_walk = (CRT_PAIR_WALK && !W.exact_slab && std::getenv("CRT_NO_PAIR_WALK") == nullptr) ? 1u : 0u;
+    class_flags(s, flags_of(s->dev[device]), s->dev[device].f32_ok, true, W);
+    W.tmin32 = static_cast<float>(cam->t_min);
     W.count_spec = std::getenv("CRT_COUNT_SPEC") != nullptr ? 1u : 0u;
     W.round_counters = std::getenv("CRT_ROUND_COUNTERS") != nullptr ? 1u : 0u;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (count_stats) HIP_TRY(hipStreamCreate(&st));
     int r;
-    if ((s->num_dnodes << kNodeFShift) <= 65536)  // every ref fits a u16 stack entry
+    if (u16_entries(s))
         r = dispatch_render<uint16_t>(s, device, cam, W, d_rgb, st, count_stats, pass);
     else
         r = dispatch_render<uint32_t>(s, device, cam, W, d_rgb, st, count_stats, pass);
@@ -4170,10 +4280,7 @@ int device_render_features(const crt_scene* s, int device, const crt_camera* cam
 template <typename SE, bool GSTACK, bool LSCENE, int PM>
 static int launch_trace(const crt_scene* s, int device, dev::Work W, size_t lds, dev::Query Q, bool any,
                         hipMemPool_t pool, hipStream_t stream) {
-    if (!LSCENE && !GSTACK) {  // the rays' f64 1 / d (query_kernel: kInvLds)
-        W.lds_inv64 = static_cast<uint32_t>(align16(lds));
-        lds = W.lds_inv64 + kInvBytes;
-    }
+    lds = trace_lds_tail(W, lds, GSTACK, LSCENE);
     const void* kfn = any ? reinterpret_cast<const void*>(dev::query_kernel<SE, GSTACK, LSCENE, PM, true>)
                           : reinterpret_cast<const void*>(dev::query_kernel<SE, GSTACK, LSCENE, PM, false>);
     int cus = 0, per_cu = 0;
@@ -4188,7 +4295,7 @@ static int launch_trace(const crt_scene* s, int device, dev::Work W, size_t lds,
     SE* gstack = nullptr;
     if (GSTACK)  // levels 0..depth, two guard levels and the level below them (render_kernel's layout)
         HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&gstack),
-                                       static_cast<size_t>(s->depth + 4) * blocks * dev::kBlock * sizeof(SE), pool, stream));
+                                       gstack_levels(s) * blocks * dev::kBlock * sizeof(SE), pool, stream));
     uint32_t* queue = nullptr;
     HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&queue), 256, pool, stream));
     HIP_TRY(hipMemsetAsync(queue, 0, sizeof(uint32_t), stream));
@@ -4210,17 +4317,20 @@ static int launch_trace(const crt_scene* s, int device, dev::Work W, size_t lds,
 static int launch_plain(const crt_scene* s, int device, const dev::Query& Q, bool any, hipMemPool_t pool,
                         hipStream_t st);
 
-// dispatch_render's decisions for a query: the scene in LDS when it and the stack fit, else the top
+// render_layout's decisions for a query: the scene in LDS when it and the stack fit, else the top
 // of the node array and the stack, else the stack in HBM too. Four waves per SIMD throughout: the
 // five-wave and flat-parallelogram-only instances of the render kernel have no query twin (a scene
 // of axis-aligned parallelograms runs its flat-box filter in the general instance).
-// query_layout fills W's LDS layout for the class it returns and *lds with the bytes laid out so far
+// query_layout fills W's LDS layout for the class it returns, with the bytes laid out so far
 // (the launchers add what their instance keeps behind that: `extra` bytes besides the rays' 1 / d,
 // which the treelet leaves free); crt_trace_async and crt_radiance_async share it.
-enum QueryClass { kQueryLdsScene, kQueryLdsStack, kQueryHbmStack };
+// the launchers' `extra`: nothing for a trace, the camera copy for a radiance query
+constexpr size_t kTraceExtra = 0;
+static size_t radiance_extra() { return align16(sizeof(dev::CamView)); }
 
 template <typename SE>
-static QueryClass query_layout(const crt_scene* s, dev::Work& W, size_t extra, size_t* lds) {
+static Layout query_layout(const crt_scene* s, dev::Work& W, size_t extra) {
+    Layout L;
     const size_t stack_bytes = align16(static_cast<size_t>(s->depth + 1) * dev::kBlock * sizeof(SE));
     W.bytes_nodes = static_cast<uint32_t>(align16(s->num_dnodes * sizeof(DevNodeF)));
     W.bytes_refs = W.spheres_f32 ? 0u : static_cast<uint32_t>(align16(s->num_prims * 4));
@@ -4233,9 +4343,12 @@ static QueryClass query_layout(const crt_scene* s, dev::Work& W, size_t extra, s
                                W.bytes_quadf;
     const uint32_t level = static_cast<uint32_t>(dev::kBlock * sizeof(SE));
     W.sentinel = static_cast<uint32_t>(s->num_dnodes - 1) << kNodeFShift;
-    // the guard levels' place, as dispatch_render lays them out
+    L.stack_bytes = stack_bytes;
+    L.level = level;
+    L.all_nodes = s->num_dnodes * sizeof(DevNodeF);
+    // the guard levels' place, as render_layout lays them out
     auto stack_at = [&](size_t data_bytes) { return static_cast<uint32_t>(std::max<size_t>(data_bytes, 2 * level) + 2 * level); };
-    if (std::getenv("CRT_NO_LDS_SCENE") == nullptr && stack_at(scene_bytes) + stack_bytes <= kLdsSceneBudget) {
+    if (std::getenv("CRT_NO_LDS_SCENE") == nullptr && stack_at(scene_bytes) + stack_bytes + extra <= kLdsSceneBudget) {
         W.lds_nodes = 0;
         W.lds_refs = W.lds_nodes + W.bytes_nodes;
         W.lds_spheres = W.lds_refs + W.bytes_refs;
@@ -4243,37 +4356,44 @@ static QueryClass query_layout(const crt_scene* s, dev::Work& W, size_t extra, s
         W.lds_quadf = W.lds_quads + W.bytes_quads;
         W.lds_sph64 = W.lds_quadf + W.bytes_quadf;
         const uint32_t sph64 = static_cast<uint32_t>(s->num_spheres * sizeof(DevSphere));
-        if (W.spheres_f32 && stack_at(scene_bytes + sph64) + stack_bytes <= kLdsSceneBudget) W.bytes_sph64 = sph64;
+        if (W.spheres_f32 && stack_at(scene_bytes + sph64) + stack_bytes + extra <= kLdsSceneBudget) W.bytes_sph64 = sph64;
         W.lds_stack = stack_at(scene_bytes + W.bytes_sph64);
-        *lds = W.lds_stack + stack_bytes;
-        return kQueryLdsScene;
+        L.cls = kQueryLdsScene;
+        L.lds = W.lds_stack + stack_bytes;
+        L.budget = kLdsSceneBudget;
+        return L;
     }
-    const size_t per_block = 160 * 1024 * dev::kBlock / (256 * CRT_WAVES_PER_EU);
+    const size_t per_block = kLdsPerBlock;
+    L.budget = per_block;
     const bool no_top = std::getenv("CRT_NO_LDS_TOP") != nullptr;
-    const size_t all_nodes = s->num_dnodes * sizeof(DevNodeF);
+    const size_t all_nodes = L.all_nodes;
     auto top_bytes = [&](size_t room) {  // whole 64-byte sibling pairs
         return no_top ? 0u : static_cast<uint32_t>(std::min(all_nodes, room / (2 * sizeof(DevNodeF)) * (2 * sizeof(DevNodeF))));
     };
-    if (stack_bytes <= kLdsStackBudget && std::getenv("CRT_FORCE_GSTACK") == nullptr) {
-        const size_t taken = stack_bytes + 3 * level + kInvBytes + extra;
-        const size_t room = per_block > taken ? per_block - taken : 0;
-        W.ntop = top_bytes(room);
+    // render_layout's admission and accounting: the stack, the levels below it, the rays' 1 / d and `extra`
+    if (stack_bytes <= kLdsStackBudget && stack_at(0) + stack_bytes + kInvBytes + extra <= per_block &&
+        std::getenv("CRT_FORCE_GSTACK") == nullptr) {
+        const size_t taken = stack_bytes + 2 * level + kInvBytes + extra;
+        W.ntop = top_bytes(per_block - taken);
         W.lds_nodes = 0;
         W.lds_stack = stack_at(align16(W.ntop));
-        *lds = W.lds_stack + stack_bytes;
-        return kQueryLdsStack;
+        L.cls = kQueryLdsStack;
+        L.lds = W.lds_stack + stack_bytes;
+        return L;
     }
     W.ntop = top_bytes(per_block - extra);
     W.lds_nodes = 0;
-    *lds = W.ntop;
-    return kQueryHbmStack;
+    L.cls = kQueryHbmStack;
+    L.lds = W.ntop;
+    return L;
 }
 
 template <typename SE>
 static int dispatch_trace(const crt_scene* s, int device, dev::Work W, const dev::Query& Q, bool any,
                           hipMemPool_t pool, hipStream_t st) {
-    size_t lds = 0;
-    switch (query_layout<SE>(s, W, 0, &lds)) {
+    const Layout L = query_layout<SE>(s, W, kTraceExtra);
+    const size_t lds = L.lds;
+    switch (L.cls) {
     case kQueryLdsScene:
         // Scenes this small are traced faster by the plain loop (rays of a few node tests each: the
         // persistent grid's per-ray costs dominate; DESIGN section 6d has the figures), so that is
@@ -4350,15 +4470,9 @@ int device_trace(const crt_scene* s, int device, const double* d_rays, size_t n,
     const DeviceCopy& c = s->dev[device];
     dev::Work W{};
     const bool filters = prm->t_min >= 0;
-    W.f32_ok = (c.f32_ok && std::fabs(prm->t_min) <= 0x1p100) ? 1u : 0u;
+    class_flags(s, flags_of(c), c.f32_ok && std::fabs(prm->t_min) <= 0x1p100, filters, W);
     W.tmin32 = static_cast<float>(prm->t_min);
-    W.sphere_only = (s->num_quads == 0 && s->num_spheres != 0) ? 1u : 0u;
-    W.spheres_f32 = (W.sphere_only && c.spheres_f32_ok && filters) ? 1u : 0u;
-    W.quads_f32 = (s->num_spheres == 0 && s->num_quads != 0 && c.quads_f32_ok && filters) ? 1u : 0u;
-    W.quads_flat = (W.quads_f32 && c.quads_flat_ok && W.f32_ok) ? 1u : 0u;
-    W.exact_slab = (s->exact_slab || std::getenv("CRT_EXACT_SLAB") != nullptr) ? 1u : 0u;
-    W.pair_walk = (CRT_PAIR_WALK && !W.exact_slab && std::getenv("CRT_NO_PAIR_WALK") == nullptr) ? 1u : 0u;
-    if ((s->num_dnodes << kNodeFShift) <= 65536) return dispatch_trace<uint16_t>(s, device, W, Q, any, pool, st);
+    if (u16_entries(s)) return dispatch_trace<uint16_t>(s, device, W, Q, any, pool, st);
     return dispatch_trace<uint32_t>(s, device, W, Q, any, pool, st);
 }
 
@@ -4404,12 +4518,7 @@ int device_trace_host(crt_scene* s, int device, const double* rays, size_t n, co
 template <typename SE, bool GSTACK, bool LSCENE, int PM>
 static int launch_radiance(const crt_scene* s, int device, dev::Work W, size_t lds, const dev::CamView& C,
                            dev::Radiance Q, hipMemPool_t pool, hipStream_t stream) {
-    W.lds_cam = static_cast<uint32_t>(align16(lds));
-    lds = W.lds_cam + align16(sizeof(dev::CamView));
-    if (!LSCENE && !GSTACK) {  // the rays' f64 1 / d (radiance_kernel: kInvLds)
-        W.lds_inv64 = static_cast<uint32_t>(align16(lds));
-        lds = W.lds_inv64 + kInvBytes;
-    }
+    lds = radiance_lds_tail(W, lds, GSTACK, LSCENE);
     const void* kfn = reinterpret_cast<const void*>(dev::radiance_kernel<SE, GSTACK, LSCENE, PM>);
     int cus = 0, per_cu = 0;
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
@@ -4423,7 +4532,7 @@ static int launch_radiance(const crt_scene* s, int device, dev::Work W, size_t l
     SE* gstack = nullptr;
     if (GSTACK)  // levels 0..depth, two guard levels and the level below them (render_kernel's layout)
         HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&gstack),
-                                       static_cast<size_t>(s->depth + 4) * blocks * dev::kBlock * sizeof(SE), pool, stream));
+                                       gstack_levels(s) * blocks * dev::kBlock * sizeof(SE), pool, stream));
     uint32_t* queue = nullptr;
     HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&queue), 256, pool, stream));
     HIP_TRY(hipMemsetAsync(queue, 0, sizeof(uint32_t), stream));
@@ -4464,8 +4573,9 @@ static int launch_plain_radiance(const crt_scene* s, int device, const dev::CamV
 template <typename SE>
 static int dispatch_radiance(const crt_scene* s, int device, dev::Work W, const dev::CamView& C,
                              const dev::Radiance& Q, hipMemPool_t pool, hipStream_t st) {
-    size_t lds = 0;
-    switch (query_layout<SE>(s, W, align16(sizeof(dev::CamView)), &lds)) {
+    const Layout L = query_layout<SE>(s, W, radiance_extra());
+    const size_t lds = L.lds;
+    switch (L.cls) {
     case kQueryLdsScene:
         if (W.sphere_only) return launch_radiance<SE, false, true, 0>(s, device, W, lds, C, Q, pool, st);
         return launch_radiance<SE, false, true, 1>(s, device, W, lds, C, Q, pool, st);
@@ -4511,16 +4621,93 @@ int device_radiance(const crt_scene* s, int device, const double* d_rays, size_t
     // device_trace's scene classes and interval rules; 0 <= t_min <= 2^100 here (crt_radiance_async)
     const DeviceCopy& c = s->dev[device];
     dev::Work W{};
-    W.f32_ok = c.f32_ok ? 1u : 0u;
+    class_flags(s, flags_of(c), c.f32_ok, true, W);
     W.tmin32 = static_cast<float>(prm->t_min);
-    W.sphere_only = (s->num_quads == 0 && s->num_spheres != 0) ? 1u : 0u;
-    W.spheres_f32 = (W.sphere_only && c.spheres_f32_ok) ? 1u : 0u;
-    W.quads_f32 = (s->num_spheres == 0 && s->num_quads != 0 && c.quads_f32_ok) ? 1u : 0u;
-    W.quads_flat = (W.quads_f32 && c.quads_flat_ok && W.f32_ok) ? 1u : 0u;
-    W.exact_slab = (s->exact_slab || std::getenv("CRT_EXACT_SLAB") != nullptr) ? 1u : 0u;
-    W.pair_walk = (CRT_PAIR_WALK && !W.exact_slab && std::getenv("CRT_NO_PAIR_WALK") == nullptr) ? 1u : 0u;
-    if ((s->num_dnodes << kNodeFShift) <= 65536) return dispatch_radiance<uint16_t>(s, device, W, C, Q, pool, st);
+    if (u16_entries(s)) return dispatch_radiance<uint16_t>(s, device, W, C, Q, pool, st);
     return dispatch_radiance<uint32_t>(s, device, W, C, Q, pool, st);
+}
+
+// ---- launch plans (crt_launch_plan) ------------------------------------------------------------
+// The plan of one kernel: device_render's, device_trace's or device_radiance's class flags, that
+// kernel's layout step and its launcher's additions, for the instance its dispatch step picks.
+template <typename SE>
+static void plan_of(const crt_scene* s, uint32_t kernel, const CopyFlags& c, crt_launch_plan_info& p) {
+    dev::Work W{};
+    W.lds_cam = W.lds_acc = W.lds_inv64 = CRT_PLAN_ABSENT;
+    class_flags(s, c, c.f32_ok, true, W);
+    Layout L;
+    size_t total;
+    int pm;
+    if (kernel == CRT_PLAN_RENDER) {
+        L = render_layout<SE>(s, W);
+        pm = render_prim_mode(W, L.cls);
+        total = render_lds_tail(W, L.lds, L.cls == kQueryHbmStack, L.cls == kQueryLdsScene, pm, L.w5);
+    } else if (kernel == CRT_PLAN_TRACE) {
+        L = query_layout<SE>(s, W, kTraceExtra);
+        pm = query_prim_mode(W);
+        total = trace_lds_tail(W, L.lds, L.cls == kQueryHbmStack, L.cls == kQueryLdsScene);
+        p.plain_route = (L.cls == kQueryLdsScene && std::getenv("CRT_TRACE_FAST") == nullptr) ? 1u : 0u;
+    } else {
+        L = query_layout<SE>(s, W, radiance_extra());
+        pm = query_prim_mode(W);
+        total = radiance_lds_tail(W, L.lds, L.cls == kQueryHbmStack, L.cls == kQueryLdsScene);
+    }
+    p.kernel = kernel;
+    p.klass = L.cls == kQueryLdsScene ? CRT_PLAN_LDS_SCENE : L.cls == kQueryLdsStack ? CRT_PLAN_LDS_STACK : CRT_PLAN_HBM_STACK;
+    p.entry_bytes = sizeof(SE);
+    p.five_waves = L.w5 ? 1u : 0u;
+    p.prim_mode = static_cast<uint32_t>(pm);
+    p.depth = s->depth;
+    p.block = dev::kBlock;
+    p.num_nodes = s->num_dnodes;
+    p.stack_bytes = static_cast<uint32_t>(L.stack_bytes);
+    p.level = static_cast<uint32_t>(L.level);
+    p.sentinel = W.sentinel;
+    p.hbm_stack_levels = L.cls == kQueryHbmStack ? static_cast<uint32_t>(gstack_levels(s)) : 0u;
+    p.lds_nodes = W.lds_nodes;
+    p.lds_refs = W.lds_refs;
+    p.lds_spheres = W.lds_spheres;
+    p.lds_quads = W.lds_quads;
+    p.lds_quadf = W.lds_quadf;
+    p.lds_sph64 = W.lds_sph64;
+    p.lds_stack = W.lds_stack;
+    p.bytes_nodes = W.bytes_nodes;
+    p.bytes_refs = W.bytes_refs;
+    p.bytes_spheres = W.bytes_spheres;
+    p.bytes_quads = W.bytes_quads;
+    p.bytes_quadf = W.bytes_quadf;
+    p.bytes_sph64 = W.bytes_sph64;
+    p.ntop = W.ntop;
+    p.all_nodes = static_cast<uint32_t>(L.all_nodes);
+    p.lds_cam = W.lds_cam;
+    p.lds_acc = W.lds_acc;
+    p.lds_inv64 = W.lds_inv64;
+    p.bytes_cam = static_cast<uint32_t>(align16(sizeof(dev::CamView)));
+    p.bytes_acc = static_cast<uint32_t>(kAccBytes);
+    p.bytes_inv64 = static_cast<uint32_t>(kInvBytes);
+    p.total_lds = static_cast<uint32_t>(total);
+    p.budget = static_cast<uint32_t>(L.budget);
+    p.spheres_f32 = W.spheres_f32;
+    p.quads_f32 = W.quads_f32;
+    p.quads_flat = W.quads_flat;
+    p.f32_ok = W.f32_ok;
+}
+
+int device_launch_plan(crt_scene* s, uint32_t kernel, crt_launch_plan_info* out) {
+    if (s->num_dnodes == 0 || s->num_dnodes >= (size_t{1} << (31 - kNodeFShift)))
+        return fail(CRT_E_INVALID, "crt_launch_plan: no device node layout for this BVH");
+    if (s->image_device < 0) {  // device_upload's staging
+        std::lock_guard<std::mutex> ls(s->mu);
+        if (!s->staged) stage_image(s);
+    }
+    crt_launch_plan_info p{};
+    const CopyFlags c = copy_flags(s);
+    if (u16_entries(s))
+        plan_of<uint16_t>(s, kernel, c, p);
+    else
+        plan_of<uint32_t>(s, kernel, c, p);
+    *out = p;
+    return CRT_OK;
 }
 
 // crt_radiance: device_radiance for host arrays, blocking: one upload of the rays (and states), one

@@ -1809,4 +1809,12 @@ int crt_render_guard(crt_scene* s, int device, uint64_t* schlick_undecided, int 
     return device_guard(s, device, schlick_undecided, reset != 0);
 }
 
+int crt_launch_plan(const crt_scene* s, uint32_t kernel, crt_launch_plan_info* out) {
+    clear_error();
+    if (!s || !out) return fail(CRT_E_INVALID, "crt_launch_plan: null argument");
+    if (kernel > CRT_PLAN_RADIANCE) return fail(CRT_E_INVALID, "crt_launch_plan: unknown kernel");
+    // the staged image is a cache the first upload would fill: the plan fills it the same way
+    return device_launch_plan(const_cast<crt_scene*>(s), kernel, out);
+}
+
 }  // extern "C"

@@ -352,6 +352,13 @@ namespace crt {
 enum DevArray { kArrNodes, kArrFNodes, kArrRefs, kArrSpheres, kArrSpherePairs, kArrSphereMat, kArrQuads,
                 kArrQuadF, kArrQuadBox, kArrQuadMat, kArrMats, kArrSphereMrec, kArrQuadMrec, kArrGuard,
                 kArrCount };
+// The pair walk (crt_device.hip fetch_two) loads a token's sibling f ^ 32 even for a token tested
+// alone. The node count is odd (root, pad, sibling pairs, sentinel), so the sentinel's sibling is
+// the 32 bytes past the f32 node array: never tested, but read. In HBM they must be mapped: an
+// array follows kArrFNodes in the same allocation (and the guard words end it, so the padding
+// before the next array is mapped even when that array is empty). In LDS the launch plans keep a
+// region behind the nodes (tests/test_launch_plan.py checks every plan for it).
+static_assert(kArrFNodes + 1 < kArrGuard, "an array must follow the f32 nodes in the device allocation");
 inline size_t device_layout(const crt_scene* s, size_t off[kArrCount + 1]) {
     const size_t n_nodes = s->num_dnodes, n_sp = s->num_spheres, n_q = s->num_quads;
     const size_t bytes[kArrCount] = {
@@ -418,6 +425,9 @@ int device_radiance(const crt_scene* s, int device, const double* d_rays, size_t
                     const crt_radiance_params* prm, double* d_rgb, void* stream);
 int device_radiance_host(crt_scene* s, int device, const double* rays, size_t n, const uint32_t* states,
                          const crt_radiance_params* prm, double* rgb);
+// crt_launch_plan: the layout steps and the launchers' additions of the three scene kernels, run on
+// the host alone (stages a host-built scene's image if no upload has yet)
+int device_launch_plan(crt_scene* s, uint32_t kernel, crt_launch_plan_info* out);
 int device_camera_rays(int device, const crt_camera* cam, const crt_tiling* t, uint32_t first_sample,
                        uint32_t num_samples, double* d_rays, uint32_t* d_states, void* stream);
 // irradiance probes (crt_probes.hip; crt_host.cpp's entry points check the arguments): the generator

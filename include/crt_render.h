@@ -917,6 +917,49 @@ int crt_ppm_write(const char* path, uint32_t w, uint32_t h, const int32_t* value
  * the reference does. Synchronizes the device; reset != 0 zeroes the count. */
 int crt_render_guard(crt_scene* scene, int device, uint64_t* schlick_undecided, int reset);
 
+/* ---- launch plans ---------------------------------------------------------------------- */
+/* What the host would decide for a launch of one of the three scene kernels, from the scene's size
+ * alone: the class, the stack entry width, the instance and the LDS layout. Host only: no device is
+ * touched and nothing is uploaded (a host-built scene that has not been uploaded yet is staged on
+ * the host, as its first upload would). The values come from the code the launches run (the layout
+ * steps and the launchers' own additions), and the CRT_* switches (CRT_NO_LDS_SCENE,
+ * CRT_FORCE_GSTACK, CRT_NO_LDS_TOP, CRT_FOUR_WAVES, CRT_TRACE_FAST, CRT_F64_*, CRT_GENERIC_QUADS)
+ * are read when the plan is asked, where a launch reads the last four when the scene is uploaded.
+ * TRACE and RADIANCE plans are those of a query with 0 <= t_min <= 2^100 and no PLAIN flag.
+ * An addition to the ABI (no existing call changes, CRT_ABI_VERSION stays): `reserved` words are
+ * zero and later fields take their place. */
+enum { CRT_PLAN_RENDER = 0, CRT_PLAN_TRACE = 1, CRT_PLAN_RADIANCE = 2 };
+enum { CRT_PLAN_LDS_SCENE = 0, CRT_PLAN_LDS_STACK = 1, CRT_PLAN_HBM_STACK = 2 };
+#define CRT_PLAN_ABSENT 0xffffffffu /* an lds_* region the instance does not have */
+typedef struct crt_launch_plan_info {
+    uint32_t kernel;        /* CRT_PLAN_RENDER / TRACE / RADIANCE                              */
+    uint32_t klass;         /* CRT_PLAN_LDS_SCENE: the scene and the stack in LDS; LDS_STACK: the
+                             * top of the node array and the stack; HBM_STACK: the top alone     */
+    uint32_t entry_bytes;   /* stack entry width: 2 or 4                                       */
+    uint32_t five_waves;    /* render: the five-waves-per-SIMD instance                         */
+    uint32_t prim_mode;     /* 0 sphere-only, 1 general, 2 flat parallelograms                  */
+    uint32_t plain_route;   /* trace: an LDS-scene launch takes the plain loop (no dynamic LDS)
+                             * unless CRT_TRACE_FAST is set; the layout is the fast instance's    */
+    uint32_t depth;         /* BVH levels: the stack holds levels 0..depth                      */
+    uint32_t block;         /* threads per block                                                */
+    uint64_t num_nodes;     /* device nodes, the pad and the sentinel included                  */
+    uint32_t stack_bytes, level, sentinel;
+    uint32_t hbm_stack_levels; /* HBM_STACK: levels allocated per lane (3 below level 0), else 0 */
+    /* dev::Work's layout: byte offsets and 16-byte padded sizes; the scene regions are meaningful
+     * for LDS_SCENE only, lds_stack for LDS_SCENE and LDS_STACK */
+    uint32_t lds_nodes, lds_refs, lds_spheres, lds_quads, lds_quadf, lds_sph64, lds_stack;
+    uint32_t bytes_nodes, bytes_refs, bytes_spheres, bytes_quads, bytes_quadf, bytes_sph64;
+    uint32_t ntop, all_nodes; /* LDS_STACK, HBM_STACK: bytes of f32 nodes staged at offset 0 / in all */
+    /* the launchers' additions (CRT_PLAN_ABSENT: none) and their sizes */
+    uint32_t lds_cam, lds_acc, lds_inv64;
+    uint32_t bytes_cam, bytes_acc, bytes_inv64;
+    uint32_t total_lds;     /* the dynamic LDS the launch requests                              */
+    uint32_t budget;        /* the budget the class was admitted under                          */
+    uint32_t spheres_f32, quads_f32, quads_flat, f32_ok; /* the instance's f32 flags            */
+    uint32_t reserved[9];
+} crt_launch_plan_info; /* 200 bytes */
+int crt_launch_plan(const crt_scene* scene, uint32_t kernel, crt_launch_plan_info* out);
+
 #ifdef __cplusplus
 }
 #endif
