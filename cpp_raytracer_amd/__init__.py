@@ -333,6 +333,31 @@ class GpuScene:
         check(lib().crt_launch_plan(self._h, int(k), C.byref(p)), "crt_launch_plan")
         return p
 
+    def walk_links(self) -> Optional[np.ndarray]:
+        """The miss links of the stackless walk (crt_walk_links): a (device nodes, 8) uint16 array,
+        entry [node, octant] = the reference (node index * 32) of the node the walk continues at when
+        it does not descend from `node`; None when the scene has no table."""
+        n = C.c_size_t(0)
+        check(lib().crt_walk_links(self._h, None, 0, C.byref(n)), "crt_walk_links")
+        if n.value == 0:
+            return None
+        out = np.zeros((n.value, 8), np.uint16)
+        check(lib().crt_walk_links(self._h, out.ctypes.data, out.size, C.byref(n)), "crt_walk_links")
+        return out
+
+    def walk_links_valid(self, links: np.ndarray) -> bool:
+        """The check every upload runs on its table, for a caller's one (crt_walk_links_validate)."""
+        t = np.ascontiguousarray(links, np.uint16)
+        ok = C.c_int(0)
+        check(lib().crt_walk_links_validate(self._h, t.ctypes.data, t.size, C.byref(ok)), "crt_walk_links_validate")
+        return bool(ok.value)
+
+    def last_walk(self, device: int = 0) -> str:
+        """The walk of the last render launch on `device`: "none", "stack" or "links" (crt_last_walk)."""
+        w = C.c_uint32(0)
+        check(lib().crt_last_walk(self._h, device, C.byref(w)), "crt_last_walk")
+        return ("none", "stack", "links")[w.value]
+
     def upload(self, device: int = 0) -> None:
         check(lib().crt_scene_upload(self._h, device), f"crt_scene_upload(device={device})")
 

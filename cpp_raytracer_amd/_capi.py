@@ -258,6 +258,9 @@ EXPORTS = {
     "crt_ppm_write": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "crt_render_guard": (C.c_int, [C.c_void_p, C.c_int, P(C.c_uint64), C.c_int]),
     "crt_launch_plan": (C.c_int, [C.c_void_p, C.c_uint32, P(LaunchPlan)]),
+    "crt_walk_links": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, P(C.c_size_t)]),
+    "crt_walk_links_validate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, P(C.c_int)]),
+    "crt_last_walk": (C.c_int, [C.c_void_p, C.c_int, P(C.c_uint32)]),
 }
 
 

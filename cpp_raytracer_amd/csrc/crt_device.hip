@@ -79,6 +79,11 @@ struct SceneView {
     uint32_t refs_lds, spheres_lds, quads_lds;
     uint32_t inv64_lds;          // flat-parallelogram LDS kernels: the lanes' 1 / d ([k][lane] doubles)
     unsigned long long* guard;   // parity guard words (DeviceCopy::guard)
+    // link instances (render_kernel LINK): the miss-link table in HBM (DeviceCopy::links) and the
+    // LDS byte offset of its staged copy, 16 bytes a node: the record of ref r at links_lds + (r >> 1)
+    const uint16_t* links;
+    uint32_t links_lds;
+    uint32_t sentinel;           // link instances: the sentinel's ref, where a traversal ends (leaf_step)
 };
 
 struct CamView {
@@ -128,6 +133,8 @@ struct Work {
     uint32_t lds_cam;       // LDS copy of the CamView (read where used: keeps it out of SGPRs)
     uint32_t lds_acc;       // five-wave instances: the lanes' pixel sums (3 x kBlock doubles)
     uint32_t lds_inv64;     // flat-parallelogram LDS instances: the lanes' 1 / d (3 x kBlock doubles)
+    // link instances: the miss-link table, staged where the plan keeps the guard levels and the stack
+    uint32_t lds_links, bytes_links;
     uint32_t packed;        // the output holds only the owned rows (CRT_TILING_PACKED)
     // instrumented pass only (COUNT): walk speculatively like the timed kernel (CRT_COUNT_SPEC=1),
     // count per-round lane numbers (CRT_ROUND_COUNTERS=1; their atomics shift the phase timings)
@@ -1029,9 +1036,35 @@ __device__ __forceinline__ Uvec2 fetch_nodef_words(const SceneView& S, uint32_t 
     return w;
 }
 
-template <typename SE, bool COUNT, bool EXACT, bool TOP, bool LS, bool GS, bool SPEC, bool INVL = false, bool G2 = true>
+// The lane's miss link at node ref `cur` (LINK instances): lbase = S.links_lds + 2 * octant
+typedef __attribute__((address_space(3))) const uint16_t LdsU16;
+__device__ __forceinline__ uint32_t link_at(uint32_t lbase, uint32_t cur) {
+    return *(LdsU16*)static_cast<uintptr_t>(lbase + (cur >> 1));
+}
+
+// ---- the stackless form (LINK: the five-wave LDS-scene render instances) -----------------------
+// BVH::hit_by (bvh.h:684-698) picks the near child by dir_is_negative[split_axis] alone, so a
+// ray's DFS order is fixed by its three sign bits (the octant, R.neg & 7), whatever t_max does.
+// The node a pop returns is therefore a static function of (node, octant): miss(root, o) = the
+// sentinel, and for an interior node N whose near and far children under o are n and f,
+// miss(n, o) = f and miss(f, o) = miss(N, o). With that table (crt_walk_links.h, staged in the
+// bytes the plan keeps for the guard levels and the stack) a step is
+//   cur = (enter && interior) ? near : miss[cur][o],
+// an entered leaf continues at its own miss link after its primitives (the stack walk's pop after
+// the leaf), and the traversal ends at the sentinel, whose links point to itself (so the "reached
+// the sentinel with no leaf recorded" case re-tests the sentinel like the second guard level made
+// it do, and parks). No push, no pop, no stack pointer, no guard levels, no R.sp. At every step the
+// stack walk's top IS miss(cur, o): by induction, pushing f on entering N leaves the top f =
+// miss(n, o) for n, and a pop below f exposes what was the top at N, miss(N, o) = miss(f, o). So
+// the visited node sequence is the stack walk's, and every primitive test, tie and frame bit
+// stays the same. The speculative walk's argument above (monotone node test, t_max only shrinking)
+// speaks of the order of the nodes alone and never of the stack, so it holds as it stands; a
+// parked lane remembers its node (`pcur`) with no pop to undo.
+template <typename SE, bool COUNT, bool EXACT, bool TOP, bool LS, bool GS, bool SPEC, bool INVL = false, bool G2 = true,
+          bool LINK = false>
 __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const double o[3], const double d[3],
                                      double tmin, float tmin32, Trav& R, LaneCounters& ctr) {
+    static_assert(!LINK || (LS && !GS && !TOP), "miss links are staged by the LDS-scene instances only");
     // Every step ends with the next node in `cur`: the near child of an entered interior node,
     // else the stack top, popped. The level below the stack holds the sentinel node, entered by
     // every ray, so popping an empty stack leads to the sentinel and the only exit is "entered a
@@ -1045,9 +1078,12 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
     // depth + 1 levels); at the sentinel that store rewrites the guard level with the sentinel's
     // own reference, and the speculative read of the top reads the level below the guard (in
     // bounds: the host keeps it inside the allocation).
-    const ptrdiff_t stride = static_cast<ptrdiff_t>(st.stride);
-    SE* const empty = st.base - stride;
-    SE* tp = st.base + (static_cast<ptrdiff_t>(R.sp) - 1) * stride;
+    // LINK: no stack (st is never read); `top` below is the lane's miss link at `cur`, read with
+    // the node like the speculative pop it replaces
+    const ptrdiff_t stride = LINK ? 0 : static_cast<ptrdiff_t>(st.stride);
+    SE* const empty = LINK ? nullptr : st.base - stride;
+    SE* tp = LINK ? nullptr : st.base + (static_cast<ptrdiff_t>(R.sp) - 1) * stride;
+    const uint32_t lbase = LINK ? S.links_lds + ((R.neg & 7u) << 1) : 0u;
     uint32_t cur = R.cur;
     uint32_t w0, w1;  // the last node's DevNodeF words (leaf / sentinel at the exit)
     bool stop;
@@ -1061,7 +1097,7 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
             NodeLines nd;
             node_lines(node64(S, cur), nd);
             const Uvec4 meta = nd.meta;  // index count axis flags
-            const uint32_t top = *tp;    // speculative pop
+            const uint32_t top = LINK ? link_at(lbase, cur) : *tp;  // speculative pop
             if (COUNT) {
                 if (meta.y != kSentinelCount) ctr.nodes++;
                 if (wave_leader()) ctr.it_walk++;
@@ -1088,10 +1124,10 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
             const bool inner = enter & (meta.y == 0);
             const bool far_first = (R.neg >> meta.z) & 1u;
             const uint32_t left = meta.w << kNodeFShift, right = meta.x << kNodeFShift;
-            tp[stride] = static_cast<SE>(far_first ? left : right);
+            if (!LINK) tp[stride] = static_cast<SE>(far_first ? left : right);
             stop = enter ^ inner;  // entered, not interior: a leaf or the sentinel
             cur = inner ? (far_first ? right : left) : top;
-            tp += inner ? stride : -stride;
+            if (!LINK) tp += inner ? stride : -stride;
             w0 = meta.x;
             w1 = meta.y == kSentinelCount ? kSentinelW1 : (kLeafFlagF | meta.y);
         } while (!stop);
@@ -1123,7 +1159,7 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
                 fetch_nodef<TOP, LS>(S, cur, q0, q1);
                 w0 = q1.z;
                 w1 = q1.w;
-                const uint32_t top = *tp;  // speculative pop
+                const uint32_t top = LINK ? link_at(lbase, cur) : *tp;  // speculative pop
                 if (COUNT) {
                     if (w1 != kSentinelW1) ctr.nodes++;
                     if (wave_leader()) ctr.it_walk++;
@@ -1150,7 +1186,7 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
                 }
                 const bool inner = enter & (w1 < kLeafFlagF);
                 const uint32_t near = w1 | (__builtin_amdgcn_ubfe(R.neg, w0, 1) << kNodeFShift);
-                tp[stride] = static_cast<SE>(near ^ (1u << kNodeFShift));
+                if (!LINK) tp[stride] = static_cast<SE>(near ^ (1u << kNodeFShift));
                 const bool reached = enter & !inner;  // a leaf or the sentinel
                 // a lane that reaches the sentinel with no leaf recorded records it and pops the
                 // second guard level, which holds the sentinel too: it parks there, with a leaf
@@ -1162,13 +1198,13 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
                 pcur = park ? cur : pcur;
                 run = !park;
                 cur = inner ? near : top;
-                tp += inner ? stride : -stride;
+                if (!LINK) tp += inner ? stride : -stride;
             }
             nopend = pref == ~0u;
         } while (__ballot(nopend) != 0);
         if (!run) {  // parked: back at the node, its pop undone
             cur = pcur;
-            tp += stride;
+            if (!LINK) tp += stride;
         }
         // the recorded node's words (a leaf's primitive range, or the sentinel: traversal over)
         {
@@ -1180,7 +1216,7 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
         R.first = w0;
         R.count = w1 & ~kLeafFlagF;
         R.cur = cur;
-        R.sp = static_cast<int32_t>(static_cast<uint32_t>(tp - empty)) / static_cast<int32_t>(st.stride);
+        if (!LINK) R.sp = static_cast<int32_t>(static_cast<uint32_t>(tp - empty)) / static_cast<int32_t>(st.stride);
         return;
     } else {
         do {
@@ -1189,7 +1225,7 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
             fetch_nodef<TOP, LS>(S, cur, q0, q1);
             w0 = q1.z;
             w1 = q1.w;
-            const uint32_t top = *tp;  // speculative pop
+            const uint32_t top = LINK ? link_at(lbase, cur) : *tp;  // speculative pop
             if (COUNT) {
                 if (w1 != kSentinelW1) ctr.nodes++;
                 if (wave_leader()) ctr.it_walk++;
@@ -1222,10 +1258,10 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
             // split axis), far = near ^ 32. At a leaf the store lands above the live stack; at the
             // sentinel it overwrites the guard level, which every traversal start rewrites.
             const uint32_t near = w1 | (__builtin_amdgcn_ubfe(R.neg, w0, 1) << kNodeFShift);
-            tp[stride] = static_cast<SE>(near ^ (1u << kNodeFShift));
+            if (!LINK) tp[stride] = static_cast<SE>(near ^ (1u << kNodeFShift));
             stop = enter ^ inner;  // entered, not interior: a leaf or the sentinel
             cur = inner ? near : top;
-            tp += inner ? stride : -stride;
+            if (!LINK) tp += inner ? stride : -stride;
         } while (!stop);
     }
     R.state = w1 == kSentinelW1 ? kDone : kLeaf;
@@ -1233,7 +1269,7 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
     R.count = w1 & ~kLeafFlagF;
     R.cur = cur;
     // levels in use after the pop; -1 when the leaf was entered with an empty stack
-    R.sp = static_cast<int32_t>(static_cast<uint32_t>(tp - empty)) / static_cast<int32_t>(st.stride);
+    if (!LINK) R.sp = static_cast<int32_t>(static_cast<uint32_t>(tp - empty)) / static_cast<int32_t>(st.stride);
 }
 
 // ---- the sibling-pair walk of the HBM-scene kernels (CRT_PAIR_WALK) ----------------------------
@@ -1430,7 +1466,8 @@ __device__ __forceinline__ void walk_pairs(const SceneView& S, Stack<SE>& st, co
 // QONLY: every primitive is a parallelogram (the flat-parallelogram instances): the sphere paths,
 // and with them the ray's sphere constants (dot(d, d), its reciprocal, the coarse-reject limits),
 // are compiled out
-template <typename SE, bool COUNT, bool TOP, bool LS, bool FAST = false, bool QONLY = false>
+// LINK: the walk left the leaf's miss link in R.cur; the traversal is over when that is the sentinel
+template <typename SE, bool COUNT, bool TOP, bool LS, bool FAST = false, bool QONLY = false, bool LINK = false>
 __device__ __forceinline__ void leaf_step(const SceneView& S, Stack<SE>& st, const double o[3],
                                               const double d[3], double tmin, float tmin32, bool sphere_only, bool pairs,
                                               bool qfilter, bool qflat, Trav& R, LaneCounters& ctr) {
@@ -1612,7 +1649,7 @@ __device__ __forceinline__ void leaf_step(const SceneView& S, Stack<SE>& st, con
         }
     }
     // the pop after the leaf was made by walk (R.cur is the next node, unless the stack was empty)
-    R.state = R.sp < 0 ? kDone : kWalk;
+    R.state = (LINK ? R.cur == S.sentinel : R.sp < 0) ? kDone : kWalk;
 }
 
 __device__ __forceinline__ uint32_t owned_row(const Work& w, uint32_t k) {
@@ -1827,7 +1864,10 @@ __device__ __forceinline__ void set_prio() {
 // the band's active tiles only: active[0] = their number, active[1 + i] = the band tile of list
 // entry i, in tile-major order (active_list_kernel). A separate instance: the unmasked instances
 // keep their code.
-template <typename SE, bool GSTACK, bool LSCENE, bool COUNT, int PM, bool W5, bool MASK = false>
+// LINK: the stackless walk over the scene's miss links (walk(), LINK), launched for the five-wave
+// sphere-only and flat-parallelogram instances when the table exists and fits the stack region
+// (dispatch_render); no Stack, no guard levels, no sentinel stores in the traversal set-up.
+template <typename SE, bool GSTACK, bool LSCENE, bool COUNT, int PM, bool W5, bool MASK = false, bool LINK = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kManyWaves : LSCENE ? CRT_WAVES_PER_EU_LDS : CRT_WAVES_PER_EU, 8))) void render_kernel(
     SceneView Sg, CamView C, Work W, double* __restrict__ partial, SE* __restrict__ gstack,
     Counters* __restrict__ counters, const uint32_t* __restrict__ active) {
@@ -1863,6 +1903,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kMa
             S.refs = reinterpret_cast<const uint32_t*>(smem + W.lds_refs);
             S.spheres = reinterpret_cast<const DevSphere*>(smem + W.lds_spheres);
         }
+        if (LINK) {  // the miss links, in the bytes of the guard levels and the stack
+            stage_lds(smem + W.lds_links, Sg.links, W.bytes_links);
+            S.links_lds = W.lds_links;
+            S.sentinel = W.sentinel;
+        }
         __syncthreads();
     } else if (W.ntop) {  // HBM scene: keep the first ntop bytes of f32 nodes (top levels) in LDS
         if (static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsByte*)smem)) != 0) __builtin_trap();
@@ -1884,16 +1929,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kMa
     const unsigned long long t_start = COUNT ? wall_clock64() : 0;
     // stack levels 0..depth of this lane, above two guard levels holding the sentinel reference
     // and one more level walk() may read (three levels in HBM; in LDS that one is other data)
-    Stack<SE> st;
-    if (GSTACK) {
+    Stack<SE> st{};
+    if (LINK) {
+        // no stack: its bytes hold the miss links
+    } else if (GSTACK) {
         st.stride = gridDim.x * kBlock;
         st.base = gstack + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x) + 3 * static_cast<size_t>(st.stride);
     } else {
         st.base = reinterpret_cast<SE*>(smem + W.lds_stack) + threadIdx.x;
         st.stride = kBlock;
     }
-    st.base[-static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel);
-    st.base[-2 * static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel);
+    if (!LINK) {
+        st.base[-static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel);
+        st.base[-2 * static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel);
+    }
     // The wave's current item (wave-uniform) and how many of its 64 units are drawn; lanes take
     // the next units in lane order. A unit's sum goes to partial[chunk][pixel] whichever lane
     // traced it, so frames do not depend on the schedule.
@@ -2026,8 +2075,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kMa
             // the pair walk's lanes hold tokens (walk_pairs): the root pair's left child, and the
             // sentinel's token in the guard level; rays that need the EXACT walk keep plain refs
             const bool tok = kPair && pw && !(R.neg & kZeroDir);
-            st.base[-static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel | (tok ? kTokAlone : 0u));
-            if (!kFlatOnly) st.base[-2 * static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel | (tok ? kTokAlone : 0u));
+            if (!LINK) st.base[-static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel | (tok ? kTokAlone : 0u));
+            if (!LINK && !kFlatOnly) st.base[-2 * static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel | (tok ? kTokAlone : 0u));
             if (tok) R.cur = kTokAlone;
             if (kInvLds) {  // the f64 node test's 1 / d, divided once per ray (slab64_inv)
                 uint32_t t = threadIdx.x;
@@ -2067,12 +2116,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kMa
             } else if (!W.exact_slab && __ballot(R.state == kWalk && (R.neg & kZeroDir)) == 0) {
                 if (R.state == kWalk) {
                     if (!COUNT || W.count_spec)
-                        walk<SE, COUNT, false, kTopTreelet && !LSCENE, LSCENE, GSTACK, true, kInvLds, !kFlatOnly>(S, st, P.o, P.d, C.t_min, tmin32, R, ctr);
+                        walk<SE, COUNT, false, kTopTreelet && !LSCENE, LSCENE, GSTACK, true, kInvLds, !kFlatOnly, LINK>(S, st, P.o, P.d, C.t_min, tmin32, R, ctr);
                     else
-                        walk<SE, COUNT, false, kTopTreelet && !LSCENE, LSCENE, GSTACK, false, kInvLds>(S, st, P.o, P.d, C.t_min, tmin32, R, ctr);
+                        walk<SE, COUNT, false, kTopTreelet && !LSCENE, LSCENE, GSTACK, false, kInvLds, true, LINK>(S, st, P.o, P.d, C.t_min, tmin32, R, ctr);
                 }
             } else {
-                if (R.state == kWalk) walk<SE, COUNT, true, kTopTreelet && !LSCENE, LSCENE, GSTACK, false>(S, st, P.o, P.d, C.t_min, tmin32, R, ctr);
+                if (R.state == kWalk) walk<SE, COUNT, true, kTopTreelet && !LSCENE, LSCENE, GSTACK, false, false, true, LINK>(S, st, P.o, P.d, C.t_min, tmin32, R, ctr);
             }
             if (COUNT) cw += static_cast<uint32_t>(wall_clock64());
             set_prio<kPrioLeaf>();
@@ -2081,7 +2130,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kMa
                 if (wave_leader()) atomicAdd(&counters->round_leaves, nl);
             }
             if (COUNT) cl -= static_cast<uint32_t>(wall_clock64());
-            if (R.state == kLeaf) leaf_step<SE, COUNT, kTopTreelet && !LSCENE, LSCENE, kFast, kFlatOnly>(S, st, P.o, P.d, C.t_min, tmin32, kSphOnly || (!kFlatOnly && W.sphere_only != 0), !kFlatOnly && W.spheres_f32 != 0, kFlatOnly || (!kSphOnly && W.quads_f32 != 0), kFlatOnly || (!kSphOnly && W.quads_flat != 0), R, ctr);
+            if (R.state == kLeaf) leaf_step<SE, COUNT, kTopTreelet && !LSCENE, LSCENE, kFast, kFlatOnly, LINK>(S, st, P.o, P.d, C.t_min, tmin32, kSphOnly || (!kFlatOnly && W.sphere_only != 0), !kFlatOnly && W.spheres_f32 != 0, kFlatOnly || (!kSphOnly && W.quads_f32 != 0), kFlatOnly || (!kSphOnly && W.quads_flat != 0), R, ctr);
             if (COUNT) cl += static_cast<uint32_t>(wall_clock64());
             const uint64_t pending = __ballot(R.state == kWalk);
             const uint64_t finished = __ballot(R.state == kDone);
@@ -3162,6 +3211,7 @@ static dev::SceneView view_of(const DeviceCopy& c) {
     dev::SceneView v{c.nodes, c.fnodes, 0, c.refs, c.spheres, c.spair, 0, c.sphere_mat, c.quads, c.quad_mat,
                      c.mats, c.quadf, c.sphere_mrec, c.quad_mrec, 0, c.quadbox};
     v.guard = c.guard;
+    v.links = c.links;
     return v;
 }
 
@@ -3308,6 +3358,9 @@ static CopyFlags flags_of(const DeviceCopy& c) {
     return CopyFlags{c.f32_ok, c.spheres_f32_ok, c.quads_f32_ok, c.quads_flat_ok};
 }
 
+static bool u16_entries(const crt_scene* s);
+static void bind_links(crt_scene* s, DeviceCopy& c);
+
 // The pointers of a scene copy at `base` (device_layout's arrays at their offsets).
 void device_bind_copy(crt_scene* s, int device, void* base, size_t total) {
     size_t off[kArrCount + 1];
@@ -3336,6 +3389,78 @@ void device_bind_copy(crt_scene* s, int device, void* base, size_t total) {
     c.quad_mrec = reinterpret_cast<DevMaterial*>(b + off[kArrQuadMrec]);
     c.guard = reinterpret_cast<unsigned long long*>(b + off[kArrGuard]);
     c.valid = true;
+    bind_links(s, c);
+}
+
+// the nodes of the copy at `c` (device order), read back: 64 bytes a node, LDS-size trees only
+static bool copy_nodes_host(const crt_scene* s, const DeviceCopy& c, std::vector<DevNode>& out) {
+    out.resize(s->num_dnodes);
+    return hipMemcpy(out.data(), c.nodes, out.size() * sizeof(DevNode), hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+// The scene's miss-link table (crt_walk_links.h), built and checked on the host once per scene
+// (scene_walk_links: a wrong link would be an endless loop of a wave) and kept in crt_scene::links:
+// for trees whose refs fit u16 entries, the only ones an LDS-scene launch can take. From the host
+// staging's nodes, or for a scene set up on a device (no host arrays) from the nodes of the copy
+// `from`, read back. Without a table (too large, failed its check) the scene keeps the stack walk;
+// that is no error.
+static const std::vector<uint16_t>& scene_links(crt_scene* s, const DeviceCopy* from) {
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->links_built) return s->links;
+    if (u16_entries(s) && s->num_dnodes >= 2) {
+        if (s->image_device < 0) {
+            std::vector<DevNode> nodes(s->dnodes.begin(), s->dnodes.end());
+            (void)scene_walk_links(nodes.data(), nodes.size(), s->links);
+        } else if (from) {
+            std::vector<DevNode> nodes;
+            if (copy_nodes_host(s, *from, nodes)) (void)scene_walk_links(nodes.data(), nodes.size(), s->links);
+            else (void)hipGetLastError();
+        } else {
+            return s->links;  // a device-built scene whose copy is not bound yet: nothing to build from
+        }
+    }
+    s->links_built = true;
+    return s->links;
+}
+
+const std::vector<uint16_t>& device_walk_links(crt_scene* s) { return scene_links(s, nullptr); }
+
+// The table beside the image after either staging route (the image itself stays as it is), in a
+// small allocation of its own: the scene's stored bytes, padded to whole 16-byte rows for stage_lds.
+// A copy that cannot get one (no table, no memory) keeps the stack walk.
+static void bind_links(crt_scene* s, DeviceCopy& c) {
+    c.links = nullptr;
+    c.links_bytes = 0;
+    std::vector<uint16_t> table = scene_links(s, &c);
+    if (table.empty()) return;
+    const size_t bytes = (table.size() * sizeof(uint16_t) + 15) & ~size_t(15);
+    table.resize(bytes / sizeof(uint16_t), 0);
+    void* d = nullptr;
+    if (hipMalloc(&d, bytes) != hipSuccess || hipMemcpy(d, table.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        if (d) (void)hipFree(d);
+        return;
+    }
+    c.links = static_cast<uint16_t*>(d);
+    c.links_bytes = static_cast<uint32_t>(bytes);
+}
+
+int device_nodes_host(crt_scene* s, std::vector<DevNode>& out) {
+    out.clear();
+    if (!u16_entries(s)) return CRT_OK;  // beyond any table: none
+    if (s->image_device < 0) {  // host-built: the staging arrays
+        out.assign(s->dnodes.begin(), s->dnodes.end());
+        return CRT_OK;
+    }
+    std::lock_guard<std::mutex> lk(s->dev_mu[s->image_device]);
+    const DeviceCopy& c = s->dev[s->image_device];
+    if (!c.valid) return fail(CRT_E_NOT_UPLOADED, "the scene's device copy is gone");
+    DeviceGuard g(s->image_device);
+    if (!copy_nodes_host(s, c, out)) {
+        (void)hipGetLastError();
+        return fail(CRT_E_HIP, "reading the scene's nodes back failed");
+    }
+    return CRT_OK;
 }
 
 // Copy the scene into HBM of `device`: the staged image in one transfer. Uploads to different
@@ -3409,6 +3534,7 @@ void device_release(crt_scene* s) {
         DeviceGuard g(d);
         (void)hipFree(c.base);
         if (c.ref_prim) (void)hipFree(c.ref_prim);
+        if (c.links) (void)hipFree(c.links);
         c = DeviceCopy{};
     }
 }
@@ -3577,7 +3703,7 @@ static int pass_pool(int device, hipMemPool_t* out) {
     return CRT_OK;
 }
 
-template <typename SE, bool GSTACK, bool LSCENE, int PM, bool W5 = false>
+template <typename SE, bool GSTACK, bool LSCENE, int PM, bool W5 = false, bool LINK = false>
 static int launch_render(const crt_scene* s, int device, const crt_camera* cam, const dev::Work& w0,
                          size_t lds, double* d_rgb, hipStream_t stream, crt_render_stats* count_stats,
                          const RenderPass* pass) {
@@ -3587,8 +3713,8 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
     constexpr int kThreads = dev::kBlock;
     // a masked pass (adaptive sampling) launches the MASK instance over the active tiles' list
     const bool masked = pass && pass->blocks;
-    const void* kfn = masked ? reinterpret_cast<const void*>(dev::render_kernel<SE, GSTACK, LSCENE, false, PM, W5, true>)
-                             : reinterpret_cast<const void*>(dev::render_kernel<SE, GSTACK, LSCENE, false, PM, W5>);
+    const void* kfn = masked ? reinterpret_cast<const void*>(dev::render_kernel<SE, GSTACK, LSCENE, false, PM, W5, true, LINK>)
+                             : reinterpret_cast<const void*>(dev::render_kernel<SE, GSTACK, LSCENE, false, PM, W5, false, LINK>);
     const uint64_t pixels = static_cast<uint64_t>(W.owned_rows) * cam->image_w;
     // Sample chunks: a function of spp ONLY, so every pixel's sum is grouped identically whatever
     // the tiling / number of GPUs / lane schedule / band split (bit-identical frames for 1..N
@@ -3727,7 +3853,7 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
             }
 #endif
             if (count) {
-                hipLaunchKernelGGL((dev::render_kernel<SE, GSTACK, LSCENE, true, PM, W5>), dim3(static_cast<uint32_t>(blocks)),
+                hipLaunchKernelGGL((dev::render_kernel<SE, GSTACK, LSCENE, true, PM, W5, false, LINK>), dim3(static_cast<uint32_t>(blocks)),
                                    dim3(dev::kBlock), lds, stream, S, C, W, partial, gstack, ctr, nullptr);
                 HIP_TRY(hipGetLastError());
             } else if (masked) {
@@ -3735,7 +3861,7 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
                 hipLaunchKernelGGL(dev::active_list_kernel, dim3(1), dim3(dev::kListThreads), 0, stream, pass->blocks, W, ftx,
                                    pass->first, active);
                 HIP_TRY(hipGetLastError());
-                hipLaunchKernelGGL((dev::render_kernel<SE, GSTACK, LSCENE, false, PM, W5, true>), dim3(static_cast<uint32_t>(blocks)),
+                hipLaunchKernelGGL((dev::render_kernel<SE, GSTACK, LSCENE, false, PM, W5, true, LINK>), dim3(static_cast<uint32_t>(blocks)),
                                    dim3(dev::kBlock), lds, stream, S, C, W, partial, gstack, ctr, active);
                 HIP_TRY(hipGetLastError());
                 hipLaunchKernelGGL(dev::accumulate_masked_kernel, dim3((W.tiles + 3) / 4), dim3(256), 0, stream, partial,
@@ -3743,7 +3869,7 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
                                    pass->first + pass->count, inv_done);
                 HIP_TRY(hipGetLastError());
             } else {
-                hipLaunchKernelGGL((dev::render_kernel<SE, GSTACK, LSCENE, false, PM, W5>), dim3(static_cast<uint32_t>(blocks)),
+                hipLaunchKernelGGL((dev::render_kernel<SE, GSTACK, LSCENE, false, PM, W5, false, LINK>), dim3(static_cast<uint32_t>(blocks)),
                                    dim3(dev::kBlock), lds, stream, S, C, W, partial, gstack, ctr, nullptr);
                 HIP_TRY(hipGetLastError());
                 const uint64_t rb = (static_cast<uint64_t>(W.bw) * W.bh + 255) / 256;
@@ -3757,6 +3883,7 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
             }
         }
     }
+    c.last_walk = LINK ? CRT_WALK_LINKS : CRT_WALK_STACK;  // every band's launches were accepted
     if (count) HIP_TRY(hipEventRecord(e1, stream));
     if (partial) HIP_TRY(hipFreeAsync(partial, stream));
     HIP_TRY(hipFreeAsync(queue, stream));
@@ -3908,6 +4035,24 @@ static int dispatch_render(const crt_scene* s, int device, const crt_camera* cam
                            double* d_rgb, hipStream_t st, crt_render_stats* count_stats, const RenderPass* pass) {
     const Layout L = render_layout<SE>(s, W);
     const int pm = render_prim_mode(W, L.cls);
+    // The stackless walk (walk(), LINK): the timed five-wave sphere-only and flat-parallelogram
+    // instances, when the copy has a validated miss-link table (u16 entries) that fits the bytes the
+    // plan keeps for the guard levels and the stack, where it is staged; the plan itself is unchanged.
+    // Their instrumented pass (COUNT) walks the same way, so its counters are the link walk's (the
+    // stack walk's, node for node). Everything else walks with the stack. CRT_NO_LINK_WALK=1
+    // (read here, at the call) keeps the stack walk: the A/B switch of tests/test_gpu_link_walk.py.
+    if constexpr (std::is_same_v<SE, uint16_t>) {
+        const DeviceCopy& c = s->dev[device];
+        const size_t table = s->num_dnodes * 16;
+        if (L.cls == kQueryLdsScene && L.w5 && (pm == 0 || pm == 2) && c.links &&
+            c.links_bytes >= align16(table) && table <= 2 * L.level + L.stack_bytes &&
+            std::getenv("CRT_NO_LINK_WALK") == nullptr) {
+            W.lds_links = static_cast<uint32_t>(W.lds_stack - 2 * L.level);
+            W.bytes_links = static_cast<uint32_t>(align16(table));
+            return pm == 0 ? launch_render<SE, false, true, 0, true, true>(s, device, cam, W, L.lds, d_rgb, st, count_stats, pass)
+                           : launch_render<SE, false, true, 2, true, true>(s, device, cam, W, L.lds, d_rgb, st, count_stats, pass);
+        }
+    }
     switch (L.cls) {
     case kQueryLdsScene:
         if (pm == 0)

@@ -25,8 +25,15 @@
 
 #include "crt_internal.h"
 #include "crt_prims.h"
+#include "crt_walk_links.h"
 
 namespace crt {
+
+bool scene_walk_links(const DevNode* nodes, size_t n, std::vector<uint16_t>& links) {
+    if (build_walk_links(nodes, n, links) && validate_walk_links(nodes, n, links.data())) return true;
+    links.clear();
+    return false;
+}
 
 // ---------------------------------------------------------------------------------------------
 // errors
@@ -1815,6 +1822,43 @@ int crt_launch_plan(const crt_scene* s, uint32_t kernel, crt_launch_plan_info* o
     if (kernel > CRT_PLAN_RADIANCE) return fail(CRT_E_INVALID, "crt_launch_plan: unknown kernel");
     // the staged image is a cache the first upload would fill: the plan fills it the same way
     return device_launch_plan(const_cast<crt_scene*>(s), kernel, out);
+}
+
+int crt_walk_links(crt_scene* s, uint16_t* links, size_t capacity, size_t* num_nodes) {
+    clear_error();
+    if (!s || !num_nodes) return fail(CRT_E_INVALID, "crt_walk_links: null argument");
+    *num_nodes = 0;
+    // the stored table: the bytes every copy of the scene uploads
+    const std::vector<uint16_t>& table = device_walk_links(s);
+    if (table.empty()) return CRT_OK;
+    *num_nodes = table.size() / kWalkLinkOctants;
+    if (!links) return CRT_OK;
+    if (capacity < table.size())
+        return fail(CRT_E_INVALID, "crt_walk_links: capacity must be at least " + std::to_string(table.size()));
+    std::memcpy(links, table.data(), table.size() * sizeof(uint16_t));
+    return CRT_OK;
+}
+
+int crt_walk_links_validate(crt_scene* s, const uint16_t* links, size_t entries, int* ok) {
+    clear_error();
+    if (!s || !links || !ok) return fail(CRT_E_INVALID, "crt_walk_links_validate: null argument");
+    *ok = 0;
+    std::vector<DevNode> nodes;
+    const int rc = device_nodes_host(s, nodes);
+    if (rc) return rc;
+    if (entries != nodes.size() * kWalkLinkOctants)
+        return fail(CRT_E_INVALID, "crt_walk_links_validate: entries must be " +
+                                       std::to_string(nodes.size() * kWalkLinkOctants));
+    *ok = validate_walk_links(nodes.data(), nodes.size(), links) ? 1 : 0;
+    return CRT_OK;
+}
+
+int crt_last_walk(const crt_scene* s, int device, uint32_t* walk) {
+    clear_error();
+    if (!s || !walk) return fail(CRT_E_INVALID, "crt_last_walk: null argument");
+    if (device < 0 || device >= kMaxDevices) return fail(CRT_E_NODEVICE, "crt_last_walk: device out of range");
+    *walk = s->dev[device].last_walk;
+    return CRT_OK;
 }
 
 }  // extern "C"

@@ -297,6 +297,16 @@ struct DeviceCopy {
     // ref -> primitive number (spheres, then parallelograms), an allocation of its own made by the
     // first crt_render_features_async on this device (device_render_features)
     uint32_t* ref_prim = nullptr;
+    // the miss-link table of the stackless walk (crt_walk_links.h), a small allocation of its own
+    // beside the image: made when the copy is bound, for trees whose refs fit u16 entries, and only
+    // when the table validated (null: the scene keeps the stack walk)
+    uint16_t* links = nullptr;
+    uint32_t links_bytes = 0;
+    // The walk of the last render launch enqueued on this copy (crt_last_walk): CRT_WALK_*. A
+    // diagnostic for tests, written by the launcher after its launches were accepted: renders take
+    // the scene const, hence mutable, and it is not synchronized, so with launches on one copy from
+    // several threads it holds one of theirs. Nothing in the library reads it but crt_last_walk.
+    mutable uint32_t last_walk = 0;
 };
 
 // A flattened primitive (Scene::get_primitive_components order) with the derived data the
@@ -343,7 +353,11 @@ struct crt_scene {
     crt::BigVec<char> image;
     bool staged = false;
     bool image_f32_ok = false, image_spheres_f32_ok = false, image_quads_f32_ok = false, image_quads_flat_ok = false;
-    std::mutex mu;  // staging
+    // the miss-link table of the stackless walk (crt_walk_links.h), built and validated once (under
+    // mu; device_walk_links): the bytes every copy uploads and crt_walk_links returns. Empty: none.
+    std::vector<uint16_t> links;
+    bool links_built = false;
+    std::mutex mu;  // staging, links
 };
 
 namespace crt {
@@ -489,6 +503,16 @@ int device_build_bvh(crt_scene* s, uint32_t num_buckets, uint32_t max_leaf, int 
                      const BigVec<double>& boxes);
 void device_bind_copy(crt_scene* s, int device, void* base, size_t total);
 int device_image(crt_scene* s, int device, void* host, size_t bytes);
+// the device-order nodes of a scene (crt_walk_links_validate): the host staging's, or for a scene set
+// up on a device the ones in that device's copy, read back under that device's lock
+int device_nodes_host(crt_scene* s, std::vector<DevNode>& out);
+// the scene's stored miss-link table (crt_scene::links; empty: none), built on first use for a
+// host-built scene; a scene set up on a device got it when its copy there was bound
+const std::vector<uint16_t>& device_walk_links(crt_scene* s);
+// The miss-link table of `n` device-order nodes (crt_host.cpp, from crt_walk_links.h): built, then
+// validated; false with `links` empty when the tree has no table (refs beyond u16, parents not
+// before their children) or the table fails its check.
+bool scene_walk_links(const DevNode* nodes, size_t n, std::vector<uint16_t>& links);
 // A tree built on the current device (crt_bvh_gpu.hip): the preorder node array (bvh.h:468-550)
 // and the slot order in HBM.
 struct DeviceTree {

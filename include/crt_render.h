@@ -960,6 +960,31 @@ typedef struct crt_launch_plan_info {
 } crt_launch_plan_info; /* 200 bytes */
 int crt_launch_plan(const crt_scene* scene, uint32_t kernel, crt_launch_plan_info* out);
 
+/* ---- the stackless walk's miss links ----------------------------------------------------- */
+/* The five-wave LDS-scene render instances walk the BVH without a stack: a ray's DFS order is
+ * fixed by the signs of its direction (its octant: bit k set when d[k] < 0), so the node a pop
+ * would return is a function of (node, octant), tabulated once per scene. Additions to the ABI (no
+ * existing call changes, CRT_ABI_VERSION stays).
+ * crt_walk_links: the table of `scene` over its device-order nodes (the pad and the sentinel
+ * included): 8 uint16 entries a node, entry [node * 8 + octant] = the reference (node index * 32)
+ * of the node the walk continues at when it does not descend from `node`. It is the table stored
+ * with the scene (built and validated once), the bytes every device copy uploads. Host only for a
+ * host-built scene; a scene built on a device got it from that device's nodes at its creation.
+ * *num_nodes = the nodes of the table, 0 when the scene has none (its references do not fit 16
+ * bits, or the table did not validate); `links` may be null to ask for the size, else `capacity`
+ * (entries) must be at least 8 * *num_nodes.
+ * crt_walk_links_validate: the check every upload runs, on a caller's table for `scene`: *ok = 1
+ * when under each octant every link is the node that follows the node's subtree in that octant's
+ * DFS order and following links from any node reaches the sentinel within num_nodes steps.
+ * crt_last_walk: the walk the last render launch on `device` took for `scene`
+ * (crt_render_async, its pass forms, crt_render_count, the blocking renders): CRT_WALK_NONE before
+ * the first one. A diagnostic, not synchronized: with renders of one scene copy from several threads
+ * it is one of theirs. CRT_NO_LINK_WALK=1, read at each launch, keeps every launch on the stack walk. */
+enum { CRT_WALK_NONE = 0, CRT_WALK_STACK = 1, CRT_WALK_LINKS = 2 };
+int crt_walk_links(crt_scene* scene, uint16_t* links, size_t capacity, size_t* num_nodes);
+int crt_walk_links_validate(crt_scene* scene, const uint16_t* links, size_t entries, int* ok);
+int crt_last_walk(const crt_scene* scene, int device, uint32_t* walk);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,18 @@ def main():
         out.append({"phase": label, "wave_iterations": it, "valu_per_iteration": n, "per_iteration": dict(m),
                     "dynamic": dyn})
         print(f"{label:26s} {it:10.3e} {n:8d} " + " ".join(f"{m[c]:11d}" for c in CLASSES) + f" {n * it:10.3e}")
+    # the walk step's memory instructions per iteration: a stack instance reads the node (two
+    # ds_read_b128, or global loads) and the stack top and stores the far child; a link instance
+    # (render_kernel LINK) reads the node and its u16 miss link and stores nothing
+    mem = collections.Counter()
+    for b in walk_main:
+        for x in b["ins"]:
+            op = x.split()[0]
+            for k in ("ds_read", "ds_write", "global_load", "global_store", "scratch_"):
+                if op.startswith(k):
+                    mem[k.rstrip("_")] += 1
+    print(f"{'walk step memory ops':26s} " + " ".join(f"{k} {v}" for k, v in sorted(mem.items())))
+    out.append({"phase": "walk step memory ops", "per_iteration": dict(mem)})
     acc = sum(total.values())
     print(f"{'sum of the four':26s} {'':10s} {'':8s} " + " ".join(f"{total[c]:11.3e}" for c in CLASSES) + f" {acc:10.3e}")
     if pmc:
