@@ -27,6 +27,7 @@
 #include "crt_hip_util.h"
 #include "crt_rows.h"
 #include "crt_ray_class.h"
+#include "crt_ray_gate.h"
 #include "crt_schlick.h"
 
 #pragma clang fp contract(off)
@@ -349,10 +350,13 @@ __device__ __forceinline__ bool slab(const NodeRegs& n, const double o[3], const
 
 // Reciprocal of a ray's dot(d, d) for div_a: ia = RN(1 / a), or NaN when a is outside the range
 // where div_a's corrections are exact (then div_a divides).
+// (in_range: gate_recip(a), crt_ray_gate.h)
 template <bool FAST = false>
-__device__ __forceinline__ double recip_a(double a) {
-    return (a >= 0x1p-500 && a <= 0x1p500) ? (FAST ? recip_core(a) : 1 / a) : __builtin_nan("");
+__device__ __forceinline__ double recip_a(double a, bool in_range) {
+    return in_range ? (FAST ? recip_core(a) : 1 / a) : __builtin_nan("");
 }
+template <bool FAST = false>
+__device__ __forceinline__ double recip_a(double a) { return recip_a<FAST>(a, gate_recip(a)); }
 
 // n / a correctly rounded from ia = RN(1/a): q0 = n * ia, then two residual corrections
 // q += fma(-a, q, n) * ia (Markstein's theorem: with ia = RN(1/a) and q within 1 ulp, the
@@ -408,6 +412,38 @@ __device__ __forceinline__ bool hit_sphere(const DevSphere& sp, const double o[3
 // v_min/v_max(3)_f32 of non-NaN operands. Written out because fminf/fmaxf make the compiler
 // quieten possible signalling NaNs of operands it cannot prove canonical (tmin', tmax') with an
 // extra v_max each, in every walk step.
+// v_cndmask_b32 with a lane mask from a ballot (scalar registers): m ? a : b per lane
+__device__ __forceinline__ uint32_t vsel(uint64_t m, uint32_t a, uint32_t b) {
+    uint32_t r;
+    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
+    return r;
+}
+
+// The walk's step on the lanes of `on` alone (an exec-masked select: the other lanes keep
+// `keep`): m ? a : top, zero-extended. A 16-bit `top` fresh from a load has its register's high
+// half undefined yet; SDWA reads the low word, where a plain select would need a v_and first.
+// (s_and_saveexec writes SCC: clobbered.)
+__device__ __forceinline__ uint32_t vsel_top_on(uint64_t on, uint64_t m, uint32_t a, uint16_t top, uint32_t keep) {
+    uint64_t save;
+    asm("s_and_saveexec_b64 %[save], %[on]\n\t"
+        "s_mov_b64 vcc, %[m]\n\t"
+        "v_cndmask_b32_sdwa %[r], %[b], %[a], vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:DWORD\n\t"
+        "s_mov_b64 exec, %[save]"
+        : [r] "+v"(keep), [save] "=&s"(save)
+        : [a] "v"(a), [b] "v"(__builtin_bit_cast(_Float16, top)), [m] "s"(m), [on] "s"(on)
+        : "vcc", "scc");
+    return keep;
+}
+__device__ __forceinline__ uint32_t vsel_top_on(uint64_t on, uint64_t m, uint32_t a, uint32_t top, uint32_t keep) {
+    uint64_t save;
+    asm("s_and_saveexec_b64 %[save], %[on]\n\t"
+        "v_cndmask_b32_e64 %[r], %[b], %[a], %[m]\n\t"
+        "s_mov_b64 exec, %[save]"
+        : [r] "+v"(keep), [save] "=&s"(save)
+        : [a] "v"(a), [b] "v"(top), [m] "s"(m), [on] "s"(on)
+        : "scc");
+    return keep;
+}
 __device__ __forceinline__ float vmin(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float vmax(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float vmin3(float a, float b, float c) {
@@ -489,12 +525,7 @@ __device__ __forceinline__ void leaf_ray32(const double o[3], const double d[3],
     L.akap = F2{static_cast<float>(a), static_cast<float>(e2 * 0x1p22 + 0x1p-50)};
     L.hilo = F2{static_cast<float>(tmax * a * (1 + 0x1p-20)), static_cast<float>(tmin * a * (1 - 0x1p-20))};
 }
-__device__ __forceinline__ bool leaf_ray32_ok(const double o[3], const double d[3], double a) {
-    bool ok = a >= 0x1p-60 && a <= 0x1p60;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ok = ok && fabs(o[k]) <= 0x1p30 && fabs(d[k]) <= 0x1p30;
-    return ok;
-}
+// (leaf_ray32's ranges: gate_leaf32, crt_ray_gate.h; trav_init keeps the verdict in Trav::neg)
 __device__ __forceinline__ float vmul_abs(float a, float b) {  // a * |b|
     float r;
     asm("v_mul_f32 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b));
@@ -786,6 +817,10 @@ __device__ __forceinline__ bool trace(const SceneView& S, Stack<SE>& st, const d
 enum : uint32_t { kWalk = 0, kLeaf = 1, kDone = 2, kIdle = 3 };
 
 constexpr uint32_t kZeroDir = 8u;
+// Trav::neg bits 4, 5: the ray is outside leaf_ray32's ranges (gate_leaf32) / div_a's (gate_recip).
+// Clear for every ray that passes ray_gate (crt_ray_gate.h). The walks index Trav::neg by a node's
+// split axis (0-2; 3 at the sentinel), so the bits are out of their way.
+constexpr uint32_t kNoLeaf32 = 16u, kNoRecip = 32u;
 
 struct Trav {
     // f32 copies for the walk's node test (walk()): inv32 = RN32(1/d), oinv32 = RN32(o * (1/d)),
@@ -798,7 +833,9 @@ struct Trav {
     uint32_t cur, ref;
     int32_t sp;      // stack levels in use; -1 after the pop that follows the last leaf
     uint32_t first, count;  // the entered leaf's primitive range (walk -> leaf_step)
-    uint32_t neg;    // bit k: d[k] < 0; kZeroDir: a slab value may be NaN (walk_step EXACT)
+    uint32_t neg;    // bit k: d[k] < 0; kZeroDir: a slab value may be NaN (walk_step EXACT);
+                     // kNoLeaf32: outside leaf_ray32's ranges (leaf_step tests every sphere
+                     // exactly); kNoRecip: dot(d, d) outside div_a's range (it divides)
     uint32_t state;
     bool found;
 };
@@ -806,8 +843,6 @@ struct Trav {
 __device__ __forceinline__ bool finite_nonzero(double x) { return fabs(x) < __builtin_inf() && x != 0; }
 __device__ __forceinline__ bool finite(double x) { return fabs(x) < __builtin_inf(); }
 __device__ __forceinline__ float tmax_f32(double t) { return static_cast<float>(fmin(t, 0x1p100)); }
-
-__device__ __forceinline__ bool dir_ok(double x) { return fabs(x) >= 0x1p-1000 && fabs(x) <= 0x1p1000; }
 
 // f32_ok: the scene's node bounds fit the f32 error analysis (Work::f32_ok)
 __device__ __forceinline__ void trav_init(const double o[3], const double d[3], bool f32_ok, Trav& R) {
@@ -817,27 +852,34 @@ __device__ __forceinline__ void trav_init(const double o[3], const double d[3], 
     R.cur = 0;
     R.sp = 0;
     R.ref = 0;
-    // NaN-free slab values (the min/max and f32 walks): 1/d finite and non-zero, o finite. Rays
-    // with a direction component outside [2^-1000, 2^1000] (zero, tiny, huge, NaN) take the EXACT
-    // walk, which is the reference's select sequence for any ray.
-    const bool fast = dir_ok(d[0]) && dir_ok(d[1]) && dir_ok(d[2]) &&
-                      finite(o[0]) && finite(o[1]) && finite(o[2]);
-    R.neg = (d[0] < 0 ? 1u : 0u) | (d[1] < 0 ? 2u : 0u) | (d[2] < 0 ? 4u : 0u) | (fast ? 0u : kZeroDir);
     // The f32 walk's ray constants, in f32 (v12): inv32 = v_rcp_f32(RN32(d)) (within 1 ulp of
     // 1/RN32(d), so within 3.01u of 1/d), oinv32 = RN32(RN32(o) * inv32) (within 5.02u of o/d);
     // walk() bounds the resulting slab values for these. The analysis holds for
-    // 2^-40 <= |1/d_k| <= 2^40 and |o_k| <= 2^40, here ensured by 2^-39 <= |RN32(d_k)| <= 2^39;
-    // other rays get marg = inf, i.e. every node test decided in f64.
-    bool f32 = f32_ok;
-    float A = 0;
+    // 2^-40 <= |1/d_k| <= 2^40 and |o_k| <= 2^40, here ensured by 2^-39 <= |RN32(d_k)| <= 2^39
+    // (gate_walk_f32); other rays get marg = inf, i.e. every node test decided in f64.
+    float d32[3], o32[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const float d32 = static_cast<float>(d[k]), o32 = static_cast<float>(o[k]);
-        R.inv32[k] = __builtin_amdgcn_rcpf(d32);
-        R.oinv32[k] = o32 * R.inv32[k];
-        A = __builtin_fmaxf(A, __builtin_fabsf(R.oinv32[k]));
-        f32 = f32 && __builtin_fabsf(d32) <= 0x1p39f && __builtin_fabsf(d32) >= 0x1p-39f &&
-              __builtin_fabsf(o32) <= 0x1p40f;
+        d32[k] = static_cast<float>(d[k]);
+        o32[k] = static_cast<float>(o[k]);
+        R.inv32[k] = __builtin_amdgcn_rcpf(d32[k]);
+        R.oinv32[k] = o32[k] * R.inv32[k];
+    }
+    // (read only where f32 holds below: no NaN among the three then)
+    const float A = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(R.oinv32[0]), __builtin_fabsf(R.oinv32[1])),
+                                    __builtin_fabsf(R.oinv32[2]));
+    // bit k: d[k] < 0 (not the sign bit: -0.0 is not negative)
+    R.neg = (d[0] < 0 ? 1u : 0u) | (d[1] < 0 ? 2u : 0u) | (d[2] < 0 ? 4u : 0u);
+    bool f32 = f32_ok;
+    // The range checks of this ray, all four implied by ray_gate (the proof is in crt_ray_gate.h);
+    // a wave with a lane outside the gate evaluates them one by one, as every set-up used to.
+    // NaN-free slab values (the min/max and f32 walks): 1/d finite and non-zero, o finite. Rays
+    // with a direction component outside [2^-1000, 2^1000] (zero, tiny, huge, NaN) take the EXACT
+    // walk, which is the reference's select sequence for any ray.
+    if (__builtin_expect(__ballot(!ray_gate(o32, d32)) != 0, 0)) {
+        f32 = f32 && gate_walk_f32(o32, d32);
+        R.neg |= (gate_walk_plain(o, d) ? 0u : kZeroDir) | (gate_leaf32(o, d, R.a) ? 0u : kNoLeaf32) |
+                 (gate_recip(R.a) ? 0u : kNoRecip);
     }
     R.marg = f32 ? __builtin_fmaxf(A * 0x1p-19f, 0x1p-60f) : __builtin_inff();
     R.state = kWalk;
@@ -1038,9 +1080,10 @@ __device__ __forceinline__ Uvec2 fetch_nodef_words(const SceneView& S, uint32_t 
 
 // The lane's miss link at node ref `cur` (LINK instances): lbase = S.links_lds + 2 * octant
 typedef __attribute__((address_space(3))) const uint16_t LdsU16;
-__device__ __forceinline__ uint32_t link_at(uint32_t lbase, uint32_t cur) {
+__device__ __forceinline__ uint16_t link16_at(uint32_t lbase, uint32_t cur) {
     return *(LdsU16*)static_cast<uintptr_t>(lbase + (cur >> 1));
 }
+__device__ __forceinline__ uint32_t link_at(uint32_t lbase, uint32_t cur) { return link16_at(lbase, cur); }
 
 // ---- the stackless form (LINK: the five-wave LDS-scene render instances) -----------------------
 // BVH::hit_by (bvh.h:684-698) picks the near child by dir_is_negative[split_axis] alone, so a
@@ -1059,7 +1102,7 @@ __device__ __forceinline__ uint32_t link_at(uint32_t lbase, uint32_t cur) {
 // the visited node sequence is the stack walk's, and every primitive test, tie and frame bit
 // stays the same. The speculative walk's argument above (monotone node test, t_max only shrinking)
 // speaks of the order of the nodes alone and never of the stack, so it holds as it stands; a
-// parked lane remembers its node (`pcur`) with no pop to undo.
+// parked lane stays on its node.
 template <typename SE, bool COUNT, bool EXACT, bool TOP, bool LS, bool GS, bool SPEC, bool INVL = false, bool G2 = true,
           bool LINK = false>
 __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const double o[3], const double d[3],
@@ -1091,7 +1134,8 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
         // divided here: without the barrier the compiler hoists these three divisions out of
         // the traversal rounds into every shade round, although the EXACT walk is rare
         double dx = d[0], dy = d[1], dz = d[2];
-        asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz));
+        uint32_t neg = R.neg;  // likewise the three sign masks
+        asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz), "+v"(neg));
         const double inv[3] = {1 / dx, 1 / dy, 1 / dz};
         do {
             NodeLines nd;
@@ -1103,7 +1147,7 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
                 if (wave_leader()) ctr.it_walk++;
             }
             // x[neg] / x[!neg]
-            const bool nx = R.neg & 1u, ny = (R.neg >> 1) & 1u, nz = (R.neg >> 2) & 1u;
+            const bool nx = neg & 1u, ny = (neg >> 1) & 1u, nz = (neg >> 2) & 1u;
             const double bx0 = nx ? nd.b[0].y : nd.b[0].x, bx1 = nx ? nd.b[0].x : nd.b[0].y;
             const double by0 = ny ? nd.b[1].y : nd.b[1].x, by1 = ny ? nd.b[1].x : nd.b[1].y;
             const double bz0 = nz ? nd.b[2].y : nd.b[2].x, bz1 = nz ? nd.b[2].x : nd.b[2].y;
@@ -1122,7 +1166,7 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
             const bool enter = (c1 & c2 & (xtmin < R.tmax) & (xtmax > tmin)) |
                                (meta.y != 0 && (meta.w & kNodeAlways) != 0) | (meta.y == kSentinelCount);
             const bool inner = enter & (meta.y == 0);
-            const bool far_first = (R.neg >> meta.z) & 1u;
+            const bool far_first = (neg >> meta.z) & 1u;
             const uint32_t left = meta.w << kNodeFShift, right = meta.x << kNodeFShift;
             if (!LINK) tp[stride] = static_cast<SE>(far_first ? left : right);
             stop = enter ^ inner;  // entered, not interior: a leaf or the sentinel
@@ -1145,21 +1189,45 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
         // values are monotone in the bounds (near(child) >= near(parent), far(child) <=
         // far(parent)), so the test fails for them at any t_max the culled one failed at.
         // Only node visits are added. The stack stays within depth + 1 levels: it is the same DFS.
-        // The loop is the wave's; parked lanes leave it through the exec mask (`run`). A lane
-        // parks by popping like at any entered leaf and remembering the node (`pcur`); after the
-        // loop its pop is undone. The recorded node is `pref` (~0u: none yet; the sentinel when
-        // the lane entered it with no leaf recorded: traversal over), so the loop's exit test is
-        // one compare.
-        bool run = true, nopend = true;
-        uint32_t pref = ~0u, pcur = 0;
-        do {
+        // The loop is the wave's, and a divergent one: a parking lane leaves it (`break`), which
+        // takes it out of the exec mask of every later step; the loop ends for the lanes still in
+        // it when no lane of the wave is on its way to a first leaf any more. A lane parks by not
+        // moving: the step's update of `cur` and of the stack pointer is made on the lanes of
+        // exec & ~park alone (vsel_top_on), so the lane keeps the parked node and, in the stack
+        // forms, the stack pointer of before the step (what popping, remembering the node and
+        // undoing the pop after the loop gave, for a select a step and a VGPR more).
+        // Whether a lane still walks to its first leaf is the lane mask `nop` (scalar registers),
+        // cleared by scalar logic at that leaf (or at the sentinel when the lane entered it with
+        // no leaf recorded: traversal over); the recorded node is `pref`. The loop's exit test is
+        // a scalar compare of the mask, and every lane leaves the loop with a node recorded, so
+        // `pref` needs no "none yet" value and no compare of its own.
+        // The node sequence is unchanged: a running lane's `cur`, stack pointer and stack
+        // stores are exactly those of the pop-and-undo form at every step (the parking step is
+        // the lane's last, and its unconditional store at tp[stride] lands where it always did);
+        // `nop` is cleared in the very step in which `pref` used to leave ~0u, so `park` and the
+        // loop's trip count are the same; and a parked lane ends on the same (cur, tp) as after
+        // the undo.
+        // How it is written follows the compiler: masks come from ballots of fresh
+        // compares only (a ballot of a lane boolean merged across blocks costs two vector
+        // instructions); `nop` is updated in the loop's own body, not under an `if`, or it moves
+        // to VGPRs; `park` exists as a lane boolean too, for the break, built from positive terms
+        // (`rec` = a leaf is recorded, the complement of `nop`), because every negated lane
+        // boolean is answered with the inverse vector compare.
+        bool rec = false;
+        uint64_t nop = __ballot(true);  // the lanes of this call
+        uint32_t pref = 0;
+        for (;;) {
             CRT_WD(4, cur, static_cast<uint32_t>(tp - empty));
-            if (run) {
+            {
                 Uvec4 q0, q1;
                 fetch_nodef<TOP, LS>(S, cur, q0, q1);
                 w0 = q1.z;
                 w1 = q1.w;
-                const uint32_t top = LINK ? link_at(lbase, cur) : *tp;  // speculative pop
+                // speculative pop, in its own width (vsel_top_on)
+                const auto top = [&] {
+                    if constexpr (LINK) return link16_at(lbase, cur);
+                    else return *tp;
+                }();
                 if (COUNT) {
                     if (w1 != kSentinelW1) ctr.nodes++;
                     if (wave_leader()) ctr.it_walk++;
@@ -1174,37 +1242,46 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
                 const float hi = vmin3(vmax(x0, x1), vmax(y0, y1), vmin(vmax(z0, z1), R.tmax32));
                 const float gap = hi - lo;
                 const float th = __builtin_fmaf(vmax_abs(lo, hi), 0x1p-19f, R.marg);
-                bool enter = gap > 0.f;
+                // The step's outcomes as lane masks (ballots of the compares: scalar algebra, and
+                // selects on the masks). The f64 decision comes back as the sign of `dec`, so that
+                // "entered" is one compare after the rare branch and not a boolean merged across
+                // it. Only `park` is a lane boolean as well (the loop's divergent exit), built
+                // from the same two compares.
+                float dec = gap;
                 const bool unc = !(fabsf(gap) > th);
                 if (__builtin_expect(__ballot(unc) != 0, 0)) {
                     if (COUNT && wave_leader()) ctr.it_slow++;
                     if (unc) {
                         if (COUNT) ctr.slow_nodes++;
-                        enter = INVL ? slab64_inv(node64(S, cur), o, S.inv64_lds, tmin, R.tmax)
-                                     : slab64(node64(S, cur), o, d, tmin, R.tmax);
+                        dec = (INVL ? slab64_inv(node64(S, cur), o, S.inv64_lds, tmin, R.tmax)
+                                    : slab64(node64(S, cur), o, d, tmin, R.tmax)) ? 1.f : -1.f;
                     }
                 }
-                const bool inner = enter & (w1 < kLeafFlagF);
+                const bool enter = dec > 0.f, leaf = w1 >= kLeafFlagF;  // leaf: or the sentinel
+                const uint64_t em = __ballot(enter), lm = __ballot(leaf);
+                const uint64_t im = em & ~lm;  // entered, interior
+                const uint64_t rm = em & lm;   // reached: entered a leaf or the sentinel
                 const uint32_t near = w1 | (__builtin_amdgcn_ubfe(R.neg, w0, 1) << kNodeFShift);
                 if (!LINK) tp[stride] = static_cast<SE>(near ^ (1u << kNodeFShift));
-                const bool reached = enter & !inner;  // a leaf or the sentinel
                 // a lane that reaches the sentinel with no leaf recorded records it and pops the
-                // second guard level, which holds the sentinel too: it parks there, with a leaf
-                // recorded (one compare fewer a step than testing for the sentinel here; G2 =
-                // false: the compare, for the flat-parallelogram instances, whose five-wave
-                // register allocation spilled 14 VGPRs instead of 8 without it)
-                const bool park = reached & (!nopend | (!G2 && w1 == kSentinelW1));
-                pref = (reached & nopend) ? cur : pref;  // the first leaf (or the sentinel)
-                pcur = park ? cur : pcur;
-                run = !park;
-                cur = inner ? near : top;
-                if (!LINK) tp += inner ? stride : -stride;
+                // second guard level, which holds the sentinel too (LINK: follows the sentinel's
+                // link to itself): it parks there, with a leaf recorded (one compare fewer a step
+                // than testing for the sentinel here; G2 = false: the compare, for the
+                // flat-parallelogram instances, whose five-wave register allocation spilled 14
+                // VGPRs instead of 8 without it)
+                const bool reached = enter && leaf;
+                const bool park = reached && (rec || (!G2 && w1 == kSentinelW1));
+                const uint64_t pm = rm & (G2 ? ~nop : (~nop | __ballot(w1 == kSentinelW1)));
+                pref = vsel(rm & nop, cur, pref);  // the first leaf (or the sentinel)
+                nop &= ~rm;
+                rec = rec || reached;
+                // a parking lane stays on its node, its stack pointer unmoved, and leaves the loop
+                const uint64_t on = __ballot(true) & ~pm;
+                cur = vsel_top_on(on, im, near, top, cur);
+                if (!LINK) tp += static_cast<int32_t>(vsel(im & on, static_cast<uint32_t>(stride), vsel(on, static_cast<uint32_t>(-stride), 0u)));
+                if (park) break;
             }
-            nopend = pref == ~0u;
-        } while (__ballot(nopend) != 0);
-        if (!run) {  // parked: back at the node, its pop undone
-            cur = pcur;
-            if (!LINK) tp += stride;
+            if (nop == 0) break;
         }
         // the recorded node's words (a leaf's primitive range, or the sentinel: traversal over)
         {
@@ -1310,13 +1387,6 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
 // the reference's DFS on random trees.
 
 constexpr uint32_t kTokAlone = 1u;  // token bit 0: the first node alone (root, sentinel, re-tests)
-
-// v_cndmask_b32 with a lane mask from a ballot (scalar registers): m ? a : b per lane
-__device__ __forceinline__ uint32_t vsel(uint64_t m, uint32_t a, uint32_t b) {
-    uint32_t r;
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
-    return r;
-}
 
 // The step's two f32 nodes: f (the first) and g = f ^ 32, read from the LDS treelet or from HBM
 // (the treelet holds whole sibling pairs, render_layout, so f and g are on the same side),
@@ -1473,9 +1543,9 @@ __device__ __forceinline__ void leaf_step(const SceneView& S, Stack<SE>& st, con
                                               bool qfilter, bool qflat, Trav& R, LaneCounters& ctr) {
     const uint2 range = make_uint2(R.first, R.count);  // index, count
     const uint32_t end = range.x + range.y;
-    const double ia = recip_a<FAST>(R.a), lo = lim_tmin(tmin, R.a);
+    const double ia = recip_a<FAST>(R.a, !(R.neg & kNoRecip)), lo = lim_tmin(tmin, R.a);
     double hi = lim_tmax(R.tmax, R.a);
-    if (!QONLY && pairs && range.y <= 32 && leaf_ray32_ok(o, d, R.a)) {
+    if (!QONLY && pairs && range.y <= 32 && !(R.neg & kNoLeaf32)) {
         // two passes: the packed f32 candidate filter over every sphere against the leaf-entry
         // t_max, then the full test of the candidates in slot order with the shrinking t_max. A
         // sphere the first pass rejects is rejected by the full test for any smaller t_max too,
