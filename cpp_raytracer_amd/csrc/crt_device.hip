@@ -1389,7 +1389,7 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
 constexpr uint32_t kTokAlone = 1u;  // token bit 0: the first node alone (root, sentinel, re-tests)
 
 // The step's two f32 nodes: f (the first) and g = f ^ 32, read from the LDS treelet or from HBM
-// (the treelet holds whole sibling pairs, render_layout, so f and g are on the same side),
+// (the treelet holds whole sibling pairs, scene_layout, so f and g are on the same side),
 // both sides in flight together as in fetch_nodef.
 template <bool TOP>
 __device__ __forceinline__ void fetch_two(const SceneView& S, uint32_t f, uint32_t g, Uvec4& a0, Uvec4& a1, Uvec4& b0,
@@ -1925,30 +1925,11 @@ __device__ __forceinline__ void set_prio() {
     if constexpr ((kPrioWalk | kPrioLeaf | kPrioShade | kPrioInit) != 0) __builtin_amdgcn_s_setprio(P);
 }
 
-// PM (primitive mix): 0 sphere-only scenes (every parallelogram path compiled out), 1 any scene,
-// 2 parallelogram-only scenes of axis-aligned parallelograms (LDS scenes: the flat-box filter
-// only, no sphere paths)
-// W5: 5 waves per SIMD (96 VGPRs, ~40-48 of them spilled), launched for sphere-only and
-// flat-parallelogram LDS scenes whose LDS copy leaves room for five blocks per CU (render_layout)
-// MASK: the masked pass of an adaptive render (crt_render_pass_masked_async). The queues run over
-// the band's active tiles only: active[0] = their number, active[1 + i] = the band tile of list
-// entry i, in tile-major order (active_list_kernel). A separate instance: the unmasked instances
-// keep their code.
-// LINK: the stackless walk over the scene's miss links (walk(), LINK), launched for the five-wave
-// sphere-only and flat-parallelogram instances when the table exists and fits the stack region
-// (dispatch_render); no Stack, no guard levels, no sentinel stores in the traversal set-up.
-template <typename SE, bool GSTACK, bool LSCENE, bool COUNT, int PM, bool W5, bool MASK = false, bool LINK = false>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kManyWaves : LSCENE ? CRT_WAVES_PER_EU_LDS : CRT_WAVES_PER_EU, 8))) void render_kernel(
-    SceneView Sg, CamView C, Work W, double* __restrict__ partial, SE* __restrict__ gstack,
-    Counters* __restrict__ counters, const uint32_t* __restrict__ active) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // the instances with PM = 0 are launched for sphere-only scenes only, PM = 2 for scenes of
-    // axis-aligned parallelograms only: the other primitive's paths are compiled out of them
-    constexpr bool kSphOnly = PM == 0, kFlatOnly = PM == 2;
-    // sqrt / reciprocal expansions without range fix-ups (sqrt_exact, recip_exact): measured
-    // faster only in the five-wave sphere-only instance
-    constexpr bool kFast = kSphOnly && W5;
-    SceneView S = Sg;
+// ---- what the persistent-wave kernels (render_kernel, query_kernel, radiance_kernel) share ------
+// The scene staging, without its barrier (the caller's). LSCENE: nodes, primitive refs, spheres and
+// parallelograms go to LDS and S points there; else the first W.ntop bytes of f32 nodes do.
+template <bool LSCENE, bool LINK>
+__device__ __forceinline__ void stage_scene(unsigned char* smem, const SceneView& Sg, const Work& W, SceneView& S) {
     if (LSCENE) {  // f32 nodes at LDS offset 0 (fetch_nodef: a node's LDS address is its ref)
         if (static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsByte*)smem)) != 0) __builtin_trap();
         stage_lds(smem, Sg.fnodes, W.bytes_nodes);
@@ -1978,13 +1959,148 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kMa
             S.links_lds = W.lds_links;
             S.sentinel = W.sentinel;
         }
-        __syncthreads();
     } else if (W.ntop) {  // HBM scene: keep the first ntop bytes of f32 nodes (top levels) in LDS
         if (static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsByte*)smem)) != 0) __builtin_trap();
         stage_lds(smem, Sg.fnodes, W.ntop);
         S.ntop = W.ntop;
-        __syncthreads();
     }
+}
+
+// The lane's stack: levels 0..depth above two guard levels holding the sentinel reference and one
+// more level walk() may read (three levels in HBM; in LDS that one is other data). LINK: no stack,
+// its bytes hold the miss links.
+template <typename SE, bool GSTACK, bool LINK>
+__device__ __forceinline__ Stack<SE> lane_stack(unsigned char* smem, SE* gstack, const Work& W) {
+    Stack<SE> st{};
+    if (LINK) return st;
+    if (GSTACK) {
+        st.stride = gridDim.x * kBlock;
+        st.base = gstack + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x) + 3 * static_cast<size_t>(st.stride);
+    } else {
+        st.base = reinterpret_cast<SE*>(smem + W.lds_stack) + threadIdx.x;
+        st.stride = kBlock;
+    }
+    st.base[-static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel);
+    st.base[-2 * static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel);
+    return st;
+}
+
+typedef __attribute__((address_space(3))) double LdsDouble;
+// the sibling-pair walk (walk_pairs) of the HBM-scene instances
+template <bool LSCENE>
+constexpr bool kPairWalk = CRT_PAIR_WALK && !LSCENE;
+
+// One ray's traversal set-up, for new rays and scattered ones alike. The guard levels get the
+// sentinel back (the f32 walk's store at the sentinel overwrote it). pw: the pair walk's lanes hold
+// tokens (walk_pairs): the root pair's left child, and the sentinel's token in the guard levels;
+// rays that need the EXACT walk keep plain refs.
+template <typename SE, bool LSCENE, bool GSTACK, bool kInvLds, bool LINK, bool kFlatOnly>
+__device__ __forceinline__ void ray_setup(const Work& W, Stack<SE>& st, const double o[3], const double d[3], bool pw, Trav& R) {
+    trav_init(o, d, W.f32_ok != 0, R);
+    const bool tok = kPairWalk<LSCENE> && pw && !(R.neg & kZeroDir);
+    if (!LINK) st.base[-static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel | (tok ? kTokAlone : 0u));
+    if (!LINK && !kFlatOnly) st.base[-2 * static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel | (tok ? kTokAlone : 0u));
+    if (tok) R.cur = kTokAlone;
+    if (kInvLds) {  // the f64 node test's 1 / d, divided once per ray (slab64_inv)
+        uint32_t t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        LdsDouble* const inv_l = (LdsDouble*)static_cast<uintptr_t>(W.lds_inv64 + t * 8);
+        inv_l[0] = 1 / d[0];
+        inv_l[kBlock] = 1 / d[1];
+        inv_l[2 * kBlock] = 1 / d[2];
+    }
+}
+
+// The walk of one traversal round: every walking lane to its next entered leaf, or to the end of
+// its traversal. The instrumented pass (COUNT) walks like the reference unless W.count_spec.
+template <typename SE, bool COUNT, bool LSCENE, bool GSTACK, bool kInvLds, bool kFlatOnly, bool LINK>
+__device__ __forceinline__ void walk_round(const SceneView& S, const Work& W, Stack<SE>& st, const double o[3], const double d[3],
+                                           double tmin, float tmin32, bool pw, Trav& R, LaneCounters& ctr) {
+    constexpr bool kTop = kTopTreelet && !LSCENE;
+    if (kPairWalk<LSCENE> && pw) {
+        // W.pair_walk is off for scenes that need the EXACT walk (W.exact_slab); a ray
+        // with a zero / tiny / huge direction component takes it, on plain refs
+        if (__ballot(R.state == kWalk && (R.neg & kZeroDir)) != 0) {
+            if (R.state == kWalk && (R.neg & kZeroDir))
+                walk<SE, COUNT, true, kTop, LSCENE, GSTACK, false>(S, st, o, d, tmin, tmin32, R, ctr);
+        }
+        if (R.state == kWalk && !(R.neg & kZeroDir))
+            walk_pairs<SE, COUNT, kTop, kInvLds>(S, st, o, d, tmin, tmin32, R, ctr);
+    } else if (!W.exact_slab && __ballot(R.state == kWalk && (R.neg & kZeroDir)) == 0) {
+        if (R.state == kWalk) {
+            if (!COUNT || W.count_spec)
+                walk<SE, COUNT, false, kTop, LSCENE, GSTACK, true, kInvLds, !kFlatOnly, LINK>(S, st, o, d, tmin, tmin32, R, ctr);
+            else
+                walk<SE, COUNT, false, kTop, LSCENE, GSTACK, false, kInvLds, true, LINK>(S, st, o, d, tmin, tmin32, R, ctr);
+        }
+    } else {
+        if (R.state == kWalk) walk<SE, COUNT, true, kTop, LSCENE, GSTACK, false, false, true, LINK>(S, st, o, d, tmin, tmin32, R, ctr);
+    }
+}
+
+// The front end of the query and radiance kernels: a wave takes 64 consecutive rays per atomic
+// (`queue` counts batches), and its lanes take the batch's rays in lane order as they finish one,
+// crossing into the next batch without waiting. The wave's batch (wave-uniform) is rays
+// [b_base, b_base + b_cnt), b_pos of them taken. True: the lane drew `ray`.
+__device__ __forceinline__ bool draw_batch(uint32_t* queue, uint32_t batches, uint32_t n, uint32_t lane, bool& need, bool& dry,
+                                           uint32_t& b_base, uint32_t& b_cnt, uint32_t& b_pos, uint32_t& ray) {
+    bool start = false;
+    while (!dry) {
+        const uint64_t m = __ballot(need);
+        if (m == 0) break;
+        if (b_pos >= b_cnt) {  // the batch is used up: the next one
+            const uint32_t leader = static_cast<uint32_t>(__ffsll(static_cast<long long>(m)) - 1);
+            uint32_t v = 0;
+            if (lane == leader) v = atomicAdd(queue, 1u);
+            const uint32_t j = __builtin_amdgcn_readlane(v, leader);
+            if (j >= batches) {
+                dry = true;
+                break;
+            }
+            b_base = j * 64u;
+            b_pos = 0;
+            b_cnt = min(64u, n - b_base);
+        }
+        const uint32_t take = min(static_cast<uint32_t>(__popcll(m)), b_cnt - b_pos);
+        const uint32_t r = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32),
+                                                     __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
+        if (need && r < take) {
+            ray = b_base + b_pos + r;
+            need = false;
+            start = true;
+        }
+        b_pos += take;
+    }
+    if (dry) need = false;
+    return start;
+}
+
+// PM (primitive mix): 0 sphere-only scenes (every parallelogram path compiled out), 1 any scene,
+// 2 parallelogram-only scenes of axis-aligned parallelograms (LDS scenes: the flat-box filter
+// only, no sphere paths)
+// W5: 5 waves per SIMD (96 VGPRs, ~40-48 of them spilled), launched for sphere-only and
+// flat-parallelogram LDS scenes whose LDS copy leaves room for five blocks per CU (scene_layout)
+// MASK: the masked pass of an adaptive render (crt_render_pass_masked_async). The queues run over
+// the band's active tiles only: active[0] = their number, active[1 + i] = the band tile of list
+// entry i, in tile-major order (active_list_kernel). A separate instance: the unmasked instances
+// keep their code.
+// LINK: the stackless walk over the scene's miss links (walk(), LINK), launched for the five-wave
+// sphere-only and flat-parallelogram instances when the table exists and fits the stack region
+// (dispatch_render); no Stack, no guard levels, no sentinel stores in the traversal set-up.
+template <typename SE, bool GSTACK, bool LSCENE, bool COUNT, int PM, bool W5, bool MASK = false, bool LINK = false>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kManyWaves : LSCENE ? CRT_WAVES_PER_EU_LDS : CRT_WAVES_PER_EU, 8))) void render_kernel(
+    SceneView Sg, CamView C, Work W, double* __restrict__ partial, SE* __restrict__ gstack,
+    Counters* __restrict__ counters, const uint32_t* __restrict__ active) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // the instances with PM = 0 are launched for sphere-only scenes only, PM = 2 for scenes of
+    // axis-aligned parallelograms only: the other primitive's paths are compiled out of them
+    constexpr bool kSphOnly = PM == 0, kFlatOnly = PM == 2;
+    // sqrt / reciprocal expansions without range fix-ups (sqrt_exact, recip_exact): measured
+    // faster only in the five-wave sphere-only instance
+    constexpr bool kFast = kSphOnly && W5;
+    SceneView S = Sg;
+    stage_scene<LSCENE, LINK>(smem, Sg, W, S);
+    if (LSCENE || W.ntop) __syncthreads();  // with the staging only: one barrier of its own
     // The camera constants are read from an LDS copy in start_path / shade: held in SGPRs for
     // the whole kernel they would spill (into VGPR lanes, reloaded with v_readlane per use).
     if (threadIdx.x == 0) *reinterpret_cast<CamView*>(smem + W.lds_cam) = C;
@@ -1997,22 +2113,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kMa
     const uint32_t lane = threadIdx.x & 63;
     LaneCounters ctr{};
     const unsigned long long t_start = COUNT ? wall_clock64() : 0;
-    // stack levels 0..depth of this lane, above two guard levels holding the sentinel reference
-    // and one more level walk() may read (three levels in HBM; in LDS that one is other data)
-    Stack<SE> st{};
-    if (LINK) {
-        // no stack: its bytes hold the miss links
-    } else if (GSTACK) {
-        st.stride = gridDim.x * kBlock;
-        st.base = gstack + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x) + 3 * static_cast<size_t>(st.stride);
-    } else {
-        st.base = reinterpret_cast<SE*>(smem + W.lds_stack) + threadIdx.x;
-        st.stride = kBlock;
-    }
-    if (!LINK) {
-        st.base[-static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel);
-        st.base[-2 * static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel);
-    }
+    Stack<SE> st = lane_stack<SE, GSTACK, LINK>(smem, gstack, W);
     // The wave's current item (wave-uniform) and how many of its 64 units are drawn; lanes take
     // the next units in lane order. A unit's sum goes to partial[chunk][pixel] whichever lane
     // traced it, so frames do not depend on the schedule.
@@ -2031,15 +2132,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kMa
     // contribution to a zeroed local (0 + x = x) that then goes into the LDS sum: the same
     // additions as acc + x
     constexpr bool kAccLds = kFast;
-    typedef __attribute__((address_space(3))) double LdsDouble;
     LdsDouble* const acc_l = (LdsDouble*)static_cast<uintptr_t>(W.lds_acc + threadIdx.x * 8);
     // the five-wave flat-parallelogram instance keeps each ray's f64 1 / d in LDS for the walk's f64
     // node tests (slab64_inv) instead of dividing at each one
     constexpr bool kInvLds = (kFlatOnly && LSCENE && W5) || (!LSCENE && !GSTACK);
-    // the sibling-pair walk (walk_pairs) of the HBM-scene instances; the instrumented pass walks
-    // that way only when it walks like the timed kernel (CRT_COUNT_SPEC=1)
-    constexpr bool kPair = CRT_PAIR_WALK && !LSCENE;
-    const bool pw = kPair && W.pair_walk && (!COUNT || W.count_spec);
+    // the instrumented pass walks pairs only when it walks like the timed kernel (CRT_COUNT_SPEC=1)
+    const bool pw = kPairWalk<LSCENE> && W.pair_walk && (!COUNT || W.count_spec);
     S.inv64_lds = W.lds_inv64;
     if (kAccLds) {
         acc_l[0] = 0;
@@ -2137,25 +2235,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kMa
             const uint32_t row = owned_row(W, W.k0 + (u_txy >> 16) * kTileH + pix / kTileW);
             start_path(CL, row, col, sample_seed(C.base_seed, row * C.w + col, s), P);
         }
-        // one traversal set-up for new samples and scattered rays alike (the wave runs it once);
-        // the guard level below the stack gets the sentinel back (the f32 walk's store at the
-        // sentinel overwrote it)
+        // one traversal set-up for new samples and scattered rays alike (the wave runs it once)
         if (start || cont) {
-            trav_init(P.o, P.d, W.f32_ok != 0, R);
-            // the pair walk's lanes hold tokens (walk_pairs): the root pair's left child, and the
-            // sentinel's token in the guard level; rays that need the EXACT walk keep plain refs
-            const bool tok = kPair && pw && !(R.neg & kZeroDir);
-            if (!LINK) st.base[-static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel | (tok ? kTokAlone : 0u));
-            if (!LINK && !kFlatOnly) st.base[-2 * static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel | (tok ? kTokAlone : 0u));
-            if (tok) R.cur = kTokAlone;
-            if (kInvLds) {  // the f64 node test's 1 / d, divided once per ray (slab64_inv)
-                uint32_t t = threadIdx.x;
-                asm volatile("" : "+v"(t));
-                LdsDouble* const inv_l = (LdsDouble*)static_cast<uintptr_t>(W.lds_inv64 + t * 8);
-                inv_l[0] = 1 / P.d[0];
-                inv_l[kBlock] = 1 / P.d[1];
-                inv_l[2 * kBlock] = 1 / P.d[2];
-            }
+            ray_setup<SE, LSCENE, GSTACK, kInvLds, LINK, kFlatOnly>(W, st, P.o, P.d, pw, R);
             if (COUNT) ctr.rays++;
         }
         start = false;
@@ -2174,25 +2256,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W5 ? kMa
             }
             if (COUNT) cw -= static_cast<uint32_t>(wall_clock64());
             set_prio<kPrioWalk>();
-            if (kPair && pw) {
-                // W.pair_walk is off for scenes that need the EXACT walk (W.exact_slab); a ray
-                // with a zero / tiny / huge direction component takes it, on plain refs
-                if (__ballot(R.state == kWalk && (R.neg & kZeroDir)) != 0) {
-                    if (R.state == kWalk && (R.neg & kZeroDir))
-                        walk<SE, COUNT, true, kTopTreelet && !LSCENE, LSCENE, GSTACK, false>(S, st, P.o, P.d, C.t_min, tmin32, R, ctr);
-                }
-                if (R.state == kWalk && !(R.neg & kZeroDir))
-                    walk_pairs<SE, COUNT, kTopTreelet && !LSCENE, kInvLds>(S, st, P.o, P.d, C.t_min, tmin32, R, ctr);
-            } else if (!W.exact_slab && __ballot(R.state == kWalk && (R.neg & kZeroDir)) == 0) {
-                if (R.state == kWalk) {
-                    if (!COUNT || W.count_spec)
-                        walk<SE, COUNT, false, kTopTreelet && !LSCENE, LSCENE, GSTACK, true, kInvLds, !kFlatOnly, LINK>(S, st, P.o, P.d, C.t_min, tmin32, R, ctr);
-                    else
-                        walk<SE, COUNT, false, kTopTreelet && !LSCENE, LSCENE, GSTACK, false, kInvLds, true, LINK>(S, st, P.o, P.d, C.t_min, tmin32, R, ctr);
-                }
-            } else {
-                if (R.state == kWalk) walk<SE, COUNT, true, kTopTreelet && !LSCENE, LSCENE, GSTACK, false, false, true, LINK>(S, st, P.o, P.d, C.t_min, tmin32, R, ctr);
-            }
+            walk_round<SE, COUNT, LSCENE, GSTACK, kInvLds, kFlatOnly, LINK>(S, W, st, P.o, P.d, C.t_min, tmin32, pw, R, ctr);
             if (COUNT) cw += static_cast<uint32_t>(wall_clock64());
             set_prio<kPrioLeaf>();
             if (COUNT && W.round_counters) {
@@ -2824,8 +2888,7 @@ __global__ __launch_bounds__(kBlock) void plain_query_kernel(SceneView S, Query 
 // lanes take the batch's rays in lane order as they finish one, crossing into the next batch
 // without waiting, so neighbouring rays share a wave and a lane idles only once the queue is dry.
 // A ray outside the contract (ray_traceable) goes straight to kDone as a miss: no traversal state
-// is set up for it. The scene staging and the stack set-up are render_kernel's, copied: that
-// kernel's register allocation is tuned to the spill and is left as it is.
+// is set up for it.
 // PM as in render_kernel (0: sphere-only scenes, 1: any scene). ANY: a lane whose leaf step found
 // an accepted primitive is done (occlusion: any primitive in the interval).
 // The interval: t_min is the call's (wave-uniform, tmin32 = RN32(t_min) in W.tmin32), the upper
@@ -2843,53 +2906,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LSCENE ?
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr bool kSphOnly = PM == 0;
     SceneView S = Sg;
-    if (LSCENE) {  // render_kernel's staging: f32 nodes at LDS offset 0, then the primitives
-        if (static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsByte*)smem)) != 0) __builtin_trap();
-        stage_lds(smem, Sg.fnodes, W.bytes_nodes);
-        stage_lds(smem + W.lds_quads, Sg.quads, W.bytes_quads);
-        S.quads = reinterpret_cast<const DevQuad*>(smem + W.lds_quads);
-        S.quads_lds = W.lds_quads;
-        if (W.quads_f32) {
-            stage_lds(smem + W.lds_quadf, W.quads_flat ? static_cast<const void*>(Sg.quadbox) : Sg.quadf, W.bytes_quadf);
-            S.quadf_lds = W.lds_quadf;
-        }
-        S.refs_lds = W.lds_refs;
-        S.spheres_lds = W.spheres_f32 ? (W.bytes_sph64 ? W.lds_sph64 : ~0u) : W.lds_spheres;
-        if (W.spheres_f32) {
-            stage_lds(smem + W.lds_spheres, Sg.spair, W.bytes_spheres);
-            if (W.bytes_sph64) stage_lds(smem + W.lds_sph64, Sg.spheres, W.bytes_sph64);
-            S.spair_lds = W.lds_spheres;
-        } else {
-            stage_lds(smem + W.lds_refs, Sg.refs, W.bytes_refs);
-            stage_lds(smem + W.lds_spheres, Sg.spheres, W.bytes_spheres);
-            S.refs = reinterpret_cast<const uint32_t*>(smem + W.lds_refs);
-            S.spheres = reinterpret_cast<const DevSphere*>(smem + W.lds_spheres);
-        }
-    } else if (W.ntop) {  // HBM scene: the top of the f32 node array in LDS
-        if (static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsByte*)smem)) != 0) __builtin_trap();
-        stage_lds(smem, Sg.fnodes, W.ntop);
-        S.ntop = W.ntop;
-    }
+    stage_scene<LSCENE, false>(smem, Sg, W, S);
     __syncthreads();
     const float tmin32 = W.tmin32;
     const double tmin = Q.t_min;
     const uint32_t lane = threadIdx.x & 63;
     LaneCounters ctr{};
-    // the lane's stack above two guard levels and one more level walk() may read (render_kernel)
-    Stack<SE> st;
-    if (GSTACK) {
-        st.stride = gridDim.x * kBlock;
-        st.base = gstack + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x) + 3 * static_cast<size_t>(st.stride);
-    } else {
-        st.base = reinterpret_cast<SE*>(smem + W.lds_stack) + threadIdx.x;
-        st.stride = kBlock;
-    }
-    st.base[-static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel);
-    st.base[-2 * static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel);
-    typedef __attribute__((address_space(3))) double LdsDouble;
+    Stack<SE> st = lane_stack<SE, GSTACK, false>(smem, gstack, W);
     constexpr bool kInvLds = !LSCENE && !GSTACK;  // the rays' f64 1 / d in LDS (slab64_inv)
-    constexpr bool kPair = CRT_PAIR_WALK && !LSCENE;
-    const bool pw = kPair && W.pair_walk;
+    const bool pw = kPairWalk<LSCENE> && W.pair_walk;
     S.inv64_lds = W.lds_inv64;
     // the wave's batch (wave-uniform): rays [b_base, b_base + b_cnt), b_pos of them taken
     uint32_t b_base = 0, b_cnt = 0, b_pos = 0;
@@ -2901,55 +2926,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LSCENE ?
     bool need = true;
     while (true) {
         set_prio<kPrioInit>();
-        bool start = false;
-        while (!dry) {
-            const uint64_t m = __ballot(need);
-            if (m == 0) break;
-            if (b_pos >= b_cnt) {  // the batch is used up: the next one
-                const uint32_t leader = static_cast<uint32_t>(__ffsll(static_cast<long long>(m)) - 1);
-                uint32_t v = 0;
-                if (lane == leader) v = atomicAdd(Q.queue, 1u);
-                const uint32_t j = __builtin_amdgcn_readlane(v, leader);
-                if (j >= Q.batches) {
-                    dry = true;
-                    break;
-                }
-                b_base = j * 64u;
-                b_pos = 0;
-                b_cnt = min(64u, Q.n - b_base);
-            }
-            const uint32_t take = min(static_cast<uint32_t>(__popcll(m)), b_cnt - b_pos);
-            const uint32_t r = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32),
-                                                         __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
-            if (need && r < take) {
-                ray = b_base + b_pos + r;
-                need = false;
-                start = true;
-            }
-            b_pos += take;
-        }
-        if (dry) need = false;
+        bool start = draw_batch(Q.queue, Q.batches, Q.n, lane, need, dry, b_base, b_cnt, b_pos, ray);
         if (start) {
             const double* src = Q.rays + 6 * static_cast<size_t>(ray);
             o[0] = src[0]; o[1] = src[1]; o[2] = src[2];
             d[0] = src[3]; d[1] = src[4]; d[2] = src[5];
             const double tm = Q.tmax ? Q.tmax[ray] : Q.t_max;
             if (ray_traceable(o, d, tm) && ray_interval_open(tmin, tm)) {
-                trav_init(o, d, W.f32_ok != 0, R);
-                R.tmax = tm;
+                ray_setup<SE, LSCENE, GSTACK, kInvLds, false, false>(W, st, o, d, pw, R);
+                R.tmax = tm;  // the ray's own upper bound
                 R.tmax32 = tmax_f32(tm);
-                const bool tok = kPair && pw && !(R.neg & kZeroDir);
-                st.base[-static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel | (tok ? kTokAlone : 0u));
-                st.base[-2 * static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel | (tok ? kTokAlone : 0u));
-                if (tok) R.cur = kTokAlone;
-                if (kInvLds) {
-                    uint32_t t = threadIdx.x;
-                    asm volatile("" : "+v"(t));
-                    LdsDouble* const inv_l = (LdsDouble*)static_cast<uintptr_t>(W.lds_inv64 + t * 8);
-                    inv_l[0] = 1 / d[0];
-                    inv_l[kBlock] = 1 / d[1];
-                    inv_l[2 * kBlock] = 1 / d[2];
-                }
             } else {  // outside the contract, or an empty interval: a miss, never traced
                 R.found = false;
                 R.ref = 0;
@@ -2957,22 +2943,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LSCENE ?
                 R.state = kDone;
             }
         }
-        // render_kernel's traversal rounds
-        while (true) {
+        while (true) {  // traversal rounds, as in render_kernel
             set_prio<kPrioWalk>();
-            if (kPair && pw) {
-                if (__ballot(R.state == kWalk && (R.neg & kZeroDir)) != 0) {
-                    if (R.state == kWalk && (R.neg & kZeroDir))
-                        walk<SE, false, true, kTopTreelet && !LSCENE, LSCENE, GSTACK, false>(S, st, o, d, tmin, tmin32, R, ctr);
-                }
-                if (R.state == kWalk && !(R.neg & kZeroDir))
-                    walk_pairs<SE, false, kTopTreelet && !LSCENE, kInvLds>(S, st, o, d, tmin, tmin32, R, ctr);
-            } else if (!W.exact_slab && __ballot(R.state == kWalk && (R.neg & kZeroDir)) == 0) {
-                if (R.state == kWalk)
-                    walk<SE, false, false, kTopTreelet && !LSCENE, LSCENE, GSTACK, true, kInvLds>(S, st, o, d, tmin, tmin32, R, ctr);
-            } else {
-                if (R.state == kWalk) walk<SE, false, true, kTopTreelet && !LSCENE, LSCENE, GSTACK, false>(S, st, o, d, tmin, tmin32, R, ctr);
-            }
+            walk_round<SE, false, LSCENE, GSTACK, kInvLds, false, false>(S, W, st, o, d, tmin, tmin32, pw, R, ctr);
             set_prio<kPrioLeaf>();
             if (R.state == kLeaf) {
                 leaf_step<SE, false, kTopTreelet && !LSCENE, LSCENE>(S, st, o, d, tmin, tmin32, kSphOnly || W.sphere_only != 0,
@@ -3054,44 +3027,17 @@ __global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, Cam
 // ends stores 0 + T * (emit | background), or +0, and the lane asks for the next ray.
 // The caller's ray is classified before any traversal state exists (load_path); one outside the
 // contract goes to kDone as a miss and is shaded as one. Scattered rays are render_kernel's: set up
-// by the common trav_init block, which rewrites both guard levels (the f32 walk's store at the
-// sentinel overwrote one). Every segment runs over (t_min, +inf) with t_min >= 0 (the ABI's rule),
-// so the leaf filters hold as in a render. The staging and the stack set-up are query_kernel's,
-// copied like that kernel's; the camera copy in LDS is render_kernel's (shade reads the background
-// from it).
+// by ray_setup, which rewrites both guard levels (the f32 walk's store at the sentinel overwrote
+// one). Every segment runs over (t_min, +inf) with t_min >= 0 (the ABI's rule), so the leaf filters
+// hold as in a render. The camera copy in LDS is render_kernel's (shade reads the background from
+// it).
 template <typename SE, bool GSTACK, bool LSCENE, int PM>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LSCENE ? CRT_WAVES_PER_EU_LDS : CRT_WAVES_PER_EU, 8))) void radiance_kernel(
     SceneView Sg, CamView C, Work W, Radiance Q, SE* __restrict__ gstack) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr bool kSphOnly = PM == 0;
     SceneView S = Sg;
-    if (LSCENE) {  // render_kernel's staging: f32 nodes at LDS offset 0, then the primitives
-        if (static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsByte*)smem)) != 0) __builtin_trap();
-        stage_lds(smem, Sg.fnodes, W.bytes_nodes);
-        stage_lds(smem + W.lds_quads, Sg.quads, W.bytes_quads);
-        S.quads = reinterpret_cast<const DevQuad*>(smem + W.lds_quads);
-        S.quads_lds = W.lds_quads;
-        if (W.quads_f32) {
-            stage_lds(smem + W.lds_quadf, W.quads_flat ? static_cast<const void*>(Sg.quadbox) : Sg.quadf, W.bytes_quadf);
-            S.quadf_lds = W.lds_quadf;
-        }
-        S.refs_lds = W.lds_refs;
-        S.spheres_lds = W.spheres_f32 ? (W.bytes_sph64 ? W.lds_sph64 : ~0u) : W.lds_spheres;
-        if (W.spheres_f32) {
-            stage_lds(smem + W.lds_spheres, Sg.spair, W.bytes_spheres);
-            if (W.bytes_sph64) stage_lds(smem + W.lds_sph64, Sg.spheres, W.bytes_sph64);
-            S.spair_lds = W.lds_spheres;
-        } else {
-            stage_lds(smem + W.lds_refs, Sg.refs, W.bytes_refs);
-            stage_lds(smem + W.lds_spheres, Sg.spheres, W.bytes_spheres);
-            S.refs = reinterpret_cast<const uint32_t*>(smem + W.lds_refs);
-            S.spheres = reinterpret_cast<const DevSphere*>(smem + W.lds_spheres);
-        }
-    } else if (W.ntop) {  // HBM scene: the top of the f32 node array in LDS
-        if (static_cast<uint32_t>(reinterpret_cast<uintptr_t>((LdsByte*)smem)) != 0) __builtin_trap();
-        stage_lds(smem, Sg.fnodes, W.ntop);
-        S.ntop = W.ntop;
-    }
+    stage_scene<LSCENE, false>(smem, Sg, W, S);
     if (threadIdx.x == 0) *reinterpret_cast<CamView*>(smem + W.lds_cam) = C;
     __syncthreads();
     const CamView& CL = *reinterpret_cast<const CamView*>(smem + W.lds_cam);
@@ -3099,21 +3045,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LSCENE ?
     const double tmin = C.t_min;
     const uint32_t lane = threadIdx.x & 63;
     LaneCounters ctr{};
-    // the lane's stack above two guard levels and one more level walk() may read (render_kernel)
-    Stack<SE> st;
-    if (GSTACK) {
-        st.stride = gridDim.x * kBlock;
-        st.base = gstack + (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x) + 3 * static_cast<size_t>(st.stride);
-    } else {
-        st.base = reinterpret_cast<SE*>(smem + W.lds_stack) + threadIdx.x;
-        st.stride = kBlock;
-    }
-    st.base[-static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel);
-    st.base[-2 * static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel);
-    typedef __attribute__((address_space(3))) double LdsDouble;
+    Stack<SE> st = lane_stack<SE, GSTACK, false>(smem, gstack, W);
     constexpr bool kInvLds = !LSCENE && !GSTACK;  // the rays' f64 1 / d in LDS (slab64_inv)
-    constexpr bool kPair = CRT_PAIR_WALK && !LSCENE;
-    const bool pw = kPair && W.pair_walk;
+    const bool pw = kPairWalk<LSCENE> && W.pair_walk;
     S.inv64_lds = W.lds_inv64;
     // the wave's batch (wave-uniform): paths [b_base, b_base + b_cnt), b_pos of them taken
     uint32_t b_base = 0, b_cnt = 0, b_pos = 0;
@@ -3125,34 +3059,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LSCENE ?
     bool need = true, cont = false;
     while (true) {
         set_prio<kPrioInit>();
-        bool start = false;
-        while (!dry) {
-            const uint64_t m = __ballot(need);
-            if (m == 0) break;
-            if (b_pos >= b_cnt) {  // the batch is used up: the next one
-                const uint32_t leader = static_cast<uint32_t>(__ffsll(static_cast<long long>(m)) - 1);
-                uint32_t v = 0;
-                if (lane == leader) v = atomicAdd(Q.queue, 1u);
-                const uint32_t j = __builtin_amdgcn_readlane(v, leader);
-                if (j >= Q.batches) {
-                    dry = true;
-                    break;
-                }
-                b_base = j * 64u;
-                b_pos = 0;
-                b_cnt = min(64u, Q.n - b_base);
-            }
-            const uint32_t take = min(static_cast<uint32_t>(__popcll(m)), b_cnt - b_pos);
-            const uint32_t r = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32),
-                                                         __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
-            if (need && r < take) {
-                ray = b_base + b_pos + r;
-                need = false;
-                start = true;
-            }
-            b_pos += take;
-        }
-        if (dry) need = false;
+        bool start = draw_batch(Q.queue, Q.batches, Q.n, lane, need, dry, b_base, b_cnt, b_pos, ray);
         if (start && !load_path(Q, ray, P)) {  // outside the contract: a miss, never traced
             start = false;
             R.found = false;
@@ -3160,39 +3067,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LSCENE ?
             R.tmax = 0;
             R.state = kDone;
         }
-        // render_kernel's traversal set-up, for new paths and scattered rays alike
-        if (start || cont) {
-            trav_init(P.o, P.d, W.f32_ok != 0, R);
-            const bool tok = kPair && pw && !(R.neg & kZeroDir);
-            st.base[-static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel | (tok ? kTokAlone : 0u));
-            st.base[-2 * static_cast<ptrdiff_t>(st.stride)] = static_cast<SE>(W.sentinel | (tok ? kTokAlone : 0u));
-            if (tok) R.cur = kTokAlone;
-            if (kInvLds) {
-                uint32_t t = threadIdx.x;
-                asm volatile("" : "+v"(t));
-                LdsDouble* const inv_l = (LdsDouble*)static_cast<uintptr_t>(W.lds_inv64 + t * 8);
-                inv_l[0] = 1 / P.d[0];
-                inv_l[kBlock] = 1 / P.d[1];
-                inv_l[2 * kBlock] = 1 / P.d[2];
-            }
-        }
+        // one traversal set-up for new paths and scattered rays alike
+        if (start || cont) ray_setup<SE, LSCENE, GSTACK, kInvLds, false, false>(W, st, P.o, P.d, pw, R);
         cont = false;
-        // render_kernel's traversal rounds
-        while (true) {
+        while (true) {  // traversal rounds, as in render_kernel
             set_prio<kPrioWalk>();
-            if (kPair && pw) {
-                if (__ballot(R.state == kWalk && (R.neg & kZeroDir)) != 0) {
-                    if (R.state == kWalk && (R.neg & kZeroDir))
-                        walk<SE, false, true, kTopTreelet && !LSCENE, LSCENE, GSTACK, false>(S, st, P.o, P.d, tmin, tmin32, R, ctr);
-                }
-                if (R.state == kWalk && !(R.neg & kZeroDir))
-                    walk_pairs<SE, false, kTopTreelet && !LSCENE, kInvLds>(S, st, P.o, P.d, tmin, tmin32, R, ctr);
-            } else if (!W.exact_slab && __ballot(R.state == kWalk && (R.neg & kZeroDir)) == 0) {
-                if (R.state == kWalk)
-                    walk<SE, false, false, kTopTreelet && !LSCENE, LSCENE, GSTACK, true, kInvLds>(S, st, P.o, P.d, tmin, tmin32, R, ctr);
-            } else {
-                if (R.state == kWalk) walk<SE, false, true, kTopTreelet && !LSCENE, LSCENE, GSTACK, false>(S, st, P.o, P.d, tmin, tmin32, R, ctr);
-            }
+            walk_round<SE, false, LSCENE, GSTACK, kInvLds, false, false>(S, W, st, P.o, P.d, tmin, tmin32, pw, R, ctr);
             set_prio<kPrioLeaf>();
             if (R.state == kLeaf)
                 leaf_step<SE, false, kTopTreelet && !LSCENE, LSCENE>(S, st, P.o, P.d, tmin, tmin32, kSphOnly || W.sphere_only != 0,
@@ -3632,6 +3512,9 @@ static dev::CamView cam_view(const crt_camera* cam) {
 }
 
 static size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
+// scene_layout's `extra`: nothing for a trace, the camera copy for a render or a radiance query
+constexpr size_t kTraceExtra = 0;
+static size_t camera_extra() { return align16(sizeof(dev::CamView)); }
 
 constexpr size_t kAccBytes = 3 * dev::kBlock * sizeof(double);  // five-wave sphere-only pixel sums
 constexpr size_t kInvBytes = 3 * dev::kBlock * sizeof(double);  // flat-parallelogram instances' 1 / d
@@ -3643,13 +3526,13 @@ constexpr size_t kLdsStackBudget = 32 * 1024 * dev::kBlock / 256;
 constexpr size_t kLdsBudget5 = 160 * 1024 * dev::kBlock / (64 * dev::kManyWaves * 4);  // LDS a block at five waves a SIMD
 constexpr size_t kLdsPerBlock = 160 * 1024 * dev::kBlock / (256 * CRT_WAVES_PER_EU);  // LDS per block at the VGPR occupancy
 
-// The class of a launch and what its layout step decided (render_layout, query_layout); the launch
+// The class of a launch and what its layout step decided (scene_layout); the launch
 // steps (dispatch_*) and crt_launch_plan read it.
 enum QueryClass { kQueryLdsScene, kQueryLdsStack, kQueryHbmStack };
 struct Layout {
     QueryClass cls = kQueryLdsScene;
     bool w5 = false;         // render: five waves per SIMD
-    size_t lds = 0;          // bytes laid out so far (the launchers add theirs: *_lds_tail)
+    size_t lds = 0;          // bytes laid out so far (the launchers add theirs: lds_tail)
     size_t stack_bytes = 0;  // levels 0..depth
     size_t level = 0;        // one stack level
     size_t all_nodes = 0;    // the f32 node array
@@ -3662,36 +3545,33 @@ static int render_prim_mode(const dev::Work& W, QueryClass cls) {
 }
 static int query_prim_mode(const dev::Work& W) { return W.sphere_only ? 0 : 1; }
 
-// What a launcher keeps behind the layout's `lds` bytes, for its instance; returns the dynamic LDS
-// the launch requests.
-static size_t render_lds_tail(dev::Work& W, size_t lds, bool gstack, bool lscene, int pm, bool w5) {
-    W.lds_cam = static_cast<uint32_t>(align16(lds));  // the camera copy after the rest
-    lds = W.lds_cam + align16(sizeof(dev::CamView));
-    if (w5 && pm == 0) {  // then the pixel sums (render_kernel: kAccLds)
+// What a launcher keeps behind the layout's `lds` bytes, for its instance: which regions (Tail),
+// and where they go (lds_tail, which returns the dynamic LDS the launch requests).
+struct Tail {
+    bool cam;          // the camera copy after the rest (render_kernel, radiance_kernel: CL)
+    bool acc;          // then the pixel sums (render_kernel: kAccLds)
+    bool inv;          // or the rays' f64 1 / d (kInvLds)
+    bool sibling_pad;  // a treelet alone (HBM stack) with nothing behind it
+};
+static Tail render_tail(bool gstack, bool lscene, int pm, bool w5) {
+    return {true, w5 && pm == 0, (lscene && pm == 2 && w5) || (!lscene && !gstack), false};
+}
+static Tail trace_tail(bool gstack, bool lscene) { return {false, false, !lscene && !gstack, gstack}; }
+static Tail radiance_tail(bool gstack, bool lscene) { return {true, false, !lscene && !gstack, false}; }
+static size_t lds_tail(dev::Work& W, size_t lds, const Tail& t) {
+    // a treelet alone that holds the whole node array ends with the sentinel, whose sibling slot
+    // fetch_two reads too (and never tests): keep it inside the request. A cut treelet is whole
+    // pairs, and every other instance has a region behind the nodes.
+    if (t.sibling_pad && lds % (2 * sizeof(DevNodeF))) lds += sizeof(DevNodeF);
+    if (t.cam) {
+        W.lds_cam = static_cast<uint32_t>(align16(lds));
+        lds = W.lds_cam + camera_extra();
+    }
+    if (t.acc) {
         W.lds_acc = static_cast<uint32_t>(align16(lds));
         lds = W.lds_acc + kAccBytes;
     }
-    if ((lscene && pm == 2 && w5) || (!lscene && !gstack)) {  // or the rays' f64 1 / d (render_kernel: kInvLds)
-        W.lds_inv64 = static_cast<uint32_t>(align16(lds));
-        lds = W.lds_inv64 + kInvBytes;
-    }
-    return lds;
-}
-static size_t trace_lds_tail(dev::Work& W, size_t lds, bool gstack, bool lscene) {
-    // a treelet alone (HBM stack) that holds the whole node array ends with the sentinel, whose
-    // sibling slot fetch_two reads too (and never tests): keep it inside the request. A cut treelet
-    // is whole pairs, and every other instance has a region behind the nodes.
-    if (gstack && lds % (2 * sizeof(DevNodeF))) lds += sizeof(DevNodeF);
-    if (!lscene && !gstack) {  // the rays' f64 1 / d (query_kernel: kInvLds)
-        W.lds_inv64 = static_cast<uint32_t>(align16(lds));
-        lds = W.lds_inv64 + kInvBytes;
-    }
-    return lds;
-}
-static size_t radiance_lds_tail(dev::Work& W, size_t lds, bool gstack, bool lscene) {
-    W.lds_cam = static_cast<uint32_t>(align16(lds));  // launch_render's place for the camera copy
-    lds = W.lds_cam + align16(sizeof(dev::CamView));
-    if (!lscene && !gstack) {  // the rays' f64 1 / d (radiance_kernel: kInvLds)
+    if (t.inv) {
         W.lds_inv64 = static_cast<uint32_t>(align16(lds));
         lds = W.lds_inv64 + kInvBytes;
     }
@@ -3773,13 +3653,79 @@ static int pass_pool(int device, hipMemPool_t* out) {
     return CRT_OK;
 }
 
+// The grid of a persistent kernel: every resident block (more would only wait); CRT_GRID_BLOCKS:
+// fewer (schedule tests: a smaller grid, same results)
+static int resident_blocks(int device, const void* kfn, size_t lds, uint64_t& resident) {
+    int cus = 0, per_cu = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, dev::kBlock, lds));
+    resident = static_cast<uint64_t>(std::max(1, cus)) * std::max(1, per_cu);
+    if (const char* e = std::getenv("CRT_GRID_BLOCKS"))
+        resident = std::max<uint64_t>(1, std::min<uint64_t>(resident, static_cast<uint64_t>(std::max(1, std::atoi(e)))));
+    return CRT_OK;
+}
+
+// The grid and scratch of a query launch (launch_trace, launch_radiance): the resident blocks, or as
+// many as the 64-ray batches fill; stream-ordered from the pass pool, an HBM stack of levels
+// 0..depth, two guard levels and the level below them (lane_stack), and the zeroed batch counter.
+// The caller frees both after its launch.
+template <typename SE>
+static int persistent_grid(const crt_scene* s, int device, const void* kfn, size_t lds, uint32_t batches, bool hbm_stack,
+                           hipMemPool_t pool, hipStream_t stream, uint32_t& blocks, SE*& gstack, uint32_t*& queue) {
+    uint64_t resident = 0;
+    const int rc = resident_blocks(device, kfn, lds, resident);
+    if (rc) return rc;
+    constexpr uint32_t kWavesPerBlock = dev::kBlock / 64;
+    blocks = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(resident, (batches + kWavesPerBlock - 1) / kWavesPerBlock)));
+    if (hbm_stack)
+        HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&gstack),
+                                       gstack_levels(s) * blocks * dev::kBlock * sizeof(SE), pool, stream));
+    HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&queue), 256, pool, stream));
+    HIP_TRY(hipMemsetAsync(queue, 0, sizeof(uint32_t), stream));
+    return CRT_OK;
+}
+
+// The plain routes (one thread per ray, trace()'s loop): launches of at most 2^20 rays that share
+// one set of stacks, [level][thread] (stream order keeps them apart). launch(blocks, first, stacks):
+// the same grid for every launch (the stacks' stride is its thread count); the kernel bounds itself
+// by the rays left.
+template <typename F>
+static int plain_launches(const crt_scene* s, uint32_t n, hipMemPool_t pool, hipStream_t st, const char* what, F launch) {
+    constexpr uint32_t kPlainRays = 1u << 20;
+    const uint32_t max_blocks = (std::min<uint32_t>(n, kPlainRays) + dev::kBlock - 1) / dev::kBlock;
+    uint32_t* d_stack = nullptr;
+    HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&d_stack),
+                                   static_cast<size_t>(s->depth + 1) * max_blocks * dev::kBlock * 4, pool, st));
+    hipError_t e = hipSuccess;
+    for (uint64_t first = 0; first < n && e == hipSuccess; first += kPlainRays) {
+        launch(max_blocks, static_cast<uint32_t>(first), d_stack);
+        e = hipGetLastError();
+    }
+    (void)hipFreeAsync(d_stack, st);
+    if (e != hipSuccess) return fail(CRT_E_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+    return CRT_OK;
+}
+
+// The class x primitive-mode switch of the query launchers: go(GSTACK, LSCENE, PM), as constants
+template <typename F>
+static int by_class(QueryClass cls, bool sphere_only, F go) {
+    auto mode = [&](auto gstack, auto lscene) {
+        return sphere_only ? go(gstack, lscene, std::integral_constant<int, 0>{}) : go(gstack, lscene, std::integral_constant<int, 1>{});
+    };
+    switch (cls) {
+    case kQueryLdsScene: return mode(std::false_type{}, std::true_type{});
+    case kQueryLdsStack: return mode(std::false_type{}, std::false_type{});
+    default: return mode(std::true_type{}, std::false_type{});
+    }
+}
+
 template <typename SE, bool GSTACK, bool LSCENE, int PM, bool W5 = false, bool LINK = false>
 static int launch_render(const crt_scene* s, int device, const crt_camera* cam, const dev::Work& w0,
                          size_t lds, double* d_rgb, hipStream_t stream, crt_render_stats* count_stats,
                          const RenderPass* pass) {
     const DeviceCopy& c = s->dev[device];
     dev::Work W = w0;
-    lds = render_lds_tail(W, lds, GSTACK, LSCENE, PM, W5);
+    lds = lds_tail(W, lds, render_tail(GSTACK, LSCENE, PM, W5));
     constexpr int kThreads = dev::kBlock;
     // a masked pass (adaptive sampling) launches the MASK instance over the active tiles' list
     const bool masked = pass && pass->blocks;
@@ -3827,13 +3773,9 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
     const uint32_t bx = static_cast<uint32_t>(std::min({tiles_x_all, kMaxTiles, cap}));
     const uint32_t by = static_cast<uint32_t>(std::min({tiles_y_all, kMaxTiles, std::max<uint64_t>(1, cap / bx)}));
     // the grid: every resident block (more would only wait), fewer when a band's items are fewer
-    int cus = 0, per_cu = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, kThreads, lds));
     constexpr uint32_t kWavesPerBlock = kThreads / 64;
-    uint64_t resident = static_cast<uint64_t>(std::max(1, cus)) * std::max(1, per_cu);
-    if (const char* e = std::getenv("CRT_GRID_BLOCKS"))  // schedule tests: a smaller grid, same frame
-        resident = std::max<uint64_t>(1, std::min<uint64_t>(resident, static_cast<uint64_t>(std::max(1, std::atoi(e)))));
+    uint64_t resident = 0;
+    if (const int rc = resident_blocks(device, kfn, lds, resident)) return rc;
     auto knob = [](const char* name, uint32_t dflt) {
         const char* e = std::getenv(name);
         return e ? static_cast<uint32_t>(std::max(0, std::min(4096, std::atoi(e)))) : dflt;
@@ -4003,10 +3945,16 @@ static int launch_render(const crt_scene* s, int device, const crt_camera* cam, 
 
 // Kernel variant per scene: u16 stack entries below 65536 nodes; the scene itself in LDS when it
 // and the stack fit the LDS budget, else the stack alone in LDS, else everything in HBM.
-// render_layout fills W's LDS layout for the class it returns (W's class flags and tmin32 are the
-// caller's: class_flags); dispatch_render launches that class's instance.
+// scene_layout fills W's LDS layout for the class it returns (W's class flags and tmin32 are the
+// caller's: class_flags), with the bytes laid out so far; the launchers add what their instance
+// keeps behind that (lds_tail). `extra`: those bytes besides the rays' 1 / d, which the treelet leaves
+// free: the camera copy of a render or a radiance query (camera_extra), nothing for a trace. The
+// five-wave and flat-parallelogram-only instances are the render kernel's alone (five_wave_ok):
+// queries run four waves per SIMD throughout, and a scene of axis-aligned parallelograms runs its
+// flat-box filter in their general instance. dispatch_render, dispatch_trace and dispatch_radiance
+// launch the class's instance.
 template <typename SE>
-static Layout render_layout(const crt_scene* s, dev::Work& W) {
+static Layout scene_layout(const crt_scene* s, dev::Work& W, size_t extra, bool five_wave_ok) {
     Layout L;
     // depth + 1 levels: walk_step stores the far child at level sp unconditionally
     const size_t stack_bytes = align16(static_cast<size_t>(s->depth + 1) * dev::kBlock * sizeof(SE));
@@ -4037,10 +3985,9 @@ static Layout render_layout(const crt_scene* s, dev::Work& W) {
     // garbage stack forever: the round-4 hang, found with -DCRT_WATCHDOG=1. Power-of-two blocks
     // had wrapped back onto the right level by the modular arithmetic alone.)
     auto stack_at = [&](size_t data_bytes) { return static_cast<uint32_t>(std::max<size_t>(data_bytes, 2 * level) + 2 * level); };
-    // every admission counts what the launcher keeps behind the layout too (render_lds_tail): a
+    // every admission counts what the launcher keeps behind the layout too (lds_tail): a
     // request above the class's budget costs a resident block
-    const size_t cam_bytes = align16(sizeof(dev::CamView));
-    if (!force_global && stack_at(scene_bytes) + stack_bytes + cam_bytes <= kLdsSceneBudget) {
+    if (!force_global && stack_at(scene_bytes) + stack_bytes + extra <= kLdsSceneBudget) {
         W.lds_nodes = 0;
         W.lds_refs = W.lds_nodes + W.bytes_nodes;
         W.lds_spheres = W.lds_refs + W.bytes_refs;
@@ -4053,12 +4000,12 @@ static Layout render_layout(const crt_scene* s, dev::Work& W) {
         // 89.8 vs 92.6); the others four, with up to 40 KB (the general instance at five: config
         // 3 116.5 vs 100.6 ms).
         const size_t budget5 = kLdsBudget5;
-        const bool w5 = (64 * dev::kManyWaves * 4) % dev::kBlock == 0 && (W.sphere_only || W.quads_flat) && std::getenv("CRT_FOUR_WAVES") == nullptr &&
-                        stack_at(scene_bytes) + stack_bytes + cam_bytes + (W.sphere_only ? kAccBytes : 0) +
+        const bool w5 = five_wave_ok && (64 * dev::kManyWaves * 4) % dev::kBlock == 0 && (W.sphere_only || W.quads_flat) && std::getenv("CRT_FOUR_WAVES") == nullptr &&
+                        stack_at(scene_bytes) + stack_bytes + extra + (W.sphere_only ? kAccBytes : 0) +
                             (W.quads_flat ? kInvBytes : 0) <= budget5;
         const size_t budget = w5 ? budget5 : kLdsSceneBudget;
         const uint32_t sph64 = static_cast<uint32_t>(s->num_spheres * sizeof(DevSphere));
-        if (W.spheres_f32 && stack_at(scene_bytes + sph64) + stack_bytes + cam_bytes + (w5 ? kAccBytes : 0) <= budget)
+        if (W.spheres_f32 && stack_at(scene_bytes + sph64) + stack_bytes + extra + (w5 ? kAccBytes : 0) <= budget)
             W.bytes_sph64 = sph64;
         W.lds_stack = stack_at(scene_bytes + W.bytes_sph64);
         L.cls = kQueryLdsScene;
@@ -4079,13 +4026,13 @@ static Layout render_layout(const crt_scene* s, dev::Work& W) {
         return no_top ? 0u : static_cast<uint32_t>(std::min(all_nodes, room / (2 * sizeof(DevNodeF)) * (2 * sizeof(DevNodeF))));
     };
     // An LDS stack needs the levels stack_at keeps below it (four without a treelet), the rays' 1 / d
-    // and the camera copy beside it: a stack within kLdsStackBudget that does not fit per_block with
+    // and `extra` beside it: a stack within kLdsStackBudget that does not fit per_block with
     // them (u16 entries: 64 levels; u32: 30 and more) goes to HBM like a larger one.
-    if (stack_bytes <= kLdsStackBudget && stack_at(0) + stack_bytes + kInvBytes + cam_bytes <= per_block &&
+    if (stack_bytes <= kLdsStackBudget && stack_at(0) + stack_bytes + kInvBytes + extra <= per_block &&
         std::getenv("CRT_FORCE_GSTACK") == nullptr) {
         // beside the treelet: the stack, the two guard levels stack_at puts above the data, the rays'
-        // 1 / d and the camera copy (the admission leaves at least two levels of room)
-        const size_t taken = stack_bytes + 2 * level + kInvBytes + cam_bytes;
+        // 1 / d and `extra` (the admission leaves at least two levels of room)
+        const size_t taken = stack_bytes + 2 * level + kInvBytes + extra;
         W.ntop = top_bytes(per_block - taken);
         W.lds_nodes = 0;
         W.lds_stack = stack_at(align16(W.ntop));
@@ -4093,7 +4040,7 @@ static Layout render_layout(const crt_scene* s, dev::Work& W) {
         L.lds = W.lds_stack + stack_bytes;
         return L;
     }
-    W.ntop = top_bytes(per_block - cam_bytes);
+    W.ntop = top_bytes(per_block - extra);
     W.lds_nodes = 0;
     L.cls = kQueryHbmStack;
     L.lds = W.ntop;
@@ -4103,7 +4050,7 @@ static Layout render_layout(const crt_scene* s, dev::Work& W) {
 template <typename SE>
 static int dispatch_render(const crt_scene* s, int device, const crt_camera* cam, dev::Work W,
                            double* d_rgb, hipStream_t st, crt_render_stats* count_stats, const RenderPass* pass) {
-    const Layout L = render_layout<SE>(s, W);
+    const Layout L = scene_layout<SE>(s, W, camera_extra(), true);
     const int pm = render_prim_mode(W, L.cls);
     // The stackless walk (walk(), LINK): the timed five-wave sphere-only and flat-parallelogram
     // instances, when the copy has a validated miss-link table (u16 entries) that fits the bytes the
@@ -4490,31 +4437,16 @@ int device_render_features(const crt_scene* s, int device, const crt_camera* cam
 }
 
 // ---- ray queries (crt_trace_async) -------------------------------------------------------------
-// One query_kernel launch: the grid is every resident block (CRT_GRID_BLOCKS: fewer), or as many as
-// the batches fill; scratch (HBM stacks, the batch counter) is stream-ordered from the pass pool.
+// One query_kernel launch (persistent_grid: its grid and scratch)
 template <typename SE, bool GSTACK, bool LSCENE, int PM>
 static int launch_trace(const crt_scene* s, int device, dev::Work W, size_t lds, dev::Query Q, bool any,
                         hipMemPool_t pool, hipStream_t stream) {
-    lds = trace_lds_tail(W, lds, GSTACK, LSCENE);
+    lds = lds_tail(W, lds, trace_tail(GSTACK, LSCENE));
     const void* kfn = any ? reinterpret_cast<const void*>(dev::query_kernel<SE, GSTACK, LSCENE, PM, true>)
                           : reinterpret_cast<const void*>(dev::query_kernel<SE, GSTACK, LSCENE, PM, false>);
-    int cus = 0, per_cu = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, dev::kBlock, lds));
-    uint64_t resident = static_cast<uint64_t>(std::max(1, cus)) * std::max(1, per_cu);
-    if (const char* e = std::getenv("CRT_GRID_BLOCKS"))
-        resident = std::max<uint64_t>(1, std::min<uint64_t>(resident, static_cast<uint64_t>(std::max(1, std::atoi(e)))));
-    constexpr uint32_t kWavesPerBlock = dev::kBlock / 64;
-    const uint32_t blocks = static_cast<uint32_t>(
-        std::max<uint64_t>(1, std::min<uint64_t>(resident, (Q.batches + kWavesPerBlock - 1) / kWavesPerBlock)));
+    uint32_t blocks = 0;
     SE* gstack = nullptr;
-    if (GSTACK)  // levels 0..depth, two guard levels and the level below them (render_kernel's layout)
-        HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&gstack),
-                                       gstack_levels(s) * blocks * dev::kBlock * sizeof(SE), pool, stream));
-    uint32_t* queue = nullptr;
-    HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&queue), 256, pool, stream));
-    HIP_TRY(hipMemsetAsync(queue, 0, sizeof(uint32_t), stream));
-    Q.queue = queue;
+    if (const int rc = persistent_grid(s, device, kfn, lds, Q.batches, GSTACK, pool, stream, blocks, gstack, Q.queue)) return rc;
     const dev::SceneView S = view_of(s->dev[device]);
     if (any)
         hipLaunchKernelGGL((dev::query_kernel<SE, GSTACK, LSCENE, PM, true>), dim3(blocks), dim3(dev::kBlock), lds, stream,
@@ -4523,7 +4455,7 @@ static int launch_trace(const crt_scene* s, int device, dev::Work W, size_t lds,
         hipLaunchKernelGGL((dev::query_kernel<SE, GSTACK, LSCENE, PM, false>), dim3(blocks), dim3(dev::kBlock), lds, stream,
                            S, W, Q, gstack);
     const hipError_t e = hipGetLastError();
-    (void)hipFreeAsync(queue, stream);
+    (void)hipFreeAsync(Q.queue, stream);
     if (gstack) (void)hipFreeAsync(gstack, stream);
     if (e != hipSuccess) return fail(CRT_E_HIP, std::string("query_kernel launch: ") + hipGetErrorString(e));
     return CRT_OK;
@@ -4532,125 +4464,29 @@ static int launch_trace(const crt_scene* s, int device, dev::Work W, size_t lds,
 static int launch_plain(const crt_scene* s, int device, const dev::Query& Q, bool any, hipMemPool_t pool,
                         hipStream_t st);
 
-// render_layout's decisions for a query: the scene in LDS when it and the stack fit, else the top
-// of the node array and the stack, else the stack in HBM too. Four waves per SIMD throughout: the
-// five-wave and flat-parallelogram-only instances of the render kernel have no query twin (a scene
-// of axis-aligned parallelograms runs its flat-box filter in the general instance).
-// query_layout fills W's LDS layout for the class it returns, with the bytes laid out so far
-// (the launchers add what their instance keeps behind that: `extra` bytes besides the rays' 1 / d,
-// which the treelet leaves free); crt_trace_async and crt_radiance_async share it.
-// the launchers' `extra`: nothing for a trace, the camera copy for a radiance query
-constexpr size_t kTraceExtra = 0;
-static size_t radiance_extra() { return align16(sizeof(dev::CamView)); }
-
-template <typename SE>
-static Layout query_layout(const crt_scene* s, dev::Work& W, size_t extra) {
-    Layout L;
-    const size_t stack_bytes = align16(static_cast<size_t>(s->depth + 1) * dev::kBlock * sizeof(SE));
-    W.bytes_nodes = static_cast<uint32_t>(align16(s->num_dnodes * sizeof(DevNodeF)));
-    W.bytes_refs = W.spheres_f32 ? 0u : static_cast<uint32_t>(align16(s->num_prims * 4));
-    W.bytes_spheres = static_cast<uint32_t>(align16(s->num_spheres * (W.spheres_f32 ? sizeof(DevSpherePair)
-                                                                                         : sizeof(DevSphere))));
-    W.bytes_quads = static_cast<uint32_t>(align16(s->num_quads * sizeof(DevQuad)));
-    W.bytes_quadf = W.quads_f32 ? static_cast<uint32_t>(s->num_quads * (W.quads_flat ? sizeof(DevQuadBox) : sizeof(DevQuadF)))
-                                : 0u;
-    const size_t scene_bytes = static_cast<size_t>(W.bytes_nodes) + W.bytes_refs + W.bytes_spheres + W.bytes_quads +
-                               W.bytes_quadf;
-    const uint32_t level = static_cast<uint32_t>(dev::kBlock * sizeof(SE));
-    W.sentinel = static_cast<uint32_t>(s->num_dnodes - 1) << kNodeFShift;
-    L.stack_bytes = stack_bytes;
-    L.level = level;
-    L.all_nodes = s->num_dnodes * sizeof(DevNodeF);
-    // the guard levels' place, as render_layout lays them out
-    auto stack_at = [&](size_t data_bytes) { return static_cast<uint32_t>(std::max<size_t>(data_bytes, 2 * level) + 2 * level); };
-    if (std::getenv("CRT_NO_LDS_SCENE") == nullptr && stack_at(scene_bytes) + stack_bytes + extra <= kLdsSceneBudget) {
-        W.lds_nodes = 0;
-        W.lds_refs = W.lds_nodes + W.bytes_nodes;
-        W.lds_spheres = W.lds_refs + W.bytes_refs;
-        W.lds_quads = W.lds_spheres + W.bytes_spheres;
-        W.lds_quadf = W.lds_quads + W.bytes_quads;
-        W.lds_sph64 = W.lds_quadf + W.bytes_quadf;
-        const uint32_t sph64 = static_cast<uint32_t>(s->num_spheres * sizeof(DevSphere));
-        if (W.spheres_f32 && stack_at(scene_bytes + sph64) + stack_bytes + extra <= kLdsSceneBudget) W.bytes_sph64 = sph64;
-        W.lds_stack = stack_at(scene_bytes + W.bytes_sph64);
-        L.cls = kQueryLdsScene;
-        L.lds = W.lds_stack + stack_bytes;
-        L.budget = kLdsSceneBudget;
-        return L;
-    }
-    const size_t per_block = kLdsPerBlock;
-    L.budget = per_block;
-    const bool no_top = std::getenv("CRT_NO_LDS_TOP") != nullptr;
-    const size_t all_nodes = L.all_nodes;
-    auto top_bytes = [&](size_t room) {  // whole 64-byte sibling pairs
-        return no_top ? 0u : static_cast<uint32_t>(std::min(all_nodes, room / (2 * sizeof(DevNodeF)) * (2 * sizeof(DevNodeF))));
-    };
-    // render_layout's admission and accounting: the stack, the levels below it, the rays' 1 / d and `extra`
-    if (stack_bytes <= kLdsStackBudget && stack_at(0) + stack_bytes + kInvBytes + extra <= per_block &&
-        std::getenv("CRT_FORCE_GSTACK") == nullptr) {
-        const size_t taken = stack_bytes + 2 * level + kInvBytes + extra;
-        W.ntop = top_bytes(per_block - taken);
-        W.lds_nodes = 0;
-        W.lds_stack = stack_at(align16(W.ntop));
-        L.cls = kQueryLdsStack;
-        L.lds = W.lds_stack + stack_bytes;
-        return L;
-    }
-    W.ntop = top_bytes(per_block - extra);
-    W.lds_nodes = 0;
-    L.cls = kQueryHbmStack;
-    L.lds = W.ntop;
-    return L;
-}
-
 template <typename SE>
 static int dispatch_trace(const crt_scene* s, int device, dev::Work W, const dev::Query& Q, bool any,
                           hipMemPool_t pool, hipStream_t st) {
-    const Layout L = query_layout<SE>(s, W, kTraceExtra);
-    const size_t lds = L.lds;
-    switch (L.cls) {
-    case kQueryLdsScene:
-        // Scenes this small are traced faster by the plain loop (rays of a few node tests each: the
-        // persistent grid's per-ray costs dominate; DESIGN section 6d has the figures), so that is
-        // their route; CRT_TRACE_FAST=1 takes the LDS-scene instances (tests, tools/ray_query_rate.py)
-        if (std::getenv("CRT_TRACE_FAST") == nullptr) return launch_plain(s, device, Q, any, pool, st);
-        if (W.sphere_only) return launch_trace<SE, false, true, 0>(s, device, W, lds, Q, any, pool, st);
-        return launch_trace<SE, false, true, 1>(s, device, W, lds, Q, any, pool, st);
-    case kQueryLdsStack:
-        if (W.sphere_only) return launch_trace<SE, false, false, 0>(s, device, W, lds, Q, any, pool, st);
-        return launch_trace<SE, false, false, 1>(s, device, W, lds, Q, any, pool, st);
-    default:
-        if (W.sphere_only) return launch_trace<SE, true, false, 0>(s, device, W, lds, Q, any, pool, st);
-        return launch_trace<SE, true, false, 1>(s, device, W, lds, Q, any, pool, st);
-    }
+    const Layout L = scene_layout<SE>(s, W, kTraceExtra, false);
+    // Scenes small enough for LDS are traced faster by the plain loop (rays of a few node tests each:
+    // the persistent grid's per-ray costs dominate; DESIGN section 6d has the figures), so that is
+    // their route; CRT_TRACE_FAST=1 takes the LDS-scene instances (tests, tools/ray_query_rate.py)
+    if (L.cls == kQueryLdsScene && std::getenv("CRT_TRACE_FAST") == nullptr) return launch_plain(s, device, Q, any, pool, st);
+    return by_class(L.cls, W.sphere_only != 0, [&](auto gstack, auto lscene, auto pm) {
+        return launch_trace<SE, decltype(gstack)::value, decltype(lscene)::value, decltype(pm)::value>(s, device, W, L.lds, Q, any, pool, st);
+    });
 }
 
-// CRT_TRACE_PLAIN: plain_query_kernel over the batch in launches of at most kPlainRays rays that
-// share one set of stacks (stream order keeps them apart)
+// CRT_TRACE_PLAIN, and trace's default route for LDS scenes: plain_query_kernel (plain_launches)
 static int launch_plain(const crt_scene* s, int device, const dev::Query& Q, bool any, hipMemPool_t pool,
                         hipStream_t st) {
-    constexpr uint32_t kPlainRays = 1u << 20;
-    const uint32_t per = std::min<uint32_t>(Q.n, kPlainRays);
-    const uint32_t max_blocks = (per + dev::kBlock - 1) / dev::kBlock;
-    uint32_t* d_stack = nullptr;  // trace()'s stacks, [level][thread]
-    HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&d_stack),
-                                   static_cast<size_t>(s->depth + 1) * max_blocks * dev::kBlock * 4, pool, st));
     const dev::SceneView S = view_of(s->dev[device]);
-    hipError_t e = hipSuccess;
-    for (uint64_t first = 0; first < Q.n && e == hipSuccess; first += kPlainRays) {
-        // the same grid for every launch (the stacks' stride is its thread count); the kernel
-        // bounds itself by the rays left
+    return plain_launches(s, Q.n, pool, st, "plain_query_kernel", [&](uint32_t blocks, uint32_t first, uint32_t* stacks) {
         if (any)
-            hipLaunchKernelGGL(dev::plain_query_kernel<true>, dim3(max_blocks), dim3(dev::kBlock), 0, st, S, Q,
-                               static_cast<uint32_t>(first), d_stack);
+            hipLaunchKernelGGL(dev::plain_query_kernel<true>, dim3(blocks), dim3(dev::kBlock), 0, st, S, Q, first, stacks);
         else
-            hipLaunchKernelGGL(dev::plain_query_kernel<false>, dim3(max_blocks), dim3(dev::kBlock), 0, st, S, Q,
-                               static_cast<uint32_t>(first), d_stack);
-        e = hipGetLastError();
-    }
-    (void)hipFreeAsync(d_stack, st);
-    if (e != hipSuccess) return fail(CRT_E_HIP, std::string("plain_query_kernel launch: ") + hipGetErrorString(e));
-    return CRT_OK;
+            hipLaunchKernelGGL(dev::plain_query_kernel<false>, dim3(blocks), dim3(dev::kBlock), 0, st, S, Q, first, stacks);
+    });
 }
 
 int device_trace(const crt_scene* s, int device, const double* d_rays, size_t n, const double* d_tmax,
@@ -4728,59 +4564,31 @@ int device_trace_host(crt_scene* s, int device, const double* rays, size_t n, co
 }
 
 // ---- radiance queries (crt_radiance_async) -----------------------------------------------------
-// One radiance_kernel launch: launch_trace's grid and scratch, with the camera copy behind the rest
-// of the LDS layout (launch_render's place for it).
+// One radiance_kernel launch (persistent_grid: its grid and scratch)
 template <typename SE, bool GSTACK, bool LSCENE, int PM>
 static int launch_radiance(const crt_scene* s, int device, dev::Work W, size_t lds, const dev::CamView& C,
                            dev::Radiance Q, hipMemPool_t pool, hipStream_t stream) {
-    lds = radiance_lds_tail(W, lds, GSTACK, LSCENE);
+    lds = lds_tail(W, lds, radiance_tail(GSTACK, LSCENE));
     const void* kfn = reinterpret_cast<const void*>(dev::radiance_kernel<SE, GSTACK, LSCENE, PM>);
-    int cus = 0, per_cu = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, dev::kBlock, lds));
-    uint64_t resident = static_cast<uint64_t>(std::max(1, cus)) * std::max(1, per_cu);
-    if (const char* e = std::getenv("CRT_GRID_BLOCKS"))
-        resident = std::max<uint64_t>(1, std::min<uint64_t>(resident, static_cast<uint64_t>(std::max(1, std::atoi(e)))));
-    constexpr uint32_t kWavesPerBlock = dev::kBlock / 64;
-    const uint32_t blocks = static_cast<uint32_t>(
-        std::max<uint64_t>(1, std::min<uint64_t>(resident, (Q.batches + kWavesPerBlock - 1) / kWavesPerBlock)));
+    uint32_t blocks = 0;
     SE* gstack = nullptr;
-    if (GSTACK)  // levels 0..depth, two guard levels and the level below them (render_kernel's layout)
-        HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&gstack),
-                                       gstack_levels(s) * blocks * dev::kBlock * sizeof(SE), pool, stream));
-    uint32_t* queue = nullptr;
-    HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&queue), 256, pool, stream));
-    HIP_TRY(hipMemsetAsync(queue, 0, sizeof(uint32_t), stream));
-    Q.queue = queue;
+    if (const int rc = persistent_grid(s, device, kfn, lds, Q.batches, GSTACK, pool, stream, blocks, gstack, Q.queue)) return rc;
     hipLaunchKernelGGL((dev::radiance_kernel<SE, GSTACK, LSCENE, PM>), dim3(blocks), dim3(dev::kBlock), lds, stream,
                        view_of(s->dev[device]), C, W, Q, gstack);
     const hipError_t e = hipGetLastError();
-    (void)hipFreeAsync(queue, stream);
+    (void)hipFreeAsync(Q.queue, stream);
     if (gstack) (void)hipFreeAsync(gstack, stream);
     if (e != hipSuccess) return fail(CRT_E_HIP, std::string("radiance_kernel launch: ") + hipGetErrorString(e));
     return CRT_OK;
 }
 
-// CRT_RADIANCE_PLAIN: plain_radiance_kernel in launches of at most 2^20 paths that share one set of
-// stacks (launch_plain's scheme)
+// CRT_RADIANCE_PLAIN: plain_radiance_kernel (plain_launches)
 static int launch_plain_radiance(const crt_scene* s, int device, const dev::CamView& C, const dev::Radiance& Q,
                                  hipMemPool_t pool, hipStream_t st) {
-    constexpr uint32_t kPlainPaths = 1u << 20;
-    const uint32_t per = std::min<uint32_t>(Q.n, kPlainPaths);
-    const uint32_t max_blocks = (per + dev::kBlock - 1) / dev::kBlock;
-    uint32_t* d_stack = nullptr;  // trace()'s stacks, [level][thread]
-    HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&d_stack),
-                                   static_cast<size_t>(s->depth + 1) * max_blocks * dev::kBlock * 4, pool, st));
     const dev::SceneView S = view_of(s->dev[device]);
-    hipError_t e = hipSuccess;
-    for (uint64_t first = 0; first < Q.n && e == hipSuccess; first += kPlainPaths) {
-        hipLaunchKernelGGL(dev::plain_radiance_kernel, dim3(max_blocks), dim3(dev::kBlock), 0, st, S, C, Q,
-                           static_cast<uint32_t>(first), d_stack);
-        e = hipGetLastError();
-    }
-    (void)hipFreeAsync(d_stack, st);
-    if (e != hipSuccess) return fail(CRT_E_HIP, std::string("plain_radiance_kernel launch: ") + hipGetErrorString(e));
-    return CRT_OK;
+    return plain_launches(s, Q.n, pool, st, "plain_radiance_kernel", [&](uint32_t blocks, uint32_t first, uint32_t* stacks) {
+        hipLaunchKernelGGL(dev::plain_radiance_kernel, dim3(blocks), dim3(dev::kBlock), 0, st, S, C, Q, first, stacks);
+    });
 }
 
 // dispatch_trace's classes; every class takes the fast route (a path is many segments per queue
@@ -4788,19 +4596,10 @@ static int launch_plain_radiance(const crt_scene* s, int device, const dev::CamV
 template <typename SE>
 static int dispatch_radiance(const crt_scene* s, int device, dev::Work W, const dev::CamView& C,
                              const dev::Radiance& Q, hipMemPool_t pool, hipStream_t st) {
-    const Layout L = query_layout<SE>(s, W, radiance_extra());
-    const size_t lds = L.lds;
-    switch (L.cls) {
-    case kQueryLdsScene:
-        if (W.sphere_only) return launch_radiance<SE, false, true, 0>(s, device, W, lds, C, Q, pool, st);
-        return launch_radiance<SE, false, true, 1>(s, device, W, lds, C, Q, pool, st);
-    case kQueryLdsStack:
-        if (W.sphere_only) return launch_radiance<SE, false, false, 0>(s, device, W, lds, C, Q, pool, st);
-        return launch_radiance<SE, false, false, 1>(s, device, W, lds, C, Q, pool, st);
-    default:
-        if (W.sphere_only) return launch_radiance<SE, true, false, 0>(s, device, W, lds, C, Q, pool, st);
-        return launch_radiance<SE, true, false, 1>(s, device, W, lds, C, Q, pool, st);
-    }
+    const Layout L = scene_layout<SE>(s, W, camera_extra(), false);
+    return by_class(L.cls, W.sphere_only != 0, [&](auto gstack, auto lscene, auto pm) {
+        return launch_radiance<SE, decltype(gstack)::value, decltype(lscene)::value, decltype(pm)::value>(s, device, W, L.lds, C, Q, pool, st);
+    });
 }
 
 int device_radiance(const crt_scene* s, int device, const double* d_rays, size_t n, const uint32_t* d_states,
@@ -4854,18 +4653,18 @@ static void plan_of(const crt_scene* s, uint32_t kernel, const CopyFlags& c, crt
     size_t total;
     int pm;
     if (kernel == CRT_PLAN_RENDER) {
-        L = render_layout<SE>(s, W);
+        L = scene_layout<SE>(s, W, camera_extra(), true);
         pm = render_prim_mode(W, L.cls);
-        total = render_lds_tail(W, L.lds, L.cls == kQueryHbmStack, L.cls == kQueryLdsScene, pm, L.w5);
+        total = lds_tail(W, L.lds, render_tail(L.cls == kQueryHbmStack, L.cls == kQueryLdsScene, pm, L.w5));
     } else if (kernel == CRT_PLAN_TRACE) {
-        L = query_layout<SE>(s, W, kTraceExtra);
+        L = scene_layout<SE>(s, W, kTraceExtra, false);
         pm = query_prim_mode(W);
-        total = trace_lds_tail(W, L.lds, L.cls == kQueryHbmStack, L.cls == kQueryLdsScene);
+        total = lds_tail(W, L.lds, trace_tail(L.cls == kQueryHbmStack, L.cls == kQueryLdsScene));
         p.plain_route = (L.cls == kQueryLdsScene && std::getenv("CRT_TRACE_FAST") == nullptr) ? 1u : 0u;
     } else {
-        L = query_layout<SE>(s, W, radiance_extra());
+        L = scene_layout<SE>(s, W, camera_extra(), false);
         pm = query_prim_mode(W);
-        total = radiance_lds_tail(W, L.lds, L.cls == kQueryHbmStack, L.cls == kQueryLdsScene);
+        total = lds_tail(W, L.lds, radiance_tail(L.cls == kQueryHbmStack, L.cls == kQueryLdsScene));
     }
     p.kernel = kernel;
     p.klass = L.cls == kQueryLdsScene ? CRT_PLAN_LDS_SCENE : L.cls == kQueryLdsStack ? CRT_PLAN_LDS_STACK : CRT_PLAN_HBM_STACK;
@@ -4897,7 +4696,7 @@ static void plan_of(const crt_scene* s, uint32_t kernel, const CopyFlags& c, crt
     p.lds_cam = W.lds_cam;
     p.lds_acc = W.lds_acc;
     p.lds_inv64 = W.lds_inv64;
-    p.bytes_cam = static_cast<uint32_t>(align16(sizeof(dev::CamView)));
+    p.bytes_cam = static_cast<uint32_t>(camera_extra());
     p.bytes_acc = static_cast<uint32_t>(kAccBytes);
     p.bytes_inv64 = static_cast<uint32_t>(kInvBytes);
     p.total_lds = static_cast<uint32_t>(total);

@@ -1,5 +1,5 @@
 """Seeded worlds with a size parameter for the launch-plan tests: the host picks a kernel instance from
-the scene's size alone (crt_device.hip render_layout, query_layout, u16_entries), and these worlds
+the scene's size alone (crt_device.hip scene_layout, u16_entries), and these worlds
 walk each family across every one of those decisions one object at a time. tests/test_launch_plan.py
 checks the plans on the way, without a GPU; tests/test_gpu_plan_edges.py runs both sides of every
 edge found. Not a test module.

@@ -30,7 +30,7 @@ def regions(p):
     else:
         out.append(("treelet", 0, p["ntop"]))
         if p["klass"] == HBM_STACK and p["kernel"] == 1 and p["ntop"] % (2 * NODE):
-            out.append(("sibling", p["ntop"], NODE))  # trace_lds_tail: the sentinel's sibling slot
+            out.append(("sibling", p["ntop"], NODE))  # lds_tail: the sentinel's sibling slot
     if p["klass"] != HBM_STACK:
         out.append(("guards", p["lds_stack"] - 2 * p["level"], 2 * p["level"]))
         out.append(("stack", p["lds_stack"], p["stack_bytes"]))
@@ -98,7 +98,7 @@ def check_plan(p, kernel, route_name, info, where):
         assert ntop <= p["all_nodes"] and (ntop % (2 * NODE) == 0 or ntop == p["all_nodes"]), where
         # the sibling read at f ^ 32 of every token below ntop: inside the staged bytes when ntop is whole
         # pairs; a whole array of an odd node count ends with the sentinel alone, and the layout keeps
-        # readable LDS behind it (the guard levels, the camera copy, or the slot trace_lds_tail adds)
+        # readable LDS behind it (the guard levels, the camera copy, or the slot lds_tail adds)
         if ntop % (2 * NODE):
             assert ntop == p["all_nodes"] and total >= ntop + NODE, (where, "the sentinel's sibling is past the request")
     else:
