@@ -1103,6 +1103,174 @@ __device__ __forceinline__ uint32_t link_at(uint32_t lbase, uint32_t cur) { retu
 // stays the same. The speculative walk's argument above (monotone node test, t_max only shrinking)
 // speaks of the order of the nodes alone and never of the stack, so it holds as it stands; a
 // parked lane stays on its node.
+//
+// The speculative link walk's loop of the sphere-only instance, written out (link_spec_steps).
+// The loop is the wave's and a divergent one: a parking lane leaves it. Written in C++, the
+// compiler keeps "still in the loop" as exec and re-merges every lane mask that lives across the
+// loop's blocks with it (three s_andn2 / s_and / s_or each), and the exec-masked select saves and
+// restores exec: 24 scalar instructions a step beside the 28 vector ones, at an issue cost of
+// about one vector instruction each. The block below owns the loop, so that the compiler never
+// sees exec differ from the call's mask: it saves exec on entry, restores it on every exit, and
+// inside it exec IS the mask of the lanes still in the loop. A lane that has recorded its first
+// leaf is then exec & ~nop, a parking lane leaves exec before the select of the next node (so it
+// keeps its node with no saved exec), and the step's mask algebra is 8 scalar instructions and
+// the f64 branch. The flat-parallelogram instance (G2 = false) keeps the C++ loop: it sends 28 %
+// of its steps to the f64 test, and leaving and re-entering the block that often cost it more
+// than the scalar instructions saved (config 3 +0.5 ms in every round).
+//
+// One step of a lane, from the node test's `enter` and the node's `leaf` bit (leaf: or the
+// sentinel). x: either value.
+//   in loop  nop  enter  leaf | in loop'  nop'  pref'  cur'
+//      0      x     x     x   |    0       0    pref   cur     not in exec: nothing written
+//      1      x     0     x   |    1      nop   pref   link    missed the node
+//      1      x     1     0   |    1      nop   pref   near    entered an interior node
+//      1      1     1     1   |    1       0    cur    link    first leaf: recorded, walks on
+//      1      0     1     1   |    0       0    pref   cur     second leaf: parks
+// A lane that reaches the sentinel with nothing recorded is row four: it records the sentinel,
+// follows its link to itself and parks there in its next step, row five. With rm = enter & leaf:
+// first = rm & nop (pref <- cur), park = rm & ~nop, nop' = nop & ~rm, exec' = exec & ~park, cur'
+// on exec' = (enter & ~leaf) ? near : link.
+// This is the C++ step's `rec` (= in loop & ~nop), `pm`, `on` and vsel_top_on, lane for lane
+// (tests/test_walk_step_masks.py enumerates the rows against a per-lane restatement of it).
+// Termination: only rm lanes park and they leave nop in the same step, so nop is a subset of
+// exec at every step and the loop's test "nop != 0" never runs on an empty exec; a lane at the
+// sentinel always enters it (its box is unbounded), so it gets rm, and every lane reaches the
+// sentinel after finitely many links. The trip count is the C++ loop's: that one also ends when
+// nop empties or the last lane parks, and a step in which the last lane parks empties nop.
+//
+// The rare f64 decision stays in C++: when a lane of exec is undecided (|gap| <= th) the block
+// restores exec and hands back `in` = the loop's exec (never empty there) and, per lane, dec = 0
+// on the undecided lanes of the loop, the f32 gap (never 0 when decided: th > 0) on its other
+// lanes and 1 outside it. The caller replaces the zeros by the f64 verdict's sign and calls the
+// block again, which sees in != 0, takes exec = in, reads the node's words and the link again
+// (cur has not moved) and continues at the mask algebra. A finished walk returns in = 0.
+// No exit leaves a load pending: the block's reads are outside the compiler's wait counters, and
+// their registers are the compiler's again at once after the statement, so the loop's exit comes
+// after the step's lgkmcnt(0) and the hand-back waits for the link's read (still in flight at
+// the "undecided" branch) before it leaves.
+// COUNT: the block counts the loop's lanes on a node other than the sentinel (nodes) and its own
+// trips (steps, per wave). The node's two reads land in fixed registers, q0 = v[8:11] and q1 =
+// v[4:7] (clobbered): an operand cannot name one register of a 128-bit tuple.
+#define CRT_LINK_STEPS_ASM(COUNT_STEP, COUNT_CMP, COUNT_ADD)                                          \
+    "s_mov_b64 %[save], exec\n\t"                                                                         \
+    "s_cmp_lg_u64 %[in], 0\n\t"                                                                           \
+    "s_cbranch_scc1 3f\n"                                                                                 \
+    "0:\n\t"                                                                                              \
+    "ds_read_b128 v[8:11], %[cur]\n\t"                                                                    \
+    "ds_read_b128 v[4:7], %[cur] offset:16\n\t"                                                           \
+    "v_lshrrev_b32_e32 %[top], 1, %[cur]\n\t"                                                                \
+    "v_add_u32_e32 %[top], %[lbase], %[top]\n\t"                                                                \
+    "ds_read_u16 %[top], %[top]\n\t"                                                                            \
+    COUNT_STEP                                                                                            \
+    "s_waitcnt lgkmcnt(2)\n\t"                                                                            \
+    "v_fma_f32 v8, v8, %[i0], -%[o0]\n\t"                                                                 \
+    "v_fma_f32 v9, v9, %[i0], -%[o0]\n\t"                                                                 \
+    "v_fma_f32 v10, v10, %[i1], -%[o1]\n\t"                                                               \
+    "v_fma_f32 v11, v11, %[i1], -%[o1]\n\t"                                                               \
+    "v_min_f32_e32 %[dec], v8, v9\n\t"                                                                    \
+    "v_max_f32_e32 v8, v8, v9\n\t"                                                                        \
+    "v_min_f32_e32 v9, v10, v11\n\t"                                                                      \
+    "v_max_f32_e32 v10, v10, v11\n\t"                                                                     \
+    "s_waitcnt lgkmcnt(1)\n\t"                                                                            \
+    COUNT_CMP                                                                                             \
+    "v_fma_f32 v4, v4, %[i2], -%[o2]\n\t"                                                                 \
+    "v_fma_f32 v5, v5, %[i2], -%[o2]\n\t"                                                                 \
+    COUNT_ADD                                                                                             \
+    "v_min_f32_e32 v11, v4, v5\n\t"                                                                       \
+    "v_max_f32_e32 v4, v4, v5\n\t"                                                                        \
+    "v_max_f32_e32 v11, %[tmin], v11\n\t"                                                                 \
+    "v_min_f32_e32 v4, v4, %[tmax]\n\t"                                                                   \
+    "v_max3_f32 v9, %[dec], v9, v11\n\t"                                                                  \
+    "v_min3_f32 v8, v8, v10, v4\n\t"                                                                      \
+    "v_sub_f32_e32 %[dec], v8, v9\n\t"                                                                    \
+    "v_max_f32_e64 v8, |v9|, |v8|\n\t"                                                                    \
+    "v_fmamk_f32 v8, v8, 0x36000000, %[marg]\n\t"                                                         \
+    "v_cmp_ngt_f32_e64 vcc, |%[dec]|, v8\n\t"                                                             \
+    "s_cbranch_vccnz 2f\n\t"                                                                              \
+    "v_cmp_lt_f32_e32 vcc, 0, %[dec]\n"                                                                   \
+    "1:\n\t"                                                                                              \
+    "v_cmp_gt_i32_e64 %[lm], 0, v7\n\t"                                                                   \
+    "v_bfe_u32 v8, %[neg], v6, 1\n\t"                                                                     \
+    "v_lshl_or_b32 v8, v8, 5, v7\n\t"                                                                     \
+    "s_and_b64 %[lm], vcc, %[lm]\n\t"                                                                     \
+    "s_andn2_b64 vcc, vcc, %[lm]\n\t"                                                                     \
+    "s_and_b64 %[in], %[lm], %[nop]\n\t"                                                                  \
+    "v_cndmask_b32_e64 %[pref], %[pref], %[cur], %[in]\n\t"                                               \
+    "s_andn2_b64 %[in], %[lm], %[nop]\n\t"                                                                \
+    "s_andn2_b64 %[nop], %[nop], %[lm]\n\t"                                                               \
+    "s_andn2_b64 exec, exec, %[in]\n\t"                                                                   \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                            \
+    "v_cndmask_b32_sdwa %[cur], %[top], v8, vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:DWORD\n\t" \
+    "s_cmp_lg_u64 %[nop], 0\n\t"                                                                          \
+    "s_cbranch_scc1 0b\n\t"                                                                               \
+    "s_mov_b64 exec, %[save]\n\t"                                                                         \
+    "s_mov_b64 %[in], 0\n\t"                                                                              \
+    "s_branch 4f\n"                                                                                       \
+    "2:\n\t" /* undecided lanes in vcc: hand back, with the link's read landed */                          \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                            \
+    "s_mov_b64 %[in], exec\n\t"                                                                           \
+    "s_nop 1\n\t"                                                                                         \
+    "v_cndmask_b32_e64 %[dec], %[dec], 0, vcc\n\t"                                                        \
+    "s_andn2_b64 exec, %[save], %[in]\n\t"                                                                \
+    "v_mov_b32_e32 %[dec], 1.0\n\t"                                                                       \
+    "s_mov_b64 exec, %[save]\n\t"                                                                         \
+    "s_branch 4f\n"                                                                                       \
+    "3:\n\t" /* called again with the f64 verdicts in dec */                                              \
+    "s_mov_b64 exec, %[in]\n\t"                                                                           \
+    "ds_read_b64 v[6:7], %[cur] offset:24\n\t"                                                            \
+    "v_lshrrev_b32_e32 %[top], 1, %[cur]\n\t"                                                                \
+    "v_add_u32_e32 %[top], %[lbase], %[top]\n\t"                                                                \
+    "ds_read_u16 %[top], %[top]\n\t"                                                                            \
+    "v_cmp_lt_f32_e32 vcc, 0, %[dec]\n\t"                                                                 \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                            \
+    "s_branch 1b\n"                                                                                       \
+    "4:"
+// COUNT: the wave's trips; the loop's lanes off the sentinel (the carry-in two instructions after
+// its compare: a VALU read of a VALU-written mask needs two wait states)
+#define CRT_LINK_COUNT_STEP "s_add_u32 %[steps], %[steps], 1\n\t"
+#define CRT_LINK_COUNT_CMP "v_cmp_ne_u32_e32 vcc, -1, v7\n\t"
+#define CRT_LINK_COUNT_ADD "v_addc_co_u32_e32 %[nodes], vcc, 0, %[nodes], vcc\n\t"
+#define CRT_LINK_STEPS_OUT [cur] "+v"(cur), [pref] "+v"(pref), [dec] "+v"(dec), [nop] "+s"(nop), [in] "+s"(in), \
+                           [save] "=&s"(save), [lm] "=&s"(lm), [top] "=&v"(top)
+#define CRT_LINK_STEPS_IN [lbase] "v"(lbase), [i0] "v"(R.inv32[0]), [i1] "v"(R.inv32[1]), [i2] "v"(R.inv32[2]),  \
+                          [o0] "v"(R.oinv32[0]), [o1] "v"(R.oinv32[1]), [o2] "v"(R.oinv32[2]), [tmax] "v"(R.tmax32), \
+                          [marg] "v"(R.marg), [neg] "v"(R.neg), [tmin] "s"(tmin32)
+#define CRT_LINK_STEPS_CLOBBER "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "vcc", "scc"
+
+// The loop of walk<SPEC, LINK> of the sphere-only instance: every lane of the call from R.cur to
+// its first entered leaf recorded in `pref` (or the sentinel) and on to where it parks, `cur`
+template <bool COUNT>
+__device__ __forceinline__ void link_spec_steps(const SceneView& S, const double o[3], const double d[3], double tmin,
+                                                float tmin32, const Trav& R, uint32_t lbase, uint32_t& cur, uint32_t& pref,
+                                                LaneCounters& ctr) {
+    uint64_t nop = __ballot(true);  // the lanes of this call
+    uint64_t in = 0;                // the loop's exec at a hand-back; 0: not in the loop
+    uint64_t save, lm;
+    float dec;
+    uint32_t top, steps = 0;
+    asm volatile("" : "=v"(dec), "=v"(pref));  // written before they are read: every lane records a node
+    for (;;) {
+        if constexpr (COUNT) {
+            asm volatile(CRT_LINK_STEPS_ASM(CRT_LINK_COUNT_STEP, CRT_LINK_COUNT_CMP, CRT_LINK_COUNT_ADD)
+                         : CRT_LINK_STEPS_OUT, [nodes] "+v"(ctr.nodes), [steps] "+s"(steps)
+                         : CRT_LINK_STEPS_IN
+                         : CRT_LINK_STEPS_CLOBBER);
+        } else {
+            asm volatile(CRT_LINK_STEPS_ASM("", "", "")
+                         : CRT_LINK_STEPS_OUT
+                         : CRT_LINK_STEPS_IN
+                         : CRT_LINK_STEPS_CLOBBER);
+        }
+        if (__builtin_expect(in == 0, 1)) break;
+        if (COUNT && wave_leader()) ctr.it_slow++;
+        if (dec == 0.f) {
+            if (COUNT) ctr.slow_nodes++;
+            dec = slab64(node64(S, cur), o, d, tmin, R.tmax) ? 1.f : -1.f;
+        }
+    }
+    if (COUNT && wave_leader()) ctr.it_walk += steps;
+}
+
 template <typename SE, bool COUNT, bool EXACT, bool TOP, bool LS, bool GS, bool SPEC, bool INVL = false, bool G2 = true,
           bool LINK = false>
 __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const double o[3], const double d[3],
@@ -1175,6 +1343,18 @@ __device__ __forceinline__ void walk(const SceneView& S, Stack<SE>& st, const do
             w0 = meta.x;
             w1 = meta.y == kSentinelCount ? kSentinelW1 : (kLeafFlagF | meta.y);
         } while (!stop);
+    } else if constexpr (SPEC && LINK && G2 && !CRT_WATCHDOG) {
+        // the speculative walk below with its loop written out (link_spec_steps); a watchdog
+        // build keeps the C++ loop, which can check its deadline in every step
+        uint32_t pref;
+        static_assert(!INVL, "link_spec_steps decides in f64 with slab64: no 1 / d in LDS in this instance");
+        link_spec_steps<COUNT>(S, o, d, tmin, tmin32, R, lbase, cur, pref, ctr);
+        const Uvec2 w = fetch_nodef_words<TOP, LS>(S, pref);
+        R.state = w.y == kSentinelW1 ? kDone : kLeaf;
+        R.first = w.x;
+        R.count = w.y & ~kLeafFlagF;
+        R.cur = cur;
+        return;
     } else if (SPEC) {
         // Speculative walk (Aila & Laine's postponed leaves): a lane that enters its first leaf
         // records it and walks on, with its t_max of now, until it enters a second leaf (or
