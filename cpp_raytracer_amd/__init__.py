@@ -22,7 +22,8 @@ from ._capi import (CRT_BOX, CRT_DIELECTRIC, CRT_DIFFUSE_LIGHT, CRT_LAMBERTIAN, 
                     DenoiseParams, RenderStats, SceneInfo, Tiling, TraceParams, CRT_TRACE_ANY, CRT_TRACE_PLAIN,
                     RadianceParams, CRT_RADIANCE_PLAIN, ProbeParams, CRT_PROBE_SPHERE, CRT_PROBE_HEMISPHERE,
                     CRT_SH_RADIANCE, CRT_SH_IRRADIANCE, Lens, CRT_LENS_PINHOLE, CRT_LENS_ORTHOGRAPHIC,
-                    CRT_LENS_EQUIRECT, CRT_LENS_FISHEYE, CRT_LENS_CUBE, check, lib)
+                    CRT_LENS_EQUIRECT, CRT_LENS_FISHEYE, CRT_LENS_CUBE, EnvView, CRT_ENV_NEAREST, CRT_ENV_BILINEAR,
+                    check, lib)
 
 __all__ = [
     "SceneData", "GpuScene", "CameraSettings", "Camera", "Tiling", "RenderStats", "CrtError",
@@ -34,6 +35,7 @@ __all__ = [
     "ProbeParams", "CRT_PROBE_SPHERE", "CRT_PROBE_HEMISPHERE", "CRT_SH_RADIANCE", "CRT_SH_IRRADIANCE", "sh_eval",
     "Lens", "make_lens", "CRT_LENS_PINHOLE", "CRT_LENS_ORTHOGRAPHIC", "CRT_LENS_EQUIRECT", "CRT_LENS_FISHEYE",
     "CRT_LENS_CUBE", "LensRender",
+    "Env", "EnvView", "make_env", "CRT_ENV_NEAREST", "CRT_ENV_BILINEAR",
     "CRT_LAMBERTIAN", "CRT_METAL", "CRT_DIELECTRIC", "CRT_DIFFUSE_LIGHT",
     "CRT_SPHERE", "CRT_PARALLELOGRAM", "CRT_BOX",
 ]
@@ -149,6 +151,20 @@ def sh_eval(coeff, index, dirs, irradiance: bool = False):
         return out
 
 
+def _basis(who, forward, up):
+    """(right, up, forward) of make_lens and make_env: forward normalised, right = normalise(forward x
+    up), up = right x forward, in numpy."""
+    f = np.asarray(forward, np.float64).reshape(3)
+    u = np.asarray(up, np.float64).reshape(3)
+    f = f / np.sqrt(f.dot(f))
+    r = np.cross(f, u)
+    r = r / np.sqrt(r.dot(r))
+    u = np.cross(r, f)
+    if not (np.isfinite(f).all() and np.isfinite(r).all()):
+        raise CrtError(f"{who}: forward and up must be finite, non-zero and not parallel")
+    return r, u, f
+
+
 _LENS_KINDS = {"pinhole": CRT_LENS_PINHOLE, "orthographic": CRT_LENS_ORTHOGRAPHIC, "equirect": CRT_LENS_EQUIRECT,
                "fisheye": CRT_LENS_FISHEYE, "cube": CRT_LENS_CUBE}
 
@@ -165,14 +181,7 @@ def make_lens(kind, origin=(0.0, 0.0, 0.0), forward=(0.0, 0.0, -1.0), up=(0.0, 1
         if kind not in _LENS_KINDS:
             raise CrtError(f"make_lens: kind must be one of {sorted(_LENS_KINDS)}")
         kind = _LENS_KINDS[kind]
-    f = np.asarray(forward, np.float64).reshape(3)
-    u = np.asarray(up, np.float64).reshape(3)
-    f = f / np.sqrt(f.dot(f))
-    r = np.cross(f, u)
-    r = r / np.sqrt(r.dot(r))
-    u = np.cross(r, f)
-    if not (np.isfinite(f).all() and np.isfinite(r).all()):
-        raise CrtError("make_lens: forward and up must be finite, non-zero and not parallel")
+    r, u, f = _basis("make_lens", forward, up)
     if extent_x == 0 and extent_y == 0:
         if kind == CRT_LENS_EQUIRECT:
             extent_x, extent_y = float(np.pi), float(np.pi) / 2
@@ -181,6 +190,61 @@ def make_lens(kind, origin=(0.0, 0.0, 0.0), forward=(0.0, 0.0, -1.0), up=(0.0, 1
     D3 = _capi.D3
     return Lens(kind, CRT_RADIANCE_PLAIN if plain else 0, D3(*[float(v) for v in origin]), D3(*r.tolist()),
                 D3(*u.tolist()), D3(*f.tolist()), float(extent_x), float(extent_y), int(batch_pixels))
+
+
+_ENV_FILTERS = {"nearest": CRT_ENV_NEAREST, "bilinear": CRT_ENV_BILINEAR}
+
+
+class Env:
+    """A cube-map environment for GpuScene.radiance / probes / render_lens (make_env): the (6n, n, 3)
+    float64 tensor on a GPU, kept alive here, and the crt_env view of it that the calls read."""
+
+    def __init__(self, texels, view: EnvView):
+        self.texels = texels
+        self.view = view
+
+    @property
+    def face_size(self) -> int:
+        return int(self.view.face_size)
+
+
+def _env_texels_ok(t) -> bool:
+    import torch
+    return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 3 and
+            t.shape[2] == 3 and t.shape[1] >= 1 and t.shape[0] == 6 * t.shape[1] and t.is_contiguous())
+
+
+def make_env(texels, forward=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), filter="bilinear") -> Env:
+    """An environment from a cube frame: texels is a contiguous (6n, n, 3) float64 torch tensor on a
+    GPU in render_lens's "cube" layout (a render_lens(cam, make_lens("cube")) frame as it is; it is
+    not copied, and the Env keeps it alive). The basis is built as make_lens builds it; filter is
+    "nearest" or "bilinear" (or a CRT_ENV_* constant). Paths that leave the scene then see the map
+    in place of the constant background (include/crt_render.h, crt_env)."""
+    if isinstance(filter, str):
+        if filter not in _ENV_FILTERS:
+            raise CrtError(f"make_env: filter must be one of {sorted(_ENV_FILTERS)}")
+        filter = _ENV_FILTERS[filter]
+    if not _env_texels_ok(texels):
+        raise CrtError("make_env: texels must be a contiguous (6n, n, 3) float64 tensor on a GPU")
+    if texels.shape[1] > 16384:
+        raise CrtError("make_env: the face size must be at most 16384")
+    r, u, f = _basis("make_env", forward, up)
+    D3 = _capi.D3
+    return Env(texels, EnvView(texels.data_ptr(), texels.shape[1], int(filter), D3(*r.tolist()), D3(*u.tolist()),
+                               D3(*f.tolist())))
+
+
+def _env_on(who: str, env, device: int) -> EnvView:
+    """The view of `env` for a call on `device`; CrtError unless it is an Env whose tensor is still a
+    contiguous float64 cube frame on that device."""
+    if not isinstance(env, Env):
+        raise CrtError(f"{who}: env must be an Env (make_env)")
+    t = env.texels
+    if not _env_texels_ok(t) or t.data_ptr() != env.view.texels or t.shape[1] != env.view.face_size:
+        raise CrtError(f"{who}: env's texels must be the contiguous (6n, n, 3) float64 tensor it was made from")
+    if t.device.index != device:
+        raise CrtError(f"{who}: env's texels are on cuda:{t.device.index}, the call runs on cuda:{device}")
+    return env.view
 
 
 def device_count() -> int:
@@ -608,31 +672,42 @@ class GpuScene:
 
     def radiance_async(self, device: int, rays_ptr: int, n: int, out_ptr: int, states_ptr: int = 0, *,
                        max_depth: int, background, t_min: float = 1e-5, base_seed: int = 0, flags: int = 0,
-                       stream: int = 0) -> None:
+                       stream: int = 0, env: Optional[EnvView] = None) -> None:
         """Enqueue a radiance query on device buffers (crt_radiance_async): n rays of 6 doubles at
         rays_ptr, each the first segment of one path of ray_color with `max_depth` bounces over
         (t_min, inf). Path i's LCG state is the uint32 states_ptr[i], or sample_seed(base_seed, i, 0)
         with states_ptr = 0. Three doubles a path go to out_ptr: what the sample adds to a pixel's
         sum in a render. CRT_RADIANCE_PLAIN takes one thread a path: the same bits. The scene must be
-        uploaded to `device`."""
+        uploaded to `device`. env: an EnvView (crt_env) whose texels are on `device`: paths that end in
+        a miss see it in place of `background` (crt_radiance_env_async)."""
         prm = RadianceParams(max_depth, base_seed & 0xFFFFFFFF, _capi.D3(*[float(v) for v in background]), t_min,
                              flags, 0)
+        if env is not None:
+            check(lib().crt_radiance_env_async(self._h, device, C.c_void_p(rays_ptr or None), n,
+                                               C.c_void_p(states_ptr or None), C.byref(prm), C.byref(env),
+                                               C.c_void_p(out_ptr or None), C.c_void_p(stream)),
+                  "crt_radiance_env_async")
+            return
         check(lib().crt_radiance_async(self._h, device, C.c_void_p(rays_ptr or None), n, C.c_void_p(states_ptr or None),
                                        C.byref(prm), C.c_void_p(out_ptr or None), C.c_void_p(stream)),
               "crt_radiance_async")
 
     def radiance(self, rays, states=None, max_depth: int = 50, background=(0.7, 0.8, 1.0), t_min: float = 1e-5,
-                 base_seed: int = 0, plain: bool = False):
+                 base_seed: int = 0, plain: bool = False, env: Optional[Env] = None):
         """Path-traced radiance of the caller's rays on torch tensors of a GPU: rays (n, 6) float64,
         states None or an (n,) int32 tensor on the rays' device whose bits are the paths' LCG states
         (None: sample_seed(base_seed, i, 0)). Runs on the rays' device and its current stream and
         does not synchronise; the scene is uploaded there first if it is not yet (that blocks).
-        Returns an (n, 3) float64 tensor."""
+        Returns an (n, 3) float64 tensor. env (make_env, on the rays' device): the environment that
+        paths leaving the scene see in place of `background`."""
         import torch
+        if env is not None and not isinstance(env, Env):
+            raise CrtError("radiance: env must be an Env (make_env)")
         if not (rays.is_cuda and rays.dtype == torch.float64 and rays.dim() == 2 and rays.shape[1] == 6):
             raise CrtError("radiance: rays must be an (n, 6) float64 tensor on a GPU")
         rays = rays.contiguous()
         n, device = rays.shape[0], rays.device.index
+        view = _env_on("radiance", env, device) if env is not None else None
         if states is not None:
             if not (states.is_cuda and states.device == rays.device and states.dtype == torch.int32 and
                     states.shape == (n,)):
@@ -646,7 +721,7 @@ class GpuScene:
                                     states.data_ptr() if states is not None else 0, max_depth=max_depth,
                                     background=background, t_min=t_min, base_seed=base_seed,
                                     flags=CRT_RADIANCE_PLAIN if plain else 0,
-                                    stream=torch.cuda.current_stream(device).cuda_stream)
+                                    stream=torch.cuda.current_stream(device).cuda_stream, env=view)
             return out
 
     @staticmethod
@@ -660,15 +735,20 @@ class GpuScene:
 
     def probes_async(self, device: int, points_ptr: int, normals_ptr: int, n: int, out_ptr: int, *, samples: int,
                      mode=CRT_PROBE_SPHERE, max_depth: int, background, t_min: float = 1e-5, base_seed: int = 0,
-                     batch_probes: int = 0, flags: int = 0, stream: int = 0) -> None:
+                     batch_probes: int = 0, flags: int = 0, stream: int = 0, env: Optional[EnvView] = None) -> None:
         """Enqueue a probe bake on device buffers (crt_probes_async): n points of 3 doubles at
         points_ptr, with CRT_PROBE_HEMISPHERE their unit normals at normals_ptr (0 with
         CRT_PROBE_SPHERE). `samples` directions a probe are drawn on the device, path-traced as
         radiance_async traces them and reduced in a fixed order: n x 9 x 3 doubles (SH coefficients of
         bands 0..2 per channel) or n x 1 x 3 (irradiance) go to out_ptr. batch_probes sizes the
         internal batches only; flags may hold CRT_RADIANCE_PLAIN: the same bits either way. The scene
-        must be uploaded to `device`."""
+        must be uploaded to `device`. env: as radiance_async's (crt_probes_env_async)."""
         prm = self._probe_params(samples, mode, max_depth, background, t_min, base_seed, batch_probes, flags)
+        if env is not None:
+            check(lib().crt_probes_env_async(self._h, device, C.c_void_p(points_ptr or None),
+                                             C.c_void_p(normals_ptr or None), n, C.byref(prm), C.byref(env),
+                                             C.c_void_p(out_ptr or None), C.c_void_p(stream)), "crt_probes_env_async")
+            return
         check(lib().crt_probes_async(self._h, device, C.c_void_p(points_ptr or None), C.c_void_p(normals_ptr or None), n,
                                      C.byref(prm), C.c_void_p(out_ptr or None), C.c_void_p(stream)), "crt_probes_async")
 
@@ -690,15 +770,19 @@ class GpuScene:
 
     def probes(self, points, normals=None, samples: int = 1024, mode: str = "sphere", max_depth: int = 50,
                background=(0.7, 0.8, 1.0), t_min: float = 1e-5, base_seed: int = 0, batch_probes: int = 0,
-               plain: bool = False):
+               plain: bool = False, env: Optional[Env] = None):
         """Probe bake on torch tensors of a GPU: points (n, 3) float64; with mode="hemisphere", normals
         (n, 3) float64 unit vectors on the points' device (None with mode="sphere"). Runs on the
         points' device and its current stream and does not synchronise; the scene is uploaded there
         first if it is not yet (that blocks). Returns an (n, 9, 3) float64 tensor of SH coefficients
-        (sphere; sh_eval evaluates them) or (n, 1, 3) of irradiance (hemisphere)."""
+        (sphere; sh_eval evaluates them) or (n, 1, 3) of irradiance (hemisphere). env (make_env, on the
+        points' device): the environment in place of `background`, as in radiance."""
         import torch
+        if env is not None and not isinstance(env, Env):
+            raise CrtError("probes: env must be an Env (make_env)")
         points, normals = self._probe_inputs("probes", points, normals, mode)
         n, device = points.shape[0], points.device.index
+        view = _env_on("probes", env, device) if env is not None else None
         with torch.cuda.device(device):
             out = torch.empty((n, 9 if mode == "sphere" else 1, 3), dtype=torch.float64, device=points.device)
             if n:
@@ -707,7 +791,7 @@ class GpuScene:
                                   out.data_ptr(), samples=samples, mode=mode, max_depth=max_depth, background=background,
                                   t_min=t_min, base_seed=base_seed, batch_probes=batch_probes,
                                   flags=CRT_RADIANCE_PLAIN if plain else 0,
-                                  stream=torch.cuda.current_stream(device).cuda_stream)
+                                  stream=torch.cuda.current_stream(device).cuda_stream, env=view)
             return out
 
     def probe_rays(self, points, normals=None, samples: int = 1024, mode: str = "sphere", base_seed: int = 0):
@@ -799,26 +883,35 @@ class GpuScene:
                       "crt_lens_rays_async")
             return rays, states
 
-    def render_lens_async(self, device: int, cam: Camera, lens: Lens, out_ptr: int, stream: int = 0) -> None:
+    def render_lens_async(self, device: int, cam: Camera, lens: Lens, out_ptr: int, stream: int = 0,
+                          env: Optional[EnvView] = None) -> None:
         """Enqueue a whole-frame render through `lens` (crt_render_lens_async) into the device buffer
         at out_ptr (image_h * image_w * 3 doubles): the rays of lens_rays, traced as radiance_async
         traces them and summed per pixel in render_async's order. The scene must be uploaded to
-        `device`."""
+        `device`. env: as radiance_async's (crt_render_lens_env_async)."""
+        if env is not None:
+            check(lib().crt_render_lens_env_async(self._h, device, C.byref(cam), C.byref(lens), C.byref(env),
+                                                  C.c_void_p(out_ptr or None), C.c_void_p(stream)),
+                  "crt_render_lens_env_async")
+            return
         check(lib().crt_render_lens_async(self._h, device, C.byref(cam), C.byref(lens), C.c_void_p(out_ptr or None),
                                           C.c_void_p(stream)), "crt_render_lens_async")
 
-    def render_lens(self, cam: Camera, lens: Lens, device: int = 0):
+    def render_lens(self, cam: Camera, lens: Lens, device: int = 0, env: Optional[Env] = None):
         """Whole-frame render through `lens` (make_lens) into an (h, w, 3) float64 torch tensor on
         `device`. Runs on that device's current stream and does not synchronise; the scene is uploaded
         there first if it is not yet (that blocks). With kind "pinhole" the frame is render_async's,
-        bit for bit."""
+        bit for bit. env (make_env, on `device`): the environment in place of cam.background, as in
+        radiance."""
         import torch
         if not isinstance(cam, Camera) or not isinstance(lens, Lens):
             raise CrtError("render_lens: cam must be a resolved Camera (resolve_camera) and lens a Lens (make_lens)")
+        view = _env_on("render_lens", env, device) if env is not None else None
         with torch.cuda.device(device):
             out = torch.empty((cam.image_h, cam.image_w, 3), dtype=torch.float64, device=torch.device("cuda", device))
             self.upload(device)
-            self.render_lens_async(device, cam, lens, out.data_ptr(), torch.cuda.current_stream(device).cuda_stream)
+            self.render_lens_async(device, cam, lens, out.data_ptr(), torch.cuda.current_stream(device).cuda_stream,
+                                   env=view)
             return out
 
     def render_lens_pass(self, device: int, cam: Camera, lens: Lens, first: int, count: int, sum_ptr: int,

@@ -137,6 +137,16 @@ CRT_LENS_PINHOLE, CRT_LENS_ORTHOGRAPHIC, CRT_LENS_EQUIRECT, CRT_LENS_FISHEYE, CR
 assert C.sizeof(Lens) == 128
 
 
+class EnvView(C.Structure):
+    """crt_env: the 88-byte view a call reads (the package's Env keeps the tensor behind it alive)."""
+    _fields_ = [("texels", C.c_void_p), ("face_size", C.c_uint32), ("filter", C.c_uint32), ("right", D3), ("up", D3),
+                ("forward", D3)]
+
+
+CRT_ENV_NEAREST, CRT_ENV_BILINEAR = 0, 1
+assert C.sizeof(EnvView) == 88
+
+
 class LaunchPlan(C.Structure):
     _fields_ = ([(n, C.c_uint32) for n in ("kernel", "klass", "entry_bytes", "five_waves", "prim_mode", "plain_route",
                                            "depth", "block")] + [("num_nodes", C.c_uint64)] +
@@ -248,6 +258,13 @@ EXPORTS = {
                                       C.c_void_p]),
     "crt_render_lens_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), C.c_void_p, C.c_void_p]),
     "crt_render_lens": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), C.c_void_p]),
+    "crt_radiance_env_async": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, P(RadianceParams),
+                                         P(EnvView), C.c_void_p, C.c_void_p]),
+    "crt_probes_env_async": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, P(ProbeParams),
+                                       P(EnvView), C.c_void_p, C.c_void_p]),
+    "crt_render_lens_env_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), P(EnvView), C.c_void_p,
+                                            C.c_void_p]),
+    "crt_render_lens_env": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), P(EnvView), C.c_void_p]),
     "crt_render_lens_pass_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), C.c_uint32, C.c_uint32,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "crt_lens_centre_rays_async": (C.c_int, [C.c_int, P(Camera), P(Lens), C.c_void_p, C.c_void_p]),

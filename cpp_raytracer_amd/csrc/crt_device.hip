@@ -29,6 +29,7 @@
 #include "crt_ray_class.h"
 #include "crt_ray_gate.h"
 #include "crt_schlick.h"
+#include "crt_env.h"
 
 #pragma clang fp contract(off)
 
@@ -3160,6 +3161,24 @@ struct Radiance {
     uint32_t base_seed;
     uint32_t* queue;          // radiance_kernel: the batch counter, zeroed before the launch
 };
+// The ENV instances' launch: the same, and the caller's environment (crt_radiance_env_async). It
+// stays in the kernel arguments and is read where a path ends in a miss: no LDS, so scene_layout
+// decides as it does without one. The instances without an environment keep their arguments.
+struct RadianceEnv : Radiance {
+    crt_env env;
+};
+template <bool ENV>
+using RadianceOf = std::conditional_t<ENV, RadianceEnv, Radiance>;
+
+// A path that ends in a miss under an environment: 0 + T * E(P.d) (crt_env.h) where shade's miss
+// branch gives 0 + T * bg
+__device__ __forceinline__ void env_miss(const crt_env& E, const CamView& C, const Path& P, double acc[3]) {
+    double e[3];
+    env_lookup(E, P.d, C.bg, e);
+    acc[0] = acc[0] + P.T[0] * e[0];
+    acc[1] = acc[1] + P.T[1] * e[1];
+    acc[2] = acc[2] + P.T[2] * e[2];
+}
 
 // path `ray` of a launch, before its first segment. False: the caller's ray is outside the query
 // contract (crt_ray_class.h) and must not be traced; shade's miss branch then gives 0 + 1 * bg.
@@ -3175,8 +3194,9 @@ __device__ __forceinline__ bool load_path(const Radiance& Q, uint32_t ray, Path&
 
 // CRT_RADIANCE_PLAIN: ray_color as a loop of trace() and shade, one thread per path
 // [first, first + gridDim.x * kBlock) of the call. Scattered rays go to trace() as they are: it is
-// the reference's sequence for any ray.
-__global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, CamView C, Radiance Q, uint32_t first,
+// the reference's sequence for any ray. ENV: a miss ends the path with env_miss instead of shade.
+template <bool ENV = false>
+__global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, CamView C, RadianceOf<ENV> Q, uint32_t first,
                                                                 uint32_t* __restrict__ gstack) {
     const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
     if (slot >= Q.n - first) return;
@@ -3193,6 +3213,12 @@ __global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, Cam
         uint32_t ref = 0;
         const bool found = traced && trace<uint32_t, false>(S, st, P.o, P.d, C.t_min, tmax, ref, ctr);
         traced = true;
+        if constexpr (ENV) {
+            if (!found) {
+                env_miss(Q.env, C, P, acc);
+                break;
+            }
+        }
         if (shade<false>(S, C, P, found, ref, tmax, acc) || P.depth == 0) break;
     }
     double* dst = Q.rgb + 3 * static_cast<size_t>(i);
@@ -3210,10 +3236,10 @@ __global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, Cam
 // by ray_setup, which rewrites both guard levels (the f32 walk's store at the sentinel overwrote
 // one). Every segment runs over (t_min, +inf) with t_min >= 0 (the ABI's rule), so the leaf filters
 // hold as in a render. The camera copy in LDS is render_kernel's (shade reads the background from
-// it).
-template <typename SE, bool GSTACK, bool LSCENE, int PM>
+// it). ENV: a lane in kDone without a hit ends its path with env_miss instead of shade.
+template <typename SE, bool GSTACK, bool LSCENE, int PM, bool ENV = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LSCENE ? CRT_WAVES_PER_EU_LDS : CRT_WAVES_PER_EU, 8))) void radiance_kernel(
-    SceneView Sg, CamView C, Work W, Radiance Q, SE* __restrict__ gstack) {
+    SceneView Sg, CamView C, Work W, RadianceOf<ENV> Q, SE* __restrict__ gstack) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr bool kSphOnly = PM == 0;
     SceneView S = Sg;
@@ -3266,7 +3292,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LSCENE ?
         set_prio<kPrioShade>();
         if (R.state == kDone) {
             double acc[3] = {0, 0, 0};
-            bool ended = shade<LSCENE, kSphOnly>(S, CL, P, R.found, R.ref, R.tmax, acc);
+            bool ended = true;
+            if constexpr (ENV) {
+                if (!R.found) env_miss(Q.env, CL, P, acc);
+                else ended = shade<LSCENE, kSphOnly>(S, CL, P, R.found, R.ref, R.tmax, acc);
+            } else {
+                ended = shade<LSCENE, kSphOnly>(S, CL, P, R.found, R.ref, R.tmax, acc);
+            }
             // a scattered ray with no bounce left returns RGB::zero() (camera.h:211-213)
             if (!ended && P.depth == 0) ended = true;
             if (!ended) {
@@ -4745,15 +4777,15 @@ int device_trace_host(crt_scene* s, int device, const double* rays, size_t n, co
 
 // ---- radiance queries (crt_radiance_async) -----------------------------------------------------
 // One radiance_kernel launch (persistent_grid: its grid and scratch)
-template <typename SE, bool GSTACK, bool LSCENE, int PM>
+template <typename SE, bool GSTACK, bool LSCENE, int PM, bool ENV>
 static int launch_radiance(const crt_scene* s, int device, dev::Work W, size_t lds, const dev::CamView& C,
-                           dev::Radiance Q, hipMemPool_t pool, hipStream_t stream) {
+                           dev::RadianceOf<ENV> Q, hipMemPool_t pool, hipStream_t stream) {
     lds = lds_tail(W, lds, radiance_tail(GSTACK, LSCENE));
-    const void* kfn = reinterpret_cast<const void*>(dev::radiance_kernel<SE, GSTACK, LSCENE, PM>);
+    const void* kfn = reinterpret_cast<const void*>(dev::radiance_kernel<SE, GSTACK, LSCENE, PM, ENV>);
     uint32_t blocks = 0;
     SE* gstack = nullptr;
     if (const int rc = persistent_grid(s, device, kfn, lds, Q.batches, GSTACK, pool, stream, blocks, gstack, Q.queue)) return rc;
-    hipLaunchKernelGGL((dev::radiance_kernel<SE, GSTACK, LSCENE, PM>), dim3(blocks), dim3(dev::kBlock), lds, stream,
+    hipLaunchKernelGGL((dev::radiance_kernel<SE, GSTACK, LSCENE, PM, ENV>), dim3(blocks), dim3(dev::kBlock), lds, stream,
                        view_of(s->dev[device]), C, W, Q, gstack);
     const hipError_t e = hipGetLastError();
     (void)hipFreeAsync(Q.queue, stream);
@@ -4763,27 +4795,44 @@ static int launch_radiance(const crt_scene* s, int device, dev::Work W, size_t l
 }
 
 // CRT_RADIANCE_PLAIN: plain_radiance_kernel (plain_launches)
-static int launch_plain_radiance(const crt_scene* s, int device, const dev::CamView& C, const dev::Radiance& Q,
+template <bool ENV>
+static int launch_plain_radiance(const crt_scene* s, int device, const dev::CamView& C, const dev::RadianceOf<ENV>& Q,
                                  hipMemPool_t pool, hipStream_t st) {
     const dev::SceneView S = view_of(s->dev[device]);
     return plain_launches(s, Q.n, pool, st, "plain_radiance_kernel", [&](uint32_t blocks, uint32_t first, uint32_t* stacks) {
-        hipLaunchKernelGGL(dev::plain_radiance_kernel, dim3(blocks), dim3(dev::kBlock), 0, st, S, C, Q, first, stacks);
+        hipLaunchKernelGGL(dev::plain_radiance_kernel<ENV>, dim3(blocks), dim3(dev::kBlock), 0, st, S, C, Q, first, stacks);
     });
 }
 
 // dispatch_trace's classes; every class takes the fast route (a path is many segments per queue
 // visit, unlike a single ray: DESIGN section 6e)
-template <typename SE>
+template <typename SE, bool ENV>
 static int dispatch_radiance(const crt_scene* s, int device, dev::Work W, const dev::CamView& C,
-                             const dev::Radiance& Q, hipMemPool_t pool, hipStream_t st) {
+                             const dev::RadianceOf<ENV>& Q, hipMemPool_t pool, hipStream_t st) {
     const Layout L = scene_layout<SE>(s, W, camera_extra(), false);
     return by_class(L.cls, W.sphere_only != 0, [&](auto gstack, auto lscene, auto pm) {
-        return launch_radiance<SE, decltype(gstack)::value, decltype(lscene)::value, decltype(pm)::value>(s, device, W, L.lds, C, Q, pool, st);
+        return launch_radiance<SE, decltype(gstack)::value, decltype(lscene)::value, decltype(pm)::value, ENV>(s, device, W, L.lds, C, Q, pool, st);
     });
 }
 
+// the route of one call: the plain kernel, or the fast one for the scene's class and entry width
+template <bool ENV>
+static int route_radiance(const crt_scene* s, int device, const crt_radiance_params* prm, const dev::CamView& C,
+                          const dev::RadianceOf<ENV>& Q, hipMemPool_t pool, hipStream_t st) {
+    if (prm->flags & CRT_RADIANCE_PLAIN) return launch_plain_radiance<ENV>(s, device, C, Q, pool, st);
+    // device_trace's scene classes and interval rules; 0 <= t_min <= 2^100 here (crt_radiance_async)
+    const DeviceCopy& c = s->dev[device];
+    dev::Work W{};
+    class_flags(s, flags_of(c), c.f32_ok, true, W);
+    W.tmin32 = static_cast<float>(prm->t_min);
+    if (u16_entries(s)) return dispatch_radiance<uint16_t, ENV>(s, device, W, C, Q, pool, st);
+    return dispatch_radiance<uint32_t, ENV>(s, device, W, C, Q, pool, st);
+}
+
+// env: null, or the call's environment (checked by crt_host.cpp; its texels on `device`): the ENV
+// instances. Without one the launch is the instances' without ENV, as before environments existed.
 int device_radiance(const crt_scene* s, int device, const double* d_rays, size_t n, const uint32_t* d_states,
-                    const crt_radiance_params* prm, double* d_rgb, void* stream) {
+                    const crt_radiance_params* prm, const crt_env* env, double* d_rgb, void* stream) {
     int rc = check_device(device);
     if (rc) return rc;
     if (!s->dev[device].valid)
@@ -4800,7 +4849,7 @@ int device_radiance(const crt_scene* s, int device, const double* d_rays, size_t
     C.t_min = prm->t_min;
     C.max_depth = prm->max_depth;
     C.base_seed = prm->base_seed;
-    dev::Radiance Q{};
+    dev::RadianceEnv Q{};
     Q.rays = d_rays;
     Q.states = d_states;
     Q.rgb = d_rgb;
@@ -4811,14 +4860,9 @@ int device_radiance(const crt_scene* s, int device, const double* d_rays, size_t
     hipMemPool_t pool = nullptr;
     rc = pass_pool(device, &pool);
     if (rc) return rc;
-    if (prm->flags & CRT_RADIANCE_PLAIN) return launch_plain_radiance(s, device, C, Q, pool, st);
-    // device_trace's scene classes and interval rules; 0 <= t_min <= 2^100 here (crt_radiance_async)
-    const DeviceCopy& c = s->dev[device];
-    dev::Work W{};
-    class_flags(s, flags_of(c), c.f32_ok, true, W);
-    W.tmin32 = static_cast<float>(prm->t_min);
-    if (u16_entries(s)) return dispatch_radiance<uint16_t>(s, device, W, C, Q, pool, st);
-    return dispatch_radiance<uint32_t>(s, device, W, C, Q, pool, st);
+    if (!env) return route_radiance<false>(s, device, prm, C, Q, pool, st);
+    Q.env = *env;
+    return route_radiance<true>(s, device, prm, C, Q, pool, st);
 }
 
 // ---- launch plans (crt_launch_plan) ------------------------------------------------------------
@@ -4920,7 +4964,7 @@ int device_radiance_host(crt_scene* s, int device, const double* rays, size_t n,
     if (e == hipSuccess) e = hipMalloc(&d_rgb, n * 3 * sizeof(double));
     if (e == hipSuccess) e = hipMemcpyAsync(d_rays, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && states) e = hipMemcpyAsync(d_states, states, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) rc = device_radiance(s, device, d_rays, n, d_states, prm, d_rgb, st);
+    if (e == hipSuccess) rc = device_radiance(s, device, d_rays, n, d_states, prm, nullptr, d_rgb, st);
     if (e == hipSuccess && rc == CRT_OK) e = hipMemcpyAsync(rgb, d_rgb, n * 3 * sizeof(double), hipMemcpyDeviceToHost, st);
     if (st) {
         const hipError_t se = hipStreamSynchronize(st);

@@ -1554,7 +1554,32 @@ int crt_radiance_async(const crt_scene* s, int device, const double* d_rays, siz
     const int rc = check_radiance("crt_radiance_async: ", s, d_rays, "d_rays", n, params, d_rgb, "d_rgb");
     if (rc) return rc;
     if (n == 0) return CRT_OK;  // no work
-    return device_radiance(s, device, d_rays, n, d_states, params, d_rgb, stream);
+    return device_radiance(s, device, d_rays, n, d_states, params, nullptr, d_rgb, stream);
+}
+
+// ---- environments: the rules of crt_env, after the call's own and before any device work ----------
+static int check_env(const std::string& who, const crt_env* env) {
+    if (!env) return fail(CRT_E_INVALID, who + "env is null");
+    if (!env->texels) return fail(CRT_E_INVALID, who + "env->texels is null");
+    if (env->face_size == 0 || env->face_size > 16384)
+        return fail(CRT_E_INVALID, who + "env->face_size must be in 1 .. 16384");
+    if (env->filter != CRT_ENV_NEAREST && env->filter != CRT_ENV_BILINEAR)
+        return fail(CRT_E_INVALID, who + "unknown env->filter");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(env->right[k]) || !std::isfinite(env->up[k]) || !std::isfinite(env->forward[k]))
+            return fail(CRT_E_INVALID, who + "the env basis (right, up, forward) must be finite");
+    return CRT_OK;
+}
+
+int crt_radiance_env_async(const crt_scene* s, int device, const double* d_rays, size_t n, const uint32_t* d_states,
+                           const crt_radiance_params* params, const crt_env* env, double* d_rgb, void* stream) {
+    clear_error();
+    const std::string who = "crt_radiance_env_async: ";
+    int rc = check_radiance(who, s, d_rays, "d_rays", n, params, d_rgb, "d_rgb");
+    if (rc == CRT_OK) rc = check_env(who, env);
+    if (rc) return rc;
+    if (n == 0) return CRT_OK;  // no work
+    return device_radiance(s, device, d_rays, n, d_states, params, env, d_rgb, stream);
 }
 
 int crt_radiance(crt_scene* s, int device, const double* rays, size_t n, const uint32_t* states,
@@ -1622,7 +1647,19 @@ int crt_probes_async(const crt_scene* s, int device, const double* d_points, con
     if (rc) return rc;
     if (n && !d_coeff) return fail(CRT_E_INVALID, who + "d_coeff is null (the output is required)");
     if (n == 0) return CRT_OK;  // no work
-    return device_probes(s, device, d_points, d_normals, n, params, d_coeff, stream);
+    return device_probes(s, device, d_points, d_normals, n, params, nullptr, d_coeff, stream);
+}
+
+int crt_probes_env_async(const crt_scene* s, int device, const double* d_points, const double* d_normals, size_t n,
+                         const crt_probe_params* params, const crt_env* env, double* d_coeff, void* stream) {
+    clear_error();
+    const std::string who = "crt_probes_env_async: ";
+    int rc = check_probes(who, true, s, d_points, "d_points", d_normals, "d_normals", n, params);
+    if (rc == CRT_OK) rc = check_env(who, env);
+    if (rc) return rc;
+    if (n && !d_coeff) return fail(CRT_E_INVALID, who + "d_coeff is null (the output is required)");
+    if (n == 0) return CRT_OK;  // no work
+    return device_probes(s, device, d_points, d_normals, n, params, env, d_coeff, stream);
 }
 
 int crt_probes(crt_scene* s, int device, const double* points, const double* normals, size_t n,
@@ -1720,7 +1757,18 @@ int crt_render_lens_async(const crt_scene* s, int device, const crt_camera* cam,
     const int rc = check_lens(who, true, s, cam, lens, true);
     if (rc) return rc;
     if (!d_rgb) return fail(CRT_E_INVALID, who + "d_rgb is null (the output is required)");
-    return device_render_lens(s, device, cam, lens, d_rgb, stream);
+    return device_render_lens(s, device, cam, lens, nullptr, d_rgb, stream);
+}
+
+int crt_render_lens_env_async(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens,
+                              const crt_env* env, double* d_rgb, void* stream) {
+    clear_error();
+    const std::string who = "crt_render_lens_env_async: ";
+    int rc = check_lens(who, true, s, cam, lens, true);
+    if (rc == CRT_OK) rc = check_env(who, env);
+    if (rc) return rc;
+    if (!d_rgb) return fail(CRT_E_INVALID, who + "d_rgb is null (the output is required)");
+    return device_render_lens(s, device, cam, lens, env, d_rgb, stream);
 }
 
 int crt_render_lens(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, double* rgb) {
@@ -1729,7 +1777,18 @@ int crt_render_lens(crt_scene* s, int device, const crt_camera* cam, const crt_l
     const int rc = check_lens(who, true, s, cam, lens, true);
     if (rc) return rc;
     if (!rgb) return fail(CRT_E_INVALID, who + "rgb is null (the output is required)");
-    return device_render_lens_host(s, device, cam, lens, rgb);
+    return device_render_lens_host(s, device, cam, lens, nullptr, rgb);
+}
+
+int crt_render_lens_env(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, const crt_env* env,
+                        double* rgb) {
+    clear_error();
+    const std::string who = "crt_render_lens_env: ";
+    int rc = check_lens(who, true, s, cam, lens, true);
+    if (rc == CRT_OK) rc = check_env(who, env);
+    if (rc) return rc;
+    if (!rgb) return fail(CRT_E_INVALID, who + "rgb is null (the output is required)");
+    return device_render_lens_host(s, device, cam, lens, env, rgb);
 }
 
 // ---- lens renders in passes: check_lens's rules, then the pass's (check_pass), the adaptive

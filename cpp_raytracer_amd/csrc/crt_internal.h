@@ -434,9 +434,11 @@ int device_trace(const crt_scene* s, int device, const double* d_rays, size_t n,
 int device_trace_host(crt_scene* s, int device, const double* rays, size_t n, const double* tmax,
                       const crt_trace_params* prm, crt_hit* hits, uint32_t* occluded);
 // radiance queries on device buffers (crt_radiance_async, which checks the arguments), the same for
-// host arrays, blocking (uploads the scene if needed), and the camera's own rays and states
+// host arrays, blocking (uploads the scene if needed), and the camera's own rays and states.
+// env (here, in device_probes and in device_render_lens): null for the constant background, or a
+// checked crt_env whose texels are on `device` (the host form of the lens render uploads them)
 int device_radiance(const crt_scene* s, int device, const double* d_rays, size_t n, const uint32_t* d_states,
-                    const crt_radiance_params* prm, double* d_rgb, void* stream);
+                    const crt_radiance_params* prm, const crt_env* env, double* d_rgb, void* stream);
 int device_radiance_host(crt_scene* s, int device, const double* rays, size_t n, const uint32_t* states,
                          const crt_radiance_params* prm, double* rgb);
 // crt_launch_plan: the layout steps and the launchers' additions of the three scene kernels, run on
@@ -450,7 +452,7 @@ int device_camera_rays(int device, const crt_camera* cam, const crt_tiling* t, u
 int device_probe_rays(int device, const double* d_points, const double* d_normals, size_t n,
                       const crt_probe_params* prm, double* d_rays, uint32_t* d_states, void* stream);
 int device_probes(const crt_scene* s, int device, const double* d_points, const double* d_normals, size_t n,
-                  const crt_probe_params* prm, double* d_coeff, void* stream);
+                  const crt_probe_params* prm, const crt_env* env, double* d_coeff, void* stream);
 int device_probes_host(crt_scene* s, int device, const double* points, const double* normals, size_t n,
                        const crt_probe_params* prm, double* coeff);
 int device_sh_eval(int device, const double* d_coeff, size_t num_probes, const uint32_t* d_index,
@@ -460,9 +462,10 @@ int device_sh_eval(int device, const double* d_coeff, size_t num_probes, const u
 // the scene if needed)
 int device_lens_rays(int device, const crt_camera* cam, const crt_lens* lens, uint32_t first_sample,
                      uint32_t num_samples, double* d_rays, uint32_t* d_states, void* stream);
-int device_render_lens(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, double* d_rgb,
-                       void* stream);
-int device_render_lens_host(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, double* rgb);
+int device_render_lens(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, const crt_env* env,
+                       double* d_rgb, void* stream);
+int device_render_lens_host(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, const crt_env* env,
+                            double* rgb);
 // lens renders in passes: one pass into running sums (blocks != null: the blocks at `first` only; it
 // then waits for the stream once), the rays through the pixel centres, and the first-hit features
 int device_render_lens_pass(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, uint32_t first,

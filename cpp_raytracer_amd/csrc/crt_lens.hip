@@ -590,8 +590,8 @@ int device_lens_rays(int device, const crt_camera* cam, const crt_lens* lens, ui
     return CRT_OK;
 }
 
-int device_render_lens(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, double* d_rgb,
-                       void* stream) {
+int device_render_lens(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, const crt_env* env,
+                       double* d_rgb, void* stream) {
     int rc = device_check(device);
     if (rc) return rc;
     if (!s->dev[device].valid)
@@ -627,7 +627,7 @@ int device_render_lens(const crt_scene* s, int device, const crt_camera* cam, co
         double* rgb = reinterpret_cast<double*>(scratch + records * 48);
         uint32_t* states = reinterpret_cast<uint32_t*>(scratch + records * (48 + 24));
         hipError_t e = ln::launch_rays(V, lens->kind, first, static_cast<uint32_t>(records), 0, spp, rays, states, st);
-        if (e == hipSuccess) rc = device_radiance(s, device, rays, records, states, &rp, rgb, st);
+        if (e == hipSuccess) rc = device_radiance(s, device, rays, records, states, &rp, env, rgb, st);
         if (e == hipSuccess && rc == CRT_OK) {
             const dim3 grid((count + ln::kWavesPerBlock - 1) / ln::kWavesPerBlock), block(64 * ln::kWavesPerBlock);
             hipLaunchKernelGGL(ln::lens_reduce_kernel, grid, block, 0, st, rgb, count, spp, L, inv_spp, d_rgb + first * 3);
@@ -711,7 +711,7 @@ int device_render_lens_pass(const crt_scene* s, int device, const crt_camera* ca
                 rgb = reinterpret_cast<double*>(scratch + records * 48);
                 uint32_t* states = reinterpret_cast<uint32_t*>(scratch + records * (48 + 24));
                 e = ln::launch_rays(V, lens->kind, at, static_cast<uint32_t>(records), first, count, rays, states, st, entries);
-                if (e == hipSuccess) rc = device_radiance(s, device, rays, records, states, &rp, rgb, st);
+                if (e == hipSuccess) rc = device_radiance(s, device, rays, records, states, &rp, nullptr, rgb, st);
             }
         }
         if (e == hipSuccess && rc == CRT_OK) {
@@ -799,17 +799,28 @@ int device_lens_features(const crt_scene* s, int device, const crt_camera* cam, 
 }
 
 // crt_render_lens: device_render_lens for a host array, blocking: the render on a stream of its
-// own, one copy back
-int device_render_lens_host(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, double* rgb) {
+// own, one copy back. env (null: none) has its texels in host memory here: uploaded for the call,
+// freed after it
+int device_render_lens_host(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, const crt_env* env,
+                            double* rgb) {
     int rc = device_upload(s, device);
     if (rc) return rc;
     DeviceGuard g(device);
     const size_t bytes = static_cast<size_t>(cam->image_w) * cam->image_h * 3 * sizeof(double);
     double* d_rgb = nullptr;
+    double* d_texels = nullptr;
+    crt_env d_env{};
     hipStream_t st = nullptr;
     hipError_t e = hipStreamCreate(&st);
     if (e == hipSuccess) e = hipMalloc(&d_rgb, bytes);
-    if (e == hipSuccess) rc = device_render_lens(s, device, cam, lens, d_rgb, st);
+    if (e == hipSuccess && env) {
+        const size_t env_bytes = size_t{6} * env->face_size * env->face_size * 3 * sizeof(double);
+        d_env = *env;
+        e = hipMalloc(&d_texels, env_bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_texels, env->texels, env_bytes, hipMemcpyHostToDevice, st);
+        d_env.texels = d_texels;
+    }
+    if (e == hipSuccess) rc = device_render_lens(s, device, cam, lens, env ? &d_env : nullptr, d_rgb, st);
     if (e == hipSuccess && rc == CRT_OK) e = hipMemcpyAsync(rgb, d_rgb, bytes, hipMemcpyDeviceToHost, st);
     if (st) {
         const hipError_t se = hipStreamSynchronize(st);
@@ -817,6 +828,7 @@ int device_render_lens_host(crt_scene* s, int device, const crt_camera* cam, con
         (void)hipStreamDestroy(st);
     }
     (void)hipFree(d_rgb);
+    (void)hipFree(d_texels);
     if (rc) return rc;
     if (e != hipSuccess) return fail(CRT_E_HIP, std::string("crt_render_lens: ") + hipGetErrorString(e));
     return CRT_OK;

@@ -96,6 +96,49 @@ struct Lens {
     }
 };
 
+// Extension (not in the reference): a cube-map environment for Camera::render_lens(world, lens, env)
+// (crt_env with the texels in host memory): what paths that leave the scene see in place of the
+// camera's constant background. The factory takes a cube frame as render_lens returns it for
+// Lens::cube (w x 6w) and builds the basis as Lens's factories do.
+struct Environment {
+    std::vector<double> texels;  // 6n rows x n columns x 3
+    uint32_t face_size = 0;
+    uint32_t filter = CRT_ENV_BILINEAR;
+    Vec3D right{1, 0, 0}, up{0, 1, 0}, forward{0, 0, -1};
+
+    static Environment from_cube(const Image& frame, const Vec3D& forward = Vec3D{0, 0, -1},
+                                 const Vec3D& up = Vec3D{0, 1, 0}, uint32_t filter = CRT_ENV_BILINEAR) {
+        Environment e;
+        e.face_size = static_cast<uint32_t>(frame.width());
+        e.filter = filter;
+        e.forward = forward.unit_vector();
+        e.right = cross(e.forward, up).unit_vector();
+        e.up = cross(e.right, e.forward);
+        e.texels.resize(frame.width() * frame.height() * 3);
+        for (size_t r = 0; r < frame.height(); ++r)
+            for (size_t c = 0; c < frame.width(); ++c) {
+                const RGB& p = frame[r][c];
+                double* t = &e.texels[(r * frame.width() + c) * 3];
+                t[0] = p.r; t[1] = p.g; t[2] = p.b;
+            }
+        if (frame.height() != 6 * frame.width()) e.face_size = 0;  // not a cube frame: the library refuses it
+        return e;
+    }
+
+    crt_env as_crt() const {
+        crt_env v{};
+        v.texels = texels.data();
+        v.face_size = face_size;
+        v.filter = filter;
+        for (size_t k = 0; k < 3; ++k) {
+            v.right[k] = right[k];
+            v.up[k] = up[k];
+            v.forward[k] = forward[k];
+        }
+        return v;
+    }
+};
+
 class Camera {
     size_t image_w = 1280, image_h = 720;
     double viewport_w = 0, viewport_h = 0;
@@ -375,12 +418,17 @@ class Camera {
         return img;
     }
 
-    Image render_scene_lens(const crt_api::GpuScene& g, const Lens& lens) {
+    Image render_scene_lens(const crt_api::GpuScene& g, const Lens& lens, const Environment* env = nullptr) {
         init();
         resolved.base_seed = SeedSeqGenerator::get_instance().next_seed();
         const crt_lens l = lens.as_crt();
         std::vector<double> rgb(image_w * image_h * 3);
-        if (crt_render_lens(g.get(), 0, &resolved, &l, rgb.data())) crt_api::die("crt_render_lens");
+        if (env) {
+            const crt_env e = env->as_crt();
+            if (crt_render_lens_env(g.get(), 0, &resolved, &l, &e, rgb.data())) crt_api::die("crt_render_lens_env");
+        } else if (crt_render_lens(g.get(), 0, &resolved, &l, rgb.data())) {
+            crt_api::die("crt_render_lens");
+        }
         auto img = Image::with_dimensions(image_w, image_h);
         for (size_t r = 0; r < image_h; ++r)
             for (size_t c = 0; c < image_w; ++c) {
@@ -602,6 +650,21 @@ public:
         } else {
             crt_api::GpuScene s(world, 32, 12, true);
             return render_scene_lens(s, lens);
+        }
+    }
+    // Extension (not in the reference): render_lens lit by a cube-map environment (crt_render_lens_env):
+    // paths that leave the scene see env in place of the constant background.
+    Image render_lens(const BVH& world, const Lens& lens, const Environment& env) {
+        return render_scene_lens(world.gpu_scene(), lens, &env);
+    }
+    template <typename T>
+    requires std::is_base_of_v<Hittable, T>
+    Image render_lens(const T& world, const Lens& lens, const Environment& env) {
+        if constexpr (std::is_same_v<T, Scene>) {
+            return render_lens(BVH(world), lens, env);
+        } else {
+            crt_api::GpuScene s(world, 32, 12, true);
+            return render_scene_lens(s, lens, &env);
         }
     }
 

@@ -807,6 +807,67 @@ int crt_render_lens_async(const crt_scene* scene, int device, const crt_camera* 
  * (the C++ drop-in's Camera::render_lens). */
 int crt_render_lens(crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens, double* rgb);
 
+/* ---- cube-map environments --------------------------------------------------------------------
+ * What a path sees where it leaves the scene, in place of the constant background, for the
+ * radiance, probe and lens calls (not for crt_render_async and its drivers, the lens renders in
+ * passes or crt_lens_features_async: those keep the constant). The map has crt_render_lens_async's
+ * CUBE layout, so a captured frame is an environment as it is. Every operation of the lookup is an
+ * IEEE f64 + - * /, a comparison or a floor; nothing is fused. */
+#define CRT_ENV_NEAREST  0u
+#define CRT_ENV_BILINEAR 1u
+typedef struct crt_env {
+    const double* texels;  /* 6n rows x n columns x 3 doubles, row = face * n + row_in_face:
+                              the frame crt_render_lens_async writes for CRT_LENS_CUBE with
+                              image_w = n, image_h = 6 n. Device memory in the *_async entries. */
+    uint32_t face_size;    /* n, 1 <= n <= 16384 */
+    uint32_t filter;       /* CRT_ENV_NEAREST | CRT_ENV_BILINEAR */
+    double right[3], up[3], forward[3];  /* used as given, never normalised (as crt_lens) */
+} crt_env;                 /* 88 bytes */
+
+/* E(d): the value of a path that ends in a miss on a segment with direction d, the path's own
+ * (unnormalised) direction: the caller's for a first-segment miss, the scattered one otherwise.
+ * With R = right, U = up, F = forward, n = face_size:
+ *   1. x = (d0 * R0 + d1 * R1) + d2 * R2, y likewise with U, z with F.
+ *   2. ax = |x|, ay = |y|, az = |z|, m = the largest of the three, NaN if any of them is NaN.
+ *      If !(m > 0 && m < inf) (zero, NaN or infinite), E(d) = the call's constant background. Rays
+ *      outside crt_trace_async's contract are shaded as misses, so they come here too.
+ *   3. The face, ties in this order: ax >= ay && ax >= az: x > 0 ? 0 (+X) : 1 (-X); else ay >= az:
+ *      y > 0 ? 2 (+Y) : 3 (-Y); else z > 0 ? 4 (+Z) : 5 (-Z).
+ *   4. (u, v), the inverse of crt_lens_rays_async's CUBE table, each one division by m:
+ *        +X: u = -z / m, v = -y / m     -X: u = z / m, v = -y / m     +Y: u = x / m, v = z / m
+ *        -Y: u = x / m, v = -z / m      +Z: u = x / m, v = -y / m     -Z: u = -x / m, v = -y / m
+ *   5. h = 0.5 * (double)n, formed once; fx = (u + 1.0) * h, fy = (v + 1.0) * h.
+ *   6. NEAREST: col = clamp((int)floor(fx), 0, n - 1), row likewise from fy; E = the texel at row
+ *      face * n + row, column col.
+ *   7. BILINEAR: gx = fx - 0.5, x0 = floor(gx), wx = gx - x0, the same for y; the columns x0 and
+ *      x0 + 1 and the rows y0 and y0 + 1 are each clamped to [0, n - 1] as integers, inside the face
+ *      (no texel of another face is read); with cXY the texel at column X, row Y, per channel
+ *        a = c00 + wx * (c10 - c00),  b = c01 + wx * (c11 - c01),  E = a + wy * (b - a).
+ *      A map of equal finite texels gives that texel exactly.
+ * The path's output is 0 + T * E(d) per channel, T its throughput, as it is 0 + T * background
+ * without an environment. Floats are converted to integers only after the range check of step 2
+ * and the indices are clamped as integers: no d reads outside the map. Texel values are not
+ * inspected; a non-finite one propagates as the arithmetic above propagates it.
+ *
+ * The *_env entries are their namesakes with one more argument: same buffers, same rules, same
+ * results for every path that does not end in a miss. CRT_E_INVALID in addition, checked with the
+ * other rules before any device work (the message names the rule): env NULL; env->texels NULL;
+ * face_size 0 or above 16384; an unknown filter; a component of right, up or forward not finite.
+ * max_depth == 0 still writes +0 with a memset. env is read during the call only; the texels must
+ * stay valid and unchanged until the enqueued work has run. */
+int crt_radiance_env_async(const crt_scene* scene, int device, const double* d_rays, size_t n,
+                           const uint32_t* d_states, const crt_radiance_params* params, const crt_env* env,
+                           double* d_rgb, void* stream);
+int crt_probes_env_async(const crt_scene* scene, int device, const double* d_points, const double* d_normals,
+                         size_t n, const crt_probe_params* params, const crt_env* env, double* d_coeff,
+                         void* stream);
+int crt_render_lens_env_async(const crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens,
+                              const crt_env* env, double* d_rgb, void* stream);
+/* crt_render_lens for a HOST array, blocking; env->texels is HOST memory here, uploaded for the call
+ * and freed after it (the C++ drop-in's Camera::render_lens(world, lens, env)). */
+int crt_render_lens_env(crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens,
+                        const crt_env* env, double* rgb);
+
 /* ---- lens renders in passes ------------------------------------------------------------------
  * A lens render cut into passes, with the state the camera-agnostic calls read: crt_noise_estimate,
  * crt_adaptive_update, crt_pixel_variance_async and crt_denoise_async take d_sum, d_noise, block
