@@ -167,11 +167,12 @@ def scatter(crt, kind, color, param, d, n, front, rng):
     return nd, rng
 
 
-def ray_color(orc, scene, rays, states, max_depth, background, t_min=1e-5, env=None, crt=None):
+def ray_color(orc, scene, rays, states, max_depth, background, t_min=1e-5, env=None, crt=None, bvh=None):
     """crt_radiance_async's (or, with env, crt_radiance_env_async's) output for rays (n, 6) and LCG
     states (n,) uint32: (rgb (n, 3), how each path ended (n,) of MISS / LIGHT / ABSORBED / DEPTH, its
     last direction (n, 3), its throughput at the end (n, 3)). A ray outside the query contract is a
-    first-segment miss, never traced. max_depth == 0: zeros, every path ends as DEPTH."""
+    first-segment miss, never traced. max_depth == 0: zeros, every path ends as DEPTH. bvh: the
+    scene's BVH parameters for oracle.hits (num_buckets, max_prims) where they are not the defaults."""
     if crt is None:
         import cpp_raytracer_amd as crt
     rays = np.array(rays, np.float64).reshape(-1, 6)
@@ -191,7 +192,7 @@ def ray_color(orc, scene, rays, states, max_depth, background, t_min=1e-5, env=N
     for depth_left in range(max_depth, 0, -1):
         if len(live) == 0:
             break
-        h = orc.hits(scene, np.concatenate([o[live], d[live]], 1), t_min)
+        h = orc.hits(scene, np.concatenate([o[live], d[live]], 1), t_min, **(bvh or {}))
         hit = h["prim"] >= 0
         missed.append(live[~hit])
         nxt = []
