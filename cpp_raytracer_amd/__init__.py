@@ -22,7 +22,7 @@ from ._capi import (CRT_BOX, CRT_DIELECTRIC, CRT_DIFFUSE_LIGHT, CRT_LAMBERTIAN, 
                     DenoiseParams, RenderStats, SceneInfo, Tiling, TraceParams, CRT_TRACE_ANY, CRT_TRACE_PLAIN,
                     RadianceParams, CRT_RADIANCE_PLAIN, ProbeParams, CRT_PROBE_SPHERE, CRT_PROBE_HEMISPHERE,
                     CRT_SH_RADIANCE, CRT_SH_IRRADIANCE, Lens, CRT_LENS_PINHOLE, CRT_LENS_ORTHOGRAPHIC,
-                    CRT_LENS_EQUIRECT, CRT_LENS_FISHEYE, CRT_LENS_CUBE, EnvView, CRT_ENV_NEAREST, CRT_ENV_BILINEAR,
+                    CRT_LENS_EQUIRECT, CRT_LENS_FISHEYE, CRT_LENS_CUBE, EnvView, EnvSamplerView, CRT_ENV_NEAREST, CRT_ENV_BILINEAR,
                     check, lib)
 
 __all__ = [
@@ -35,7 +35,7 @@ __all__ = [
     "ProbeParams", "CRT_PROBE_SPHERE", "CRT_PROBE_HEMISPHERE", "CRT_SH_RADIANCE", "CRT_SH_IRRADIANCE", "sh_eval",
     "Lens", "make_lens", "CRT_LENS_PINHOLE", "CRT_LENS_ORTHOGRAPHIC", "CRT_LENS_EQUIRECT", "CRT_LENS_FISHEYE",
     "CRT_LENS_CUBE", "LensRender",
-    "Env", "EnvView", "make_env", "CRT_ENV_NEAREST", "CRT_ENV_BILINEAR",
+    "Env", "EnvView", "EnvSamplerView", "EnvTables", "make_env", "CRT_ENV_NEAREST", "CRT_ENV_BILINEAR",
     "CRT_LAMBERTIAN", "CRT_METAL", "CRT_DIELECTRIC", "CRT_DIFFUSE_LIGHT",
     "CRT_SPHERE", "CRT_PARALLELOGRAM", "CRT_BOX",
 ]
@@ -195,17 +195,56 @@ def make_lens(kind, origin=(0.0, 0.0, 0.0), forward=(0.0, 0.0, -1.0), up=(0.0, 1
 _ENV_FILTERS = {"nearest": CRT_ENV_NEAREST, "bilinear": CRT_ENV_BILINEAR}
 
 
+class _DevicePtr:
+    """A device allocation of `count` doubles as torch.as_tensor reads it."""
+
+    def __init__(self, ptr: int, shape):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f8", "data": (ptr, False), "version": 2}
+
+
+class EnvTables:
+    """A sampler's tables (crt_env_sampler_view), copied: w and c (6n, n), m (6n,) float64 tensors on
+    the sampler's device, and the total W."""
+
+    def __init__(self, w, c, m, W: float):
+        self.w, self.c, self.m, self.W = w, c, m, W
+
+
 class Env:
     """A cube-map environment for GpuScene.radiance / probes / render_lens (make_env): the (6n, n, 3)
-    float64 tensor on a GPU, kept alive here, and the crt_env view of it that the calls read."""
+    float64 tensor on a GPU, kept alive here, and the crt_env view of it that the calls read. With
+    make_env(importance=True) it owns a crt_env_sampler (freed with it) and the calls take the
+    *_env_sampled entries: next-event estimation of the map with MIS."""
 
-    def __init__(self, texels, view: EnvView):
+    def __init__(self, texels, view: EnvView, sampler: Optional[int] = None):
         self.texels = texels
         self.view = view
+        self.sampler = sampler  # the crt_env_sampler handle, or None
 
     @property
     def face_size(self) -> int:
         return int(self.view.face_size)
+
+    @property
+    def tables(self) -> EnvTables:
+        """The sampler's tables as the device holds them (CrtError without importance=True)."""
+        import torch
+        if self.sampler is None:
+            raise CrtError("Env.tables: the Env has no sampler (make_env(..., importance=True))")
+        v = EnvSamplerView()
+        check(lib().crt_env_sampler_view(C.c_void_p(self.sampler), C.byref(v)), "crt_env_sampler_view")
+        n, dev = int(v.env.face_size), self.texels.device
+        with torch.cuda.device(dev):
+            torch.cuda.synchronize(dev)
+            w, c, m = (torch.as_tensor(_DevicePtr(p, shape), device=dev).clone()
+                       for p, shape in ((v.w, (6 * n, n)), (v.c, (6 * n, n)), (v.m, (6 * n,))))
+            torch.cuda.synchronize(dev)
+        return EnvTables(w, c, m, float(v.W))
+
+    def __del__(self):
+        h, self.sampler = getattr(self, "sampler", None), None
+        if h is not None and _capi._lib is not None:
+            _capi._lib.crt_env_sampler_free(C.c_void_p(h))
 
 
 def _env_texels_ok(t) -> bool:
@@ -214,12 +253,16 @@ def _env_texels_ok(t) -> bool:
             t.shape[2] == 3 and t.shape[1] >= 1 and t.shape[0] == 6 * t.shape[1] and t.is_contiguous())
 
 
-def make_env(texels, forward=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), filter="bilinear") -> Env:
+def make_env(texels, forward=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), filter="bilinear", importance: bool = False) -> Env:
     """An environment from a cube frame: texels is a contiguous (6n, n, 3) float64 torch tensor on a
     GPU in render_lens's "cube" layout (a render_lens(cam, make_lens("cube")) frame as it is; it is
     not copied, and the Env keeps it alive). The basis is built as make_lens builds it; filter is
     "nearest" or "bilinear" (or a CRT_ENV_* constant). Paths that leave the scene then see the map
-    in place of the constant background (include/crt_render.h, crt_env)."""
+    in place of the constant background (include/crt_render.h, crt_env). importance=True builds a
+    luminance sampler of the map on the texels' device (crt_env_sampler_create: it waits for that
+    device, and the texels must then stay unchanged): radiance, probes and render_lens sample the map
+    at every Lambertian bounce and weight it against the bounce's own escape (MIS), so a small bright
+    region no longer has to be found by chance. The face size is then at most 2048."""
     if isinstance(filter, str):
         if filter not in _ENV_FILTERS:
             raise CrtError(f"make_env: filter must be one of {sorted(_ENV_FILTERS)}")
@@ -230,8 +273,15 @@ def make_env(texels, forward=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), filter="bilin
         raise CrtError("make_env: the face size must be at most 16384")
     r, u, f = _basis("make_env", forward, up)
     D3 = _capi.D3
-    return Env(texels, EnvView(texels.data_ptr(), texels.shape[1], int(filter), D3(*r.tolist()), D3(*u.tolist()),
-                               D3(*f.tolist())))
+    view = EnvView(texels.data_ptr(), texels.shape[1], int(filter), D3(*r.tolist()), D3(*u.tolist()), D3(*f.tolist()))
+    if not importance:
+        return Env(texels, view)
+    import torch
+    handle = C.c_void_p()
+    with torch.cuda.device(texels.device):
+        torch.cuda.synchronize(texels.device)  # the build reads the texels on the device's null stream
+        check(lib().crt_env_sampler_create(texels.device.index, C.byref(view), C.byref(handle)), "crt_env_sampler_create")
+    return Env(texels, view, handle.value)
 
 
 def _env_on(who: str, env, device: int) -> EnvView:
@@ -672,16 +722,23 @@ class GpuScene:
 
     def radiance_async(self, device: int, rays_ptr: int, n: int, out_ptr: int, states_ptr: int = 0, *,
                        max_depth: int, background, t_min: float = 1e-5, base_seed: int = 0, flags: int = 0,
-                       stream: int = 0, env: Optional[EnvView] = None) -> None:
+                       stream: int = 0, env: Optional[EnvView] = None, sampler: int = 0) -> None:
         """Enqueue a radiance query on device buffers (crt_radiance_async): n rays of 6 doubles at
         rays_ptr, each the first segment of one path of ray_color with `max_depth` bounces over
         (t_min, inf). Path i's LCG state is the uint32 states_ptr[i], or sample_seed(base_seed, i, 0)
         with states_ptr = 0. Three doubles a path go to out_ptr: what the sample adds to a pixel's
         sum in a render. CRT_RADIANCE_PLAIN takes one thread a path: the same bits. The scene must be
         uploaded to `device`. env: an EnvView (crt_env) whose texels are on `device`: paths that end in
-        a miss see it in place of `background` (crt_radiance_env_async)."""
+        a miss see it in place of `background` (crt_radiance_env_async). sampler: a crt_env_sampler
+        handle built on `device` (Env.sampler) in place of env (crt_radiance_env_sampled_async)."""
         prm = RadianceParams(max_depth, base_seed & 0xFFFFFFFF, _capi.D3(*[float(v) for v in background]), t_min,
                              flags, 0)
+        if sampler:
+            check(lib().crt_radiance_env_sampled_async(self._h, device, C.c_void_p(rays_ptr or None), n,
+                                                       C.c_void_p(states_ptr or None), C.byref(prm), C.c_void_p(sampler),
+                                                       C.c_void_p(out_ptr or None), C.c_void_p(stream)),
+                  "crt_radiance_env_sampled_async")
+            return
         if env is not None:
             check(lib().crt_radiance_env_async(self._h, device, C.c_void_p(rays_ptr or None), n,
                                                C.c_void_p(states_ptr or None), C.byref(prm), C.byref(env),
@@ -721,7 +778,8 @@ class GpuScene:
                                     states.data_ptr() if states is not None else 0, max_depth=max_depth,
                                     background=background, t_min=t_min, base_seed=base_seed,
                                     flags=CRT_RADIANCE_PLAIN if plain else 0,
-                                    stream=torch.cuda.current_stream(device).cuda_stream, env=view)
+                                    stream=torch.cuda.current_stream(device).cuda_stream, env=view,
+                                    sampler=(env.sampler or 0) if env is not None else 0)
             return out
 
     @staticmethod
@@ -735,15 +793,23 @@ class GpuScene:
 
     def probes_async(self, device: int, points_ptr: int, normals_ptr: int, n: int, out_ptr: int, *, samples: int,
                      mode=CRT_PROBE_SPHERE, max_depth: int, background, t_min: float = 1e-5, base_seed: int = 0,
-                     batch_probes: int = 0, flags: int = 0, stream: int = 0, env: Optional[EnvView] = None) -> None:
+                     batch_probes: int = 0, flags: int = 0, stream: int = 0, env: Optional[EnvView] = None,
+                     sampler: int = 0) -> None:
         """Enqueue a probe bake on device buffers (crt_probes_async): n points of 3 doubles at
         points_ptr, with CRT_PROBE_HEMISPHERE their unit normals at normals_ptr (0 with
         CRT_PROBE_SPHERE). `samples` directions a probe are drawn on the device, path-traced as
         radiance_async traces them and reduced in a fixed order: n x 9 x 3 doubles (SH coefficients of
         bands 0..2 per channel) or n x 1 x 3 (irradiance) go to out_ptr. batch_probes sizes the
         internal batches only; flags may hold CRT_RADIANCE_PLAIN: the same bits either way. The scene
-        must be uploaded to `device`. env: as radiance_async's (crt_probes_env_async)."""
+        must be uploaded to `device`. env, sampler: as radiance_async's (crt_probes_env_async,
+        crt_probes_env_sampled_async)."""
         prm = self._probe_params(samples, mode, max_depth, background, t_min, base_seed, batch_probes, flags)
+        if sampler:
+            check(lib().crt_probes_env_sampled_async(self._h, device, C.c_void_p(points_ptr or None),
+                                                     C.c_void_p(normals_ptr or None), n, C.byref(prm),
+                                                     C.c_void_p(sampler), C.c_void_p(out_ptr or None),
+                                                     C.c_void_p(stream)), "crt_probes_env_sampled_async")
+            return
         if env is not None:
             check(lib().crt_probes_env_async(self._h, device, C.c_void_p(points_ptr or None),
                                              C.c_void_p(normals_ptr or None), n, C.byref(prm), C.byref(env),
@@ -791,7 +857,8 @@ class GpuScene:
                                   out.data_ptr(), samples=samples, mode=mode, max_depth=max_depth, background=background,
                                   t_min=t_min, base_seed=base_seed, batch_probes=batch_probes,
                                   flags=CRT_RADIANCE_PLAIN if plain else 0,
-                                  stream=torch.cuda.current_stream(device).cuda_stream, env=view)
+                                  stream=torch.cuda.current_stream(device).cuda_stream, env=view,
+                                  sampler=(env.sampler or 0) if env is not None else 0)
             return out
 
     def probe_rays(self, points, normals=None, samples: int = 1024, mode: str = "sphere", base_seed: int = 0):
@@ -884,11 +951,17 @@ class GpuScene:
             return rays, states
 
     def render_lens_async(self, device: int, cam: Camera, lens: Lens, out_ptr: int, stream: int = 0,
-                          env: Optional[EnvView] = None) -> None:
+                          env: Optional[EnvView] = None, sampler: int = 0) -> None:
         """Enqueue a whole-frame render through `lens` (crt_render_lens_async) into the device buffer
         at out_ptr (image_h * image_w * 3 doubles): the rays of lens_rays, traced as radiance_async
         traces them and summed per pixel in render_async's order. The scene must be uploaded to
-        `device`. env: as radiance_async's (crt_render_lens_env_async)."""
+        `device`. env, sampler: as radiance_async's (crt_render_lens_env_async,
+        crt_render_lens_env_sampled_async)."""
+        if sampler:
+            check(lib().crt_render_lens_env_sampled_async(self._h, device, C.byref(cam), C.byref(lens),
+                                                          C.c_void_p(sampler), C.c_void_p(out_ptr or None),
+                                                          C.c_void_p(stream)), "crt_render_lens_env_sampled_async")
+            return
         if env is not None:
             check(lib().crt_render_lens_env_async(self._h, device, C.byref(cam), C.byref(lens), C.byref(env),
                                                   C.c_void_p(out_ptr or None), C.c_void_p(stream)),
@@ -911,7 +984,7 @@ class GpuScene:
             out = torch.empty((cam.image_h, cam.image_w, 3), dtype=torch.float64, device=torch.device("cuda", device))
             self.upload(device)
             self.render_lens_async(device, cam, lens, out.data_ptr(), torch.cuda.current_stream(device).cuda_stream,
-                                   env=view)
+                                   env=view, sampler=(env.sampler or 0) if env is not None else 0)
             return out
 
     def render_lens_pass(self, device: int, cam: Camera, lens: Lens, first: int, count: int, sum_ptr: int,

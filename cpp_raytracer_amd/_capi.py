@@ -147,6 +147,14 @@ CRT_ENV_NEAREST, CRT_ENV_BILINEAR = 0, 1
 assert C.sizeof(EnvView) == 88
 
 
+class EnvSamplerView(C.Structure):
+    """struct crt_env_sampler_view: the recorded crt_env, the device pointers of the tables and W."""
+    _fields_ = [("env", EnvView), ("w", C.c_void_p), ("c", C.c_void_p), ("m", C.c_void_p), ("W", C.c_double)]
+
+
+assert C.sizeof(EnvSamplerView) == 120
+
+
 class LaunchPlan(C.Structure):
     _fields_ = ([(n, C.c_uint32) for n in ("kernel", "klass", "entry_bytes", "five_waves", "prim_mode", "plain_route",
                                            "depth", "block")] + [("num_nodes", C.c_uint64)] +
@@ -265,6 +273,16 @@ EXPORTS = {
     "crt_render_lens_env_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), P(EnvView), C.c_void_p,
                                             C.c_void_p]),
     "crt_render_lens_env": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), P(EnvView), C.c_void_p]),
+    "crt_env_sampler_create": (C.c_int, [C.c_int, P(EnvView), P(C.c_void_p)]),
+    "crt_env_sampler_free": (C.c_int, [C.c_void_p]),
+    "crt_env_sampler_view": (C.c_int, [C.c_void_p, P(EnvSamplerView)]),
+    "crt_radiance_env_sampled_async": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                 P(RadianceParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "crt_probes_env_sampled_async": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                               P(ProbeParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "crt_render_lens_env_sampled_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]),
+    "crt_render_lens_env_sampled": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), P(EnvView), C.c_void_p]),
     "crt_render_lens_pass_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), C.c_uint32, C.c_uint32,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "crt_lens_centre_rays_async": (C.c_int, [C.c_int, P(Camera), P(Lens), C.c_void_p, C.c_void_p]),

@@ -30,6 +30,7 @@
 #include "crt_ray_gate.h"
 #include "crt_schlick.h"
 #include "crt_env.h"
+#include "crt_env_sampler.h"
 
 #pragma clang fp contract(off)
 
@@ -1959,9 +1960,16 @@ __device__ __forceinline__ void start_path(const CamView& C, uint32_t row, uint3
 // One level of ray_color (camera.h:205-258) after the closest-hit query: scatters
 // (material.h:64-263) into the next ray, or ends the path adding T * (background | emission) to
 // acc. Returns true when the path has ended (miss, light, absorption).
-template <bool LS, bool SPH = false, bool QONLY = false, bool FAST = false>
+// What shade tells the NEE instances (nee_segment) about a hit that scattered: the normal facing
+// the ray and the material kind. Every other instance compiles it out.
+struct ShadeOut {
+    double n[3];
+    uint32_t kind;
+};
+
+template <bool LS, bool SPH = false, bool QONLY = false, bool FAST = false, bool NEE = false>
 __device__ __forceinline__ bool shade(const SceneView& S, const CamView& C, Path& P, bool hit,
-                                      uint32_t ref, double t, double acc[3]) {
+                                      uint32_t ref, double t, double acc[3], ShadeOut* ex = nullptr) {
     if (!hit) {
         acc[0] = acc[0] + P.T[0] * C.bg[0];
         acc[1] = acc[1] + P.T[1] * C.bg[1];
@@ -2048,6 +2056,10 @@ __device__ __forceinline__ bool shade(const SceneView& S, const CamView& C, Path
     P.o[0] = p[0]; P.o[1] = p[1]; P.o[2] = p[2];
     P.d[0] = nd[0]; P.d[1] = nd[1]; P.d[2] = nd[2];
     P.depth -= 1;
+    if constexpr (NEE) {
+        ex->n[0] = n[0]; ex->n[1] = n[1]; ex->n[2] = n[2];
+        ex->kind = kind;
+    }
     return false;
 }
 
@@ -2081,6 +2093,11 @@ __device__ __forceinline__ void stage_lds(unsigned char* dst, const void* src, u
 // 1939); with v10's block pools 5 had measured +0.7%. The HBM-scene kernels lose 14% at 5.
 #ifndef CRT_WAVES_PER_EU_LDS
 #define CRT_WAVES_PER_EU_LDS 4
+#endif
+// The NEE instances of radiance_kernel carry about 16 more VGPRs a lane (Nee) than instances that
+// sit at 107 to 123 of 128: three waves per SIMD (168 VGPRs) keep them out of scratch.
+#ifndef CRT_WAVES_PER_EU_NEE
+#define CRT_WAVES_PER_EU_NEE 3
 #endif
 #ifndef CRT_SHADE_BATCH
 #define CRT_SHADE_BATCH 48
@@ -3167,8 +3184,13 @@ struct Radiance {
 struct RadianceEnv : Radiance {
     crt_env env;
 };
-template <bool ENV>
-using RadianceOf = std::conditional_t<ENV, RadianceEnv, Radiance>;
+// The NEE instances' launch (crt_radiance_env_sampled_async): the sampler's recorded environment
+// and its tables, in the kernel arguments too, so scene_layout still decides as without one.
+struct RadianceNee : RadianceEnv {
+    EnvTables tb;
+};
+template <bool ENV, bool NEE = false>
+using RadianceOf = std::conditional_t<NEE, RadianceNee, std::conditional_t<ENV, RadianceEnv, Radiance>>;
 
 // A path that ends in a miss under an environment: 0 + T * E(P.d) (crt_env.h) where shade's miss
 // branch gives 0 + T * bg
@@ -3178,6 +3200,85 @@ __device__ __forceinline__ void env_miss(const crt_env& E, const CamView& C, con
     acc[0] = acc[0] + P.T[0] * e[0];
     acc[1] = acc[1] + P.T[1] * e[1];
     acc[2] = acc[2] + P.T[2] * e[2];
+}
+
+// What a path of the NEE instances carries besides its Path (include/crt_render.h, the estimator):
+// what it gathered, the previous bounce's density, and across a shadow segment the scattered
+// direction to go on with and the sample's weight.
+struct Nee {
+    double acc[3];
+    double pb;
+    double nd[3];
+    double f;
+    bool has_pb;  // false: pb is "none" (the path's start, after a Metal or Dielectric bounce)
+    bool shadow;  // the segment being traced is a shadow segment along P.d = d_s
+};
+
+__device__ __forceinline__ void nee_start(Nee& N) {
+    N.acc[0] = 0; N.acc[1] = 0; N.acc[2] = 0;
+    N.has_pb = false;
+    N.shadow = false;
+}
+
+__device__ __forceinline__ double dot3(const double a[3], const double b[3]) {
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
+}
+
+__device__ __forceinline__ void nee_add(const crt_env& E, const CamView& C, const Path& P, double f, double acc[3]) {
+    double e[3];
+    env_lookup(E, P.d, C.bg, e);
+    acc[0] = acc[0] + (P.T[0] * e[0]) * f;
+    acc[1] = acc[1] + (P.T[1] * e[1]) * f;
+    acc[2] = acc[2] + (P.T[2] * e[2]) * f;
+}
+
+// One finished segment of a path of the NEE instances, the header's estimator: true when the path
+// has ended (N.acc is its output), false when P holds the next segment to trace: the scattered ray,
+// or first the shadow ray of a Lambertian bounce (the same origin; N keeps the scattered direction).
+template <bool LS, bool SPH>
+__device__ __forceinline__ bool nee_segment(const SceneView& S, const CamView& C, const RadianceNee& Q, Path& P,
+                                            Nee& N, bool found, uint32_t ref, double tmax) {
+    constexpr double kPi = 3.141592653589793;
+    if (N.shadow) {  // any hit occludes; a free segment adds the sample
+        if (!found) nee_add(Q.env, C, P, N.f, N.acc);
+        P.d[0] = N.nd[0]; P.d[1] = N.nd[1]; P.d[2] = N.nd[2];
+        N.shadow = false;
+        return false;
+    }
+    if (!found) {  // escape along d, weighted against the sampler unless pb is none
+        double f = 1.0;
+        if (N.has_pb) {
+            const double sum = env_pdf(Q.env, Q.tb, P.d) + N.pb;
+            f = sum > 0 ? N.pb / sum : 0.0;
+        }
+        nee_add(Q.env, C, P, f, N.acc);
+        return true;
+    }
+    ShadeOut X;
+    if (shade<LS, SPH, false, false, true>(S, C, P, true, ref, tmax, N.acc, &X)) return true;  // a light, or absorbed
+    if (P.depth == 0) return true;
+    if (X.kind != CRT_LAMBERTIAN) {
+        N.has_pb = false;
+        return false;
+    }
+    const double xi1 = rnd_01(P.rng);
+    const double xi2 = rnd_01(P.rng);
+    const double xi3 = rnd_01(P.rng);
+    const double xi4 = rnd_01(P.rng);
+    double ds[3];
+    env_sample(Q.env, Q.tb, xi1, xi2, xi3, xi4, ds);
+    const double cs = dot3(X.n, ds) / sqrt(dot3(ds, ds));
+    const double pbs = cs / kPi;
+    const double pes = env_pdf(Q.env, Q.tb, ds);
+    N.pb = (dot3(X.n, P.d) / sqrt(dot3(P.d, P.d))) / kPi;
+    N.has_pb = true;
+    if (cs > 0 && pes > 0) {
+        N.nd[0] = P.d[0]; N.nd[1] = P.d[1]; N.nd[2] = P.d[2];
+        P.d[0] = ds[0]; P.d[1] = ds[1]; P.d[2] = ds[2];
+        N.f = pbs / (pes + pbs);
+        N.shadow = true;
+    }
+    return false;
 }
 
 // path `ray` of a launch, before its first segment. False: the caller's ray is outside the query
@@ -3195,8 +3296,9 @@ __device__ __forceinline__ bool load_path(const Radiance& Q, uint32_t ray, Path&
 // CRT_RADIANCE_PLAIN: ray_color as a loop of trace() and shade, one thread per path
 // [first, first + gridDim.x * kBlock) of the call. Scattered rays go to trace() as they are: it is
 // the reference's sequence for any ray. ENV: a miss ends the path with env_miss instead of shade.
-template <bool ENV = false>
-__global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, CamView C, RadianceOf<ENV> Q, uint32_t first,
+// NEE (on top of ENV): every finished segment goes through nee_segment, shadow segments included.
+template <bool ENV = false, bool NEE = false>
+__global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, CamView C, RadianceOf<ENV, NEE> Q, uint32_t first,
                                                                 uint32_t* __restrict__ gstack) {
     const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
     if (slot >= Q.n - first) return;
@@ -3208,18 +3310,26 @@ __global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, Cam
     bool traced = load_path(Q, i, P);
     LaneCounters ctr{};
     double acc[3] = {0, 0, 0};
+    [[maybe_unused]] Nee N;
+    if constexpr (NEE) nee_start(N);
     while (true) {
         double tmax = __builtin_inf();
         uint32_t ref = 0;
         const bool found = traced && trace<uint32_t, false>(S, st, P.o, P.d, C.t_min, tmax, ref, ctr);
         traced = true;
-        if constexpr (ENV) {
+        if constexpr (NEE) {
+            if (nee_segment<false, false>(S, C, Q, P, N, found, ref, tmax)) break;
+            continue;
+        } else if constexpr (ENV) {
             if (!found) {
                 env_miss(Q.env, C, P, acc);
                 break;
             }
         }
         if (shade<false>(S, C, P, found, ref, tmax, acc) || P.depth == 0) break;
+    }
+    if constexpr (NEE) {
+        acc[0] = N.acc[0]; acc[1] = N.acc[1]; acc[2] = N.acc[2];
     }
     double* dst = Q.rgb + 3 * static_cast<size_t>(i);
     dst[0] = acc[0];
@@ -3237,9 +3347,13 @@ __global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, Cam
 // one). Every segment runs over (t_min, +inf) with t_min >= 0 (the ABI's rule), so the leaf filters
 // hold as in a render. The camera copy in LDS is render_kernel's (shade reads the background from
 // it). ENV: a lane in kDone without a hit ends its path with env_miss instead of shade.
-template <typename SE, bool GSTACK, bool LSCENE, int PM, bool ENV = false>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LSCENE ? CRT_WAVES_PER_EU_LDS : CRT_WAVES_PER_EU, 8))) void radiance_kernel(
-    SceneView Sg, CamView C, Work W, RadianceOf<ENV> Q, SE* __restrict__ gstack) {
+// NEE (on top of ENV): a lane in kDone hands its finished segment to nee_segment. A Lambertian
+// bounce may leave a shadow ray in P; it runs through the same ray_setup, walk_round and leaf_step
+// rounds as any segment (closest hit: only "any hit" enters), and nee_segment then puts the saved
+// scattered direction back. The lane's Nee stays in registers across all of it.
+template <typename SE, bool GSTACK, bool LSCENE, int PM, bool ENV = false, bool NEE = false>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NEE ? CRT_WAVES_PER_EU_NEE : LSCENE ? CRT_WAVES_PER_EU_LDS : CRT_WAVES_PER_EU, 8))) void radiance_kernel(
+    SceneView Sg, CamView C, Work W, RadianceOf<ENV, NEE> Q, SE* __restrict__ gstack) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr bool kSphOnly = PM == 0;
     SceneView S = Sg;
@@ -3262,10 +3376,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LSCENE ?
     Path P;
     Trav R;
     R.state = kIdle;
+    [[maybe_unused]] Nee N;
     bool need = true, cont = false;
     while (true) {
         set_prio<kPrioInit>();
         bool start = draw_batch(Q.queue, Q.batches, Q.n, lane, need, dry, b_base, b_cnt, b_pos, ray);
+        if constexpr (NEE) {
+            if (start) nee_start(N);
+        }
         if (start && !load_path(Q, ray, P)) {  // outside the contract: a miss, never traced
             start = false;
             R.found = false;
@@ -3293,7 +3411,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LSCENE ?
         if (R.state == kDone) {
             double acc[3] = {0, 0, 0};
             bool ended = true;
-            if constexpr (ENV) {
+            if constexpr (NEE) {
+                ended = nee_segment<LSCENE, kSphOnly>(S, CL, Q, P, N, R.found, R.ref, R.tmax);
+                acc[0] = N.acc[0]; acc[1] = N.acc[1]; acc[2] = N.acc[2];
+            } else if constexpr (ENV) {
                 if (!R.found) env_miss(Q.env, CL, P, acc);
                 else ended = shade<LSCENE, kSphOnly>(S, CL, P, R.found, R.ref, R.tmax, acc);
             } else {
@@ -4777,15 +4898,15 @@ int device_trace_host(crt_scene* s, int device, const double* rays, size_t n, co
 
 // ---- radiance queries (crt_radiance_async) -----------------------------------------------------
 // One radiance_kernel launch (persistent_grid: its grid and scratch)
-template <typename SE, bool GSTACK, bool LSCENE, int PM, bool ENV>
+template <typename SE, bool GSTACK, bool LSCENE, int PM, bool ENV, bool NEE>
 static int launch_radiance(const crt_scene* s, int device, dev::Work W, size_t lds, const dev::CamView& C,
-                           dev::RadianceOf<ENV> Q, hipMemPool_t pool, hipStream_t stream) {
+                           dev::RadianceOf<ENV, NEE> Q, hipMemPool_t pool, hipStream_t stream) {
     lds = lds_tail(W, lds, radiance_tail(GSTACK, LSCENE));
-    const void* kfn = reinterpret_cast<const void*>(dev::radiance_kernel<SE, GSTACK, LSCENE, PM, ENV>);
+    const void* kfn = reinterpret_cast<const void*>(dev::radiance_kernel<SE, GSTACK, LSCENE, PM, ENV, NEE>);
     uint32_t blocks = 0;
     SE* gstack = nullptr;
     if (const int rc = persistent_grid(s, device, kfn, lds, Q.batches, GSTACK, pool, stream, blocks, gstack, Q.queue)) return rc;
-    hipLaunchKernelGGL((dev::radiance_kernel<SE, GSTACK, LSCENE, PM, ENV>), dim3(blocks), dim3(dev::kBlock), lds, stream,
+    hipLaunchKernelGGL((dev::radiance_kernel<SE, GSTACK, LSCENE, PM, ENV, NEE>), dim3(blocks), dim3(dev::kBlock), lds, stream,
                        view_of(s->dev[device]), C, W, Q, gstack);
     const hipError_t e = hipGetLastError();
     (void)hipFreeAsync(Q.queue, stream);
@@ -4795,44 +4916,47 @@ static int launch_radiance(const crt_scene* s, int device, dev::Work W, size_t l
 }
 
 // CRT_RADIANCE_PLAIN: plain_radiance_kernel (plain_launches)
-template <bool ENV>
-static int launch_plain_radiance(const crt_scene* s, int device, const dev::CamView& C, const dev::RadianceOf<ENV>& Q,
+template <bool ENV, bool NEE>
+static int launch_plain_radiance(const crt_scene* s, int device, const dev::CamView& C, const dev::RadianceOf<ENV, NEE>& Q,
                                  hipMemPool_t pool, hipStream_t st) {
     const dev::SceneView S = view_of(s->dev[device]);
     return plain_launches(s, Q.n, pool, st, "plain_radiance_kernel", [&](uint32_t blocks, uint32_t first, uint32_t* stacks) {
-        hipLaunchKernelGGL(dev::plain_radiance_kernel<ENV>, dim3(blocks), dim3(dev::kBlock), 0, st, S, C, Q, first, stacks);
+        hipLaunchKernelGGL((dev::plain_radiance_kernel<ENV, NEE>), dim3(blocks), dim3(dev::kBlock), 0, st, S, C, Q, first, stacks);
     });
 }
 
 // dispatch_trace's classes; every class takes the fast route (a path is many segments per queue
 // visit, unlike a single ray: DESIGN section 6e)
-template <typename SE, bool ENV>
+template <typename SE, bool ENV, bool NEE>
 static int dispatch_radiance(const crt_scene* s, int device, dev::Work W, const dev::CamView& C,
-                             const dev::RadianceOf<ENV>& Q, hipMemPool_t pool, hipStream_t st) {
+                             const dev::RadianceOf<ENV, NEE>& Q, hipMemPool_t pool, hipStream_t st) {
     const Layout L = scene_layout<SE>(s, W, camera_extra(), false);
     return by_class(L.cls, W.sphere_only != 0, [&](auto gstack, auto lscene, auto pm) {
-        return launch_radiance<SE, decltype(gstack)::value, decltype(lscene)::value, decltype(pm)::value, ENV>(s, device, W, L.lds, C, Q, pool, st);
+        return launch_radiance<SE, decltype(gstack)::value, decltype(lscene)::value, decltype(pm)::value, ENV, NEE>(s, device, W, L.lds, C, Q, pool, st);
     });
 }
 
 // the route of one call: the plain kernel, or the fast one for the scene's class and entry width
-template <bool ENV>
+template <bool ENV, bool NEE = false>
 static int route_radiance(const crt_scene* s, int device, const crt_radiance_params* prm, const dev::CamView& C,
-                          const dev::RadianceOf<ENV>& Q, hipMemPool_t pool, hipStream_t st) {
-    if (prm->flags & CRT_RADIANCE_PLAIN) return launch_plain_radiance<ENV>(s, device, C, Q, pool, st);
+                          const dev::RadianceOf<ENV, NEE>& Q, hipMemPool_t pool, hipStream_t st) {
+    if (prm->flags & CRT_RADIANCE_PLAIN) return launch_plain_radiance<ENV, NEE>(s, device, C, Q, pool, st);
     // device_trace's scene classes and interval rules; 0 <= t_min <= 2^100 here (crt_radiance_async)
     const DeviceCopy& c = s->dev[device];
     dev::Work W{};
     class_flags(s, flags_of(c), c.f32_ok, true, W);
     W.tmin32 = static_cast<float>(prm->t_min);
-    if (u16_entries(s)) return dispatch_radiance<uint16_t, ENV>(s, device, W, C, Q, pool, st);
-    return dispatch_radiance<uint32_t, ENV>(s, device, W, C, Q, pool, st);
+    if (u16_entries(s)) return dispatch_radiance<uint16_t, ENV, NEE>(s, device, W, C, Q, pool, st);
+    return dispatch_radiance<uint32_t, ENV, NEE>(s, device, W, C, Q, pool, st);
 }
 
 // env: null, or the call's environment (checked by crt_host.cpp; its texels on `device`): the ENV
 // instances. Without one the launch is the instances' without ENV, as before environments existed.
+// smp: null, or the sampler (built on `device`; crt_host.cpp checks it) whose recorded environment
+// and tables the NEE instances read; env is not used then.
 int device_radiance(const crt_scene* s, int device, const double* d_rays, size_t n, const uint32_t* d_states,
-                    const crt_radiance_params* prm, const crt_env* env, double* d_rgb, void* stream) {
+                    const crt_radiance_params* prm, const crt_env* env, double* d_rgb, void* stream,
+                    const crt_env_sampler* smp) {
     int rc = check_device(device);
     if (rc) return rc;
     if (!s->dev[device].valid)
@@ -4849,7 +4973,7 @@ int device_radiance(const crt_scene* s, int device, const double* d_rays, size_t
     C.t_min = prm->t_min;
     C.max_depth = prm->max_depth;
     C.base_seed = prm->base_seed;
-    dev::RadianceEnv Q{};
+    dev::RadianceNee Q{};
     Q.rays = d_rays;
     Q.states = d_states;
     Q.rgb = d_rgb;
@@ -4860,6 +4984,11 @@ int device_radiance(const crt_scene* s, int device, const double* d_rays, size_t
     hipMemPool_t pool = nullptr;
     rc = pass_pool(device, &pool);
     if (rc) return rc;
+    if (smp) {
+        Q.env = smp->env;
+        Q.tb = EnvTables{smp->w, smp->c, smp->m, smp->W};
+        return route_radiance<true, true>(s, device, prm, C, Q, pool, st);
+    }
     if (!env) return route_radiance<false>(s, device, prm, C, Q, pool, st);
     Q.env = *env;
     return route_radiance<true>(s, device, prm, C, Q, pool, st);

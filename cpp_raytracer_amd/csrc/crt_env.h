@@ -21,8 +21,15 @@ namespace crt {
 
 CRT_HD int env_clamp(int i, int n) { return i < 0 ? 0 : (i > n - 1 ? n - 1 : i); }
 
-// E(d) into out[3]; bg: the call's constant background, the value where d has no major axis
-CRT_HD void env_lookup(const crt_env& E, const double d[3], const double bg[3], double out[3]) {
+// Steps 1 to 5 of E(d): the face, (u, v), h and (fx, fy) of a direction. One copy for env_lookup and
+// for env_pdf (crt_env_sampler.h).
+struct EnvProj {
+    uint32_t face;
+    double u, v, h, fx, fy;
+};
+
+// false where d has no major axis (step 2): nothing of J is written then
+CRT_HD bool env_project(const crt_env& E, const double d[3], EnvProj& J) {
     const double x = (d[0] * E.right[0] + d[1] * E.right[1]) + d[2] * E.right[2];
     const double y = (d[0] * E.up[0] + d[1] * E.up[1]) + d[2] * E.up[2];
     const double z = (d[0] * E.forward[0] + d[1] * E.forward[1]) + d[2] * E.forward[2];
@@ -31,28 +38,36 @@ CRT_HD void env_lookup(const crt_env& E, const double d[3], const double bg[3], 
     m = m >= az ? m : az;
     // the comparisons above drop a NaN; m must carry it
     const bool ordered = ax == ax && ay == ay && az == az;
-    if (!(ordered && m > 0 && m < __builtin_inf())) {
+    if (!(ordered && m > 0 && m < __builtin_inf())) return false;
+    if (ax >= ay && ax >= az) {
+        J.face = x > 0 ? 0u : 1u;
+        J.u = (x > 0 ? -z : z) / m;
+        J.v = -y / m;
+    } else if (ay >= az) {
+        J.face = y > 0 ? 2u : 3u;
+        J.u = x / m;
+        J.v = (y > 0 ? z : -z) / m;
+    } else {
+        J.face = z > 0 ? 4u : 5u;
+        J.u = (z > 0 ? x : -x) / m;
+        J.v = -y / m;
+    }
+    J.h = 0.5 * static_cast<double>(E.face_size);
+    J.fx = (J.u + 1.0) * J.h;
+    J.fy = (J.v + 1.0) * J.h;
+    return true;
+}
+
+// E(d) into out[3]; bg: the call's constant background, the value where d has no major axis
+CRT_HD void env_lookup(const crt_env& E, const double d[3], const double bg[3], double out[3]) {
+    EnvProj J;
+    if (!env_project(E, d, J)) {
         out[0] = bg[0]; out[1] = bg[1]; out[2] = bg[2];
         return;
     }
-    uint32_t face;
-    double u, v;
-    if (ax >= ay && ax >= az) {
-        face = x > 0 ? 0u : 1u;
-        u = (x > 0 ? -z : z) / m;
-        v = -y / m;
-    } else if (ay >= az) {
-        face = y > 0 ? 2u : 3u;
-        u = x / m;
-        v = (y > 0 ? z : -z) / m;
-    } else {
-        face = z > 0 ? 4u : 5u;
-        u = (z > 0 ? x : -x) / m;
-        v = -y / m;
-    }
+    const uint32_t face = J.face;
+    const double fx = J.fx, fy = J.fy;
     const int n = static_cast<int>(E.face_size);
-    const double h = 0.5 * static_cast<double>(E.face_size);
-    const double fx = (u + 1.0) * h, fy = (v + 1.0) * h;
     const size_t row0 = static_cast<size_t>(face) * E.face_size;
     if (E.filter == CRT_ENV_NEAREST) {
         const int col = env_clamp(static_cast<int>(__builtin_floor(fx)), n);

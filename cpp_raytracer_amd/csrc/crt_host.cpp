@@ -1582,6 +1582,67 @@ int crt_radiance_env_async(const crt_scene* s, int device, const double* d_rays,
     return device_radiance(s, device, d_rays, n, d_states, params, env, d_rgb, stream);
 }
 
+// ---- luminance samplers: crt_env's rules, then the sampler's own, before any device work -----------
+static int check_sampler_env(const std::string& who, const crt_env* env) {
+    const int rc = check_env(who, env);
+    if (rc) return rc;
+    if (env->face_size > 2048) return fail(CRT_E_INVALID, who + "env->face_size must be at most 2048 for a sampler");
+    const double* b[3] = {env->right, env->up, env->forward};
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double g = (b[i][0] * b[j][0] + b[i][1] * b[j][1]) + b[i][2] * b[j][2];
+            if (!(std::fabs(g - (i == j ? 1.0 : 0.0)) <= 1e-9))
+                return fail(CRT_E_INVALID, who + "the env basis must be orthonormal (Gram matrix within 1e-9 of the identity)");
+        }
+    return CRT_OK;
+}
+
+static int check_sampler(const std::string& who, const crt_env_sampler* smp, int device) {
+    if (!smp) return fail(CRT_E_INVALID, who + "sampler is null");
+    if (smp->device != device)
+        return fail(CRT_E_INVALID, who + "the sampler was built on device " + std::to_string(smp->device));
+    return CRT_OK;
+}
+
+int crt_env_sampler_create(int device, const crt_env* env, crt_env_sampler** out) {
+    clear_error();
+    const std::string who = "crt_env_sampler_create: ";
+    if (!out) return fail(CRT_E_INVALID, who + "out is null");
+    *out = nullptr;
+    const int rc = check_sampler_env(who, env);
+    if (rc) return rc;
+    return device_env_sampler_create(device, env, out);
+}
+
+int crt_env_sampler_free(crt_env_sampler* sampler) {
+    clear_error();
+    return device_env_sampler_free(sampler);
+}
+
+int crt_env_sampler_view(const crt_env_sampler* sampler, struct crt_env_sampler_view* out) {
+    clear_error();
+    if (!sampler) return fail(CRT_E_INVALID, "crt_env_sampler_view: sampler is null");
+    if (!out) return fail(CRT_E_INVALID, "crt_env_sampler_view: out is null");
+    out->env = sampler->env;
+    out->w = sampler->w;
+    out->c = sampler->c;
+    out->m = sampler->m;
+    out->W = sampler->W;
+    return CRT_OK;
+}
+
+int crt_radiance_env_sampled_async(const crt_scene* s, int device, const double* d_rays, size_t n,
+                                   const uint32_t* d_states, const crt_radiance_params* params,
+                                   const crt_env_sampler* sampler, double* d_rgb, void* stream) {
+    clear_error();
+    const std::string who = "crt_radiance_env_sampled_async: ";
+    int rc = check_radiance(who, s, d_rays, "d_rays", n, params, d_rgb, "d_rgb");
+    if (rc == CRT_OK) rc = check_sampler(who, sampler, device);
+    if (rc) return rc;
+    if (n == 0) return CRT_OK;  // no work
+    return device_radiance(s, device, d_rays, n, d_states, params, &sampler->env, d_rgb, stream, sampler);
+}
+
 int crt_radiance(crt_scene* s, int device, const double* rays, size_t n, const uint32_t* states,
                  const crt_radiance_params* params, double* rgb) {
     clear_error();
@@ -1660,6 +1721,19 @@ int crt_probes_env_async(const crt_scene* s, int device, const double* d_points,
     if (n && !d_coeff) return fail(CRT_E_INVALID, who + "d_coeff is null (the output is required)");
     if (n == 0) return CRT_OK;  // no work
     return device_probes(s, device, d_points, d_normals, n, params, env, d_coeff, stream);
+}
+
+int crt_probes_env_sampled_async(const crt_scene* s, int device, const double* d_points, const double* d_normals,
+                                 size_t n, const crt_probe_params* params, const crt_env_sampler* sampler,
+                                 double* d_coeff, void* stream) {
+    clear_error();
+    const std::string who = "crt_probes_env_sampled_async: ";
+    int rc = check_probes(who, true, s, d_points, "d_points", d_normals, "d_normals", n, params);
+    if (rc == CRT_OK) rc = check_sampler(who, sampler, device);
+    if (rc) return rc;
+    if (n && !d_coeff) return fail(CRT_E_INVALID, who + "d_coeff is null (the output is required)");
+    if (n == 0) return CRT_OK;  // no work
+    return device_probes(s, device, d_points, d_normals, n, params, &sampler->env, d_coeff, stream, sampler);
 }
 
 int crt_probes(crt_scene* s, int device, const double* points, const double* normals, size_t n,
@@ -1789,6 +1863,28 @@ int crt_render_lens_env(crt_scene* s, int device, const crt_camera* cam, const c
     if (rc) return rc;
     if (!rgb) return fail(CRT_E_INVALID, who + "rgb is null (the output is required)");
     return device_render_lens_host(s, device, cam, lens, env, rgb);
+}
+
+int crt_render_lens_env_sampled_async(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens,
+                                      const crt_env_sampler* sampler, double* d_rgb, void* stream) {
+    clear_error();
+    const std::string who = "crt_render_lens_env_sampled_async: ";
+    int rc = check_lens(who, true, s, cam, lens, true);
+    if (rc == CRT_OK) rc = check_sampler(who, sampler, device);
+    if (rc) return rc;
+    if (!d_rgb) return fail(CRT_E_INVALID, who + "d_rgb is null (the output is required)");
+    return device_render_lens(s, device, cam, lens, &sampler->env, d_rgb, stream, sampler);
+}
+
+int crt_render_lens_env_sampled(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens,
+                                const crt_env* env, double* rgb) {
+    clear_error();
+    const std::string who = "crt_render_lens_env_sampled: ";
+    int rc = check_lens(who, true, s, cam, lens, true);
+    if (rc == CRT_OK) rc = check_sampler_env(who, env);
+    if (rc) return rc;
+    if (!rgb) return fail(CRT_E_INVALID, who + "rgb is null (the output is required)");
+    return device_render_lens_host(s, device, cam, lens, env, rgb, true);
 }
 
 // ---- lens renders in passes: check_lens's rules, then the pass's (check_pass), the adaptive

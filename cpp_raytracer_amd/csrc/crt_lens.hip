@@ -591,7 +591,7 @@ int device_lens_rays(int device, const crt_camera* cam, const crt_lens* lens, ui
 }
 
 int device_render_lens(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, const crt_env* env,
-                       double* d_rgb, void* stream) {
+                       double* d_rgb, void* stream, const crt_env_sampler* smp) {
     int rc = device_check(device);
     if (rc) return rc;
     if (!s->dev[device].valid)
@@ -627,7 +627,7 @@ int device_render_lens(const crt_scene* s, int device, const crt_camera* cam, co
         double* rgb = reinterpret_cast<double*>(scratch + records * 48);
         uint32_t* states = reinterpret_cast<uint32_t*>(scratch + records * (48 + 24));
         hipError_t e = ln::launch_rays(V, lens->kind, first, static_cast<uint32_t>(records), 0, spp, rays, states, st);
-        if (e == hipSuccess) rc = device_radiance(s, device, rays, records, states, &rp, env, rgb, st);
+        if (e == hipSuccess) rc = device_radiance(s, device, rays, records, states, &rp, env, rgb, st, smp);
         if (e == hipSuccess && rc == CRT_OK) {
             const dim3 grid((count + ln::kWavesPerBlock - 1) / ln::kWavesPerBlock), block(64 * ln::kWavesPerBlock);
             hipLaunchKernelGGL(ln::lens_reduce_kernel, grid, block, 0, st, rgb, count, spp, L, inv_spp, d_rgb + first * 3);
@@ -800,9 +800,10 @@ int device_lens_features(const crt_scene* s, int device, const crt_camera* cam, 
 
 // crt_render_lens: device_render_lens for a host array, blocking: the render on a stream of its
 // own, one copy back. env (null: none) has its texels in host memory here: uploaded for the call,
-// freed after it
+// freed after it. sampled: once the texels have arrived a sampler is built on them (blocking), the
+// render goes through it, and it is freed with them
 int device_render_lens_host(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, const crt_env* env,
-                            double* rgb) {
+                            double* rgb, bool sampled) {
     int rc = device_upload(s, device);
     if (rc) return rc;
     DeviceGuard g(device);
@@ -820,13 +821,19 @@ int device_render_lens_host(crt_scene* s, int device, const crt_camera* cam, con
         if (e == hipSuccess) e = hipMemcpyAsync(d_texels, env->texels, env_bytes, hipMemcpyHostToDevice, st);
         d_env.texels = d_texels;
     }
-    if (e == hipSuccess) rc = device_render_lens(s, device, cam, lens, env ? &d_env : nullptr, d_rgb, st);
+    crt_env_sampler* smp = nullptr;
+    if (e == hipSuccess && env && sampled) {
+        e = hipStreamSynchronize(st);
+        if (e == hipSuccess) rc = device_env_sampler_create(device, &d_env, &smp);
+    }
+    if (e == hipSuccess && rc == CRT_OK) rc = device_render_lens(s, device, cam, lens, env ? &d_env : nullptr, d_rgb, st, smp);
     if (e == hipSuccess && rc == CRT_OK) e = hipMemcpyAsync(rgb, d_rgb, bytes, hipMemcpyDeviceToHost, st);
     if (st) {
         const hipError_t se = hipStreamSynchronize(st);
         if (e == hipSuccess) e = se;
         (void)hipStreamDestroy(st);
     }
+    (void)device_env_sampler_free(smp);
     (void)hipFree(d_rgb);
     (void)hipFree(d_texels);
     if (rc) return rc;

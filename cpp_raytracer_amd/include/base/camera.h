@@ -99,18 +99,24 @@ struct Lens {
 // Extension (not in the reference): a cube-map environment for Camera::render_lens(world, lens, env)
 // (crt_env with the texels in host memory): what paths that leave the scene see in place of the
 // camera's constant background. The factory takes a cube frame as render_lens returns it for
-// Lens::cube (w x 6w) and builds the basis as Lens's factories do.
+// Lens::cube (w x 6w) and builds the basis as Lens's factories do. importance: render_lens samples the
+// map by luminance at every Lambertian bounce and weights it against the bounce's own escape
+// (crt_render_lens_env_sampled: next-event estimation with MIS), so a small bright region of the map
+// is no longer found by chance alone. The face size is then at most 2048.
 struct Environment {
     std::vector<double> texels;  // 6n rows x n columns x 3
     uint32_t face_size = 0;
     uint32_t filter = CRT_ENV_BILINEAR;
     Vec3D right{1, 0, 0}, up{0, 1, 0}, forward{0, 0, -1};
+    bool importance = false;
 
     static Environment from_cube(const Image& frame, const Vec3D& forward = Vec3D{0, 0, -1},
-                                 const Vec3D& up = Vec3D{0, 1, 0}, uint32_t filter = CRT_ENV_BILINEAR) {
+                                 const Vec3D& up = Vec3D{0, 1, 0}, uint32_t filter = CRT_ENV_BILINEAR,
+                                 bool importance = false) {
         Environment e;
         e.face_size = static_cast<uint32_t>(frame.width());
         e.filter = filter;
+        e.importance = importance;
         e.forward = forward.unit_vector();
         e.right = cross(e.forward, up).unit_vector();
         e.up = cross(e.right, e.forward);
@@ -425,7 +431,11 @@ class Camera {
         std::vector<double> rgb(image_w * image_h * 3);
         if (env) {
             const crt_env e = env->as_crt();
-            if (crt_render_lens_env(g.get(), 0, &resolved, &l, &e, rgb.data())) crt_api::die("crt_render_lens_env");
+            if (env->importance) {
+                if (crt_render_lens_env_sampled(g.get(), 0, &resolved, &l, &e, rgb.data())) crt_api::die("crt_render_lens_env_sampled");
+            } else if (crt_render_lens_env(g.get(), 0, &resolved, &l, &e, rgb.data())) {
+                crt_api::die("crt_render_lens_env");
+            }
         } else if (crt_render_lens(g.get(), 0, &resolved, &l, rgb.data())) {
             crt_api::die("crt_render_lens");
         }
@@ -652,8 +662,9 @@ public:
             return render_scene_lens(s, lens);
         }
     }
-    // Extension (not in the reference): render_lens lit by a cube-map environment (crt_render_lens_env):
-    // paths that leave the scene see env in place of the constant background.
+    // Extension (not in the reference): render_lens lit by a cube-map environment (crt_render_lens_env, or
+    // crt_render_lens_env_sampled for an Environment with importance): paths that leave the scene see
+    // env in place of the constant background.
     Image render_lens(const BVH& world, const Lens& lens, const Environment& env) {
         return render_scene_lens(world.gpu_scene(), lens, &env);
     }

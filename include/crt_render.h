@@ -868,6 +868,89 @@ int crt_render_lens_env_async(const crt_scene* scene, int device, const crt_came
 int crt_render_lens_env(crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens,
                         const crt_env* env, double* rgb);
 
+/* ---- environments sampled by luminance: next-event estimation with MIS ----------------------
+ * As above, a path finds the environment only by bouncing into it. A crt_env_sampler draws
+ * directions from a distribution built on the map's luminance, and the *_env_sampled entries send a
+ * shadow ray that way at every Lambertian bounce and combine it with the escape the scatter produces
+ * by the balance heuristic. An addition to the ABI (no existing call changes, CRT_ABI_VERSION stays).
+ * Tables are doubles; every operation below is an IEEE f64 + - * /, a sqrt, a comparison or a
+ * floor; nothing is fused.
+ *
+ * crt_env_sampler_create blocks. It records *env (device texels, n = face_size, filter, basis; the
+ * texels must stay valid and unchanged for the sampler's life) and builds on `device`, with rows
+ * r = face * n + row_in_face, the map's own layout:
+ *   Y = (0.2126 * r + 0.7152 * g) + 0.0722 * b, then Y = Y > 0 ? Y : 0 (NaN and negatives give 0);
+ *   uc = ((double)col + 0.5) * (2.0 / (double)n) - 1.0, vc likewise from row_in_face,
+ *   sc = (1.0 + uc * uc) + vc * vc,  w[r][col] = Y / (sc * sqrt(sc))   (luminance times the texel's
+ *     solid angle up to the constant 4 / n^2);
+ *   c[r][0] = 0.0 + w[r][0],  c[r][k] = c[r][k - 1] + w[r][k];
+ *   m[0] = 0.0 + c[0][n - 1],  m[r] = m[r - 1] + c[r][n - 1],  W = m[6n - 1].
+ * The sums are sequential in that order. CRT_E_INVALID (the message names the rule): env or out
+ * NULL; crt_env's rules (above); face_size above 2048; a basis whose Gram matrix (the nine dot
+ * products of right, up, forward, each (a0 b0 + a1 b1) + a2 b2) differs from the identity by more
+ * than 1e-9 in any entry (the densities below are solid-angle densities only for an orthonormal
+ * basis); these are checked before any device work; then !(W > 0 && W < inf), read back after the
+ * build (an all-black, NaN or overflowing map).
+ * crt_env_sampler_view gives the recorded crt_env, the device pointers of w (6n x n), c (6n x n)
+ * and m (6n) and W. crt_env_sampler_free(NULL) is CRT_OK.
+ *
+ * env_pdf(d), the solid-angle density of d: steps 1 to 5 of E(d). If d has no major axis (step 2),
+ *   env_pdf = 0. Else col, row as in step 6, whatever the filter; s = (1.0 + u * u) + v * v,
+ *   hh = h * h,  env_pdf = ((w[face * n + row][col] / W) * hh) * (s * sqrt(s)).
+ * env_sample(xi1, xi2, xi3, xi4): r = the number of rows with m[r] <= xi1 * W, clamped to 6n - 1;
+ *   k = the number of columns with c[r][k] <= xi2 * c[r][n - 1], clamped to n - 1; face = r / n,
+ *   row_in_face = r % n; fx = (double)k + xi3, fy = (double)row_in_face + xi4,
+ *   u = fx * (2.0 / (double)n) - 1.0, v likewise from fy; (x, y, z) from crt_lens_rays_async's CUBE
+ *   table; d_s = (R * x + U * y) + F * z per component.
+ *
+ * The estimator is crt_radiance_env_async's integrator with these additions. A path carries acc,
+ * +0 per channel at its start, and pb, the previous bounce's solid-angle density: "none" at the
+ * start and after a Metal or Dielectric bounce. pi is the double 3.141592653589793; dot products
+ * are (a0 b0 + a1 b1) + a2 b2.
+ *   Light hit: acc = acc + T * emit, the path ends.
+ *   Lambertian bounce, after the material's own draws, the throughput multiply and the depth
+ *   decrement, if depth left > 0: xi1..xi4 = crt_rand_double(state, 0, 1) in that order (always
+ *     drawn); d_s = env_sample(xi); c_s = (n . d_s) / sqrt(d_s . d_s), n the hit normal facing the
+ *     ray; pb_s = c_s / pi; pe_s = env_pdf(d_s). If c_s > 0 && pe_s > 0, the segment from the hit
+ *     point along d_s over (t_min, +inf) is traced, and any hit means occluded; if it is free,
+ *     f = pb_s / (pe_s + pb_s), e = E(d_s), acc = acc + (T * e) * f per channel. Then
+ *     pb = ((n . nd) / sqrt(nd . nd)) / pi for the scattered direction nd (the nd = n fallback
+ *     included).
+ *   Metal or Dielectric bounce: pb = none.
+ *   Escape along d: e = E(d); f = 1.0 if pb is none, else pe = env_pdf(d) and
+ *     f = (pe + pb) > 0 ? pb / (pe + pb) : 0.0; acc = acc + (T * e) * f per channel, the path ends.
+ *   The output is acc: absorbed paths and paths out of depth write what they gathered.
+ * A path with no Lambertian bounce, and every path with max_depth == 1, gets
+ * crt_radiance_env_async's bytes. Rays the query contract refuses stay first-segment misses with
+ * f = 1. Neither the grid nor the route (CRT_RADIANCE_PLAIN) changes a bit.
+ *
+ * The *_env_sampled entries are the *_env entries with the sampler in place of the environment, whose
+ * recorded copy is used: same buffers, same rules. CRT_E_INVALID in addition, before any device
+ * work: sampler NULL; a sampler built on another device. max_depth == 0 is still a memset. The
+ * probes' and the lens frames' first segments have pb = none. */
+typedef struct crt_env_sampler crt_env_sampler;
+struct crt_env_sampler_view {      /* the entry below has the same name: no typedef, say `struct` */
+    crt_env env;                    /* as recorded by create */
+    const double *w, *c, *m;        /* DEVICE: 6n x n, 6n x n, 6n doubles */
+    double W;
+};                                  /* 120 bytes */
+int crt_env_sampler_create(int device, const crt_env* env, crt_env_sampler** out);
+int crt_env_sampler_free(crt_env_sampler* sampler);
+int crt_env_sampler_view(const crt_env_sampler* sampler, struct crt_env_sampler_view* out);
+int crt_radiance_env_sampled_async(const crt_scene* scene, int device, const double* d_rays, size_t n,
+                                   const uint32_t* d_states, const crt_radiance_params* params,
+                                   const crt_env_sampler* sampler, double* d_rgb, void* stream);
+int crt_probes_env_sampled_async(const crt_scene* scene, int device, const double* d_points,
+                                 const double* d_normals, size_t n, const crt_probe_params* params,
+                                 const crt_env_sampler* sampler, double* d_coeff, void* stream);
+int crt_render_lens_env_sampled_async(const crt_scene* scene, int device, const crt_camera* cam,
+                                      const crt_lens* lens, const crt_env_sampler* sampler, double* d_rgb,
+                                      void* stream);
+/* crt_render_lens_env with luminance sampling: env->texels is HOST memory; the call uploads it,
+ * builds a sampler, renders, and frees both. crt_env_sampler_create's rules hold. */
+int crt_render_lens_env_sampled(crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens,
+                                const crt_env* env, double* rgb);
+
 /* ---- lens renders in passes ------------------------------------------------------------------
  * A lens render cut into passes, with the state the camera-agnostic calls read: crt_noise_estimate,
  * crt_adaptive_update, crt_pixel_variance_async and crt_denoise_async take d_sum, d_noise, block
