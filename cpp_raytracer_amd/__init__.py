@@ -22,7 +22,7 @@ from ._capi import (CRT_BOX, CRT_DIELECTRIC, CRT_DIFFUSE_LIGHT, CRT_LAMBERTIAN, 
                     DenoiseParams, RenderStats, SceneInfo, Tiling, TraceParams, CRT_TRACE_ANY, CRT_TRACE_PLAIN,
                     RadianceParams, CRT_RADIANCE_PLAIN, ProbeParams, CRT_PROBE_SPHERE, CRT_PROBE_HEMISPHERE,
                     CRT_SH_RADIANCE, CRT_SH_IRRADIANCE, Lens, CRT_LENS_PINHOLE, CRT_LENS_ORTHOGRAPHIC,
-                    CRT_LENS_EQUIRECT, CRT_LENS_FISHEYE, CRT_LENS_CUBE, EnvView, EnvSamplerView, CRT_ENV_NEAREST, CRT_ENV_BILINEAR,
+                    CRT_LENS_EQUIRECT, CRT_LENS_FISHEYE, CRT_LENS_CUBE, EnvView, EnvSamplerView, LightSamplerView, CRT_ENV_NEAREST, CRT_ENV_BILINEAR,
                     check, lib)
 
 __all__ = [
@@ -36,6 +36,7 @@ __all__ = [
     "Lens", "make_lens", "CRT_LENS_PINHOLE", "CRT_LENS_ORTHOGRAPHIC", "CRT_LENS_EQUIRECT", "CRT_LENS_FISHEYE",
     "CRT_LENS_CUBE", "LensRender",
     "Env", "EnvView", "EnvSamplerView", "EnvTables", "make_env", "CRT_ENV_NEAREST", "CRT_ENV_BILINEAR",
+    "LightSampler", "LightSamplerView", "LightTables",
     "CRT_LAMBERTIAN", "CRT_METAL", "CRT_DIELECTRIC", "CRT_DIFFUSE_LIGHT",
     "CRT_SPHERE", "CRT_PARALLELOGRAM", "CRT_BOX",
 ]
@@ -198,8 +199,8 @@ _ENV_FILTERS = {"nearest": CRT_ENV_NEAREST, "bilinear": CRT_ENV_BILINEAR}
 class _DevicePtr:
     """A device allocation of `count` doubles as torch.as_tensor reads it."""
 
-    def __init__(self, ptr: int, shape):
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f8", "data": (ptr, False), "version": 2}
+    def __init__(self, ptr: int, shape, typestr: str = "<f8"):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (ptr, False), "version": 2}
 
 
 class EnvTables:
@@ -245,6 +246,54 @@ class Env:
         h, self.sampler = getattr(self, "sampler", None), None
         if h is not None and _capi._lib is not None:
             _capi._lib.crt_env_sampler_free(C.c_void_p(h))
+
+
+class LightTables:
+    """A light sampler's tables (crt_light_sampler_view), copied to the host: prim (L,) uint32, the
+    lights' flattened primitive indices in pick order, w and cdf (L,) float64, and the total W."""
+
+    def __init__(self, prim, w, cdf, W: float):
+        self.prim, self.w, self.cdf, self.W = prim, w, cdf, W
+
+
+class LightSampler:
+    """A sampler of a scene's own lights on one device (GpuScene.light_sampler): it owns the
+    crt_light_sampler handle, freed with it, and keeps the scene alive. radiance, probes and
+    render_lens take it as lights=: next-event estimation of the DiffuseLight primitives with MIS."""
+
+    def __init__(self, scene, device: int, handle: int):
+        self.scene, self.device, self.handle = scene, device, handle
+
+    @property
+    def tables(self) -> LightTables:
+        import torch
+        v = LightSamplerView()
+        check(lib().crt_light_sampler_view(C.c_void_p(self.handle), C.byref(v)), "crt_light_sampler_view")
+        L, dev = int(v.num_lights), torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            torch.cuda.synchronize(dev)
+            w, cdf = (torch.as_tensor(_DevicePtr(p, (L,)), device=dev).cpu().numpy().copy() for p in (v.w, v.cdf))
+            # uint32 through int32: the bits are the indices' (below 2^31)
+            prim = torch.as_tensor(_DevicePtr(v.prim, (L,), "<i4"), device=dev).cpu().numpy().astype(np.uint32)
+        return LightTables(prim, w, cdf, float(v.W))
+
+    def __del__(self):
+        h, self.handle = getattr(self, "handle", None), None
+        if h is not None and _capi is not None and _capi._lib is not None:  # _capi is gone at interpreter exit
+            _capi._lib.crt_light_sampler_free(C.c_void_p(h))
+
+
+def _lights_on(who: str, lights, env, scene, device: int) -> int:
+    """The handle of lights= for a call of `scene` on `device` (0 without one), after the front end's rules."""
+    if lights is None:
+        return 0
+    if env is not None:
+        raise ValueError(f"{who}: lights= and env= cannot be combined")
+    if not isinstance(lights, LightSampler):
+        raise CrtError(f"{who}: lights must be a LightSampler (GpuScene.light_sampler)")
+    if lights.scene is not scene or lights.device != device:
+        raise CrtError(f"{who}: the LightSampler belongs to another scene or device (it is on device {lights.device})")
+    return lights.handle
 
 
 def _env_texels_ok(t) -> bool:
@@ -474,6 +523,14 @@ class GpuScene:
 
     def upload(self, device: int = 0) -> None:
         check(lib().crt_scene_upload(self._h, device), f"crt_scene_upload(device={device})")
+
+    def light_sampler(self, device: int = 0) -> LightSampler:
+        """A sampler of the scene's DiffuseLight primitives on `device` (crt_light_sampler_create; it
+        uploads the scene there if needed and blocks). CrtError for a scene without a light."""
+        self.upload(device)
+        h = C.c_void_p()
+        check(lib().crt_light_sampler_create(self._h, device, C.byref(h)), "crt_light_sampler_create")
+        return LightSampler(self, device, h.value)
 
     def device_image(self, device: int = 0) -> np.ndarray:
         """The bytes of the scene's copy in HBM of `device` (crt_scene_image)."""
@@ -722,7 +779,7 @@ class GpuScene:
 
     def radiance_async(self, device: int, rays_ptr: int, n: int, out_ptr: int, states_ptr: int = 0, *,
                        max_depth: int, background, t_min: float = 1e-5, base_seed: int = 0, flags: int = 0,
-                       stream: int = 0, env: Optional[EnvView] = None, sampler: int = 0) -> None:
+                       stream: int = 0, env: Optional[EnvView] = None, sampler: int = 0, lights: int = 0) -> None:
         """Enqueue a radiance query on device buffers (crt_radiance_async): n rays of 6 doubles at
         rays_ptr, each the first segment of one path of ray_color with `max_depth` bounces over
         (t_min, inf). Path i's LCG state is the uint32 states_ptr[i], or sample_seed(base_seed, i, 0)
@@ -730,9 +787,17 @@ class GpuScene:
         sum in a render. CRT_RADIANCE_PLAIN takes one thread a path: the same bits. The scene must be
         uploaded to `device`. env: an EnvView (crt_env) whose texels are on `device`: paths that end in
         a miss see it in place of `background` (crt_radiance_env_async). sampler: a crt_env_sampler
-        handle built on `device` (Env.sampler) in place of env (crt_radiance_env_sampled_async)."""
+        handle built on `device` (Env.sampler) in place of env (crt_radiance_env_sampled_async). lights: a
+        crt_light_sampler handle of this scene on `device` (LightSampler.handle), without env or sampler
+        (crt_radiance_lights_async)."""
         prm = RadianceParams(max_depth, base_seed & 0xFFFFFFFF, _capi.D3(*[float(v) for v in background]), t_min,
                              flags, 0)
+        if lights:
+            check(lib().crt_radiance_lights_async(self._h, device, C.c_void_p(rays_ptr or None), n,
+                                                  C.c_void_p(states_ptr or None), C.byref(prm), C.c_void_p(lights),
+                                                  C.c_void_p(out_ptr or None), C.c_void_p(stream)),
+                  "crt_radiance_lights_async")
+            return
         if sampler:
             check(lib().crt_radiance_env_sampled_async(self._h, device, C.c_void_p(rays_ptr or None), n,
                                                        C.c_void_p(states_ptr or None), C.byref(prm), C.c_void_p(sampler),
@@ -750,13 +815,15 @@ class GpuScene:
               "crt_radiance_async")
 
     def radiance(self, rays, states=None, max_depth: int = 50, background=(0.7, 0.8, 1.0), t_min: float = 1e-5,
-                 base_seed: int = 0, plain: bool = False, env: Optional[Env] = None):
+                 base_seed: int = 0, plain: bool = False, env: Optional[Env] = None,
+                 lights: Optional[LightSampler] = None):
         """Path-traced radiance of the caller's rays on torch tensors of a GPU: rays (n, 6) float64,
         states None or an (n,) int32 tensor on the rays' device whose bits are the paths' LCG states
         (None: sample_seed(base_seed, i, 0)). Runs on the rays' device and its current stream and
         does not synchronise; the scene is uploaded there first if it is not yet (that blocks).
         Returns an (n, 3) float64 tensor. env (make_env, on the rays' device): the environment that
-        paths leaving the scene see in place of `background`."""
+        paths leaving the scene see in place of `background`. lights (light_sampler, of the
+        rays' device; not with env): every Lambertian bounce also samples the scene's lights (MIS)."""
         import torch
         if env is not None and not isinstance(env, Env):
             raise CrtError("radiance: env must be an Env (make_env)")
@@ -764,6 +831,7 @@ class GpuScene:
             raise CrtError("radiance: rays must be an (n, 6) float64 tensor on a GPU")
         rays = rays.contiguous()
         n, device = rays.shape[0], rays.device.index
+        lh = _lights_on("radiance", lights, env, self, device)
         view = _env_on("radiance", env, device) if env is not None else None
         if states is not None:
             if not (states.is_cuda and states.device == rays.device and states.dtype == torch.int32 and
@@ -779,7 +847,7 @@ class GpuScene:
                                     background=background, t_min=t_min, base_seed=base_seed,
                                     flags=CRT_RADIANCE_PLAIN if plain else 0,
                                     stream=torch.cuda.current_stream(device).cuda_stream, env=view,
-                                    sampler=(env.sampler or 0) if env is not None else 0)
+                                    sampler=(env.sampler or 0) if env is not None else 0, lights=lh)
             return out
 
     @staticmethod
@@ -794,7 +862,7 @@ class GpuScene:
     def probes_async(self, device: int, points_ptr: int, normals_ptr: int, n: int, out_ptr: int, *, samples: int,
                      mode=CRT_PROBE_SPHERE, max_depth: int, background, t_min: float = 1e-5, base_seed: int = 0,
                      batch_probes: int = 0, flags: int = 0, stream: int = 0, env: Optional[EnvView] = None,
-                     sampler: int = 0) -> None:
+                     sampler: int = 0, lights: int = 0) -> None:
         """Enqueue a probe bake on device buffers (crt_probes_async): n points of 3 doubles at
         points_ptr, with CRT_PROBE_HEMISPHERE their unit normals at normals_ptr (0 with
         CRT_PROBE_SPHERE). `samples` directions a probe are drawn on the device, path-traced as
@@ -802,8 +870,13 @@ class GpuScene:
         bands 0..2 per channel) or n x 1 x 3 (irradiance) go to out_ptr. batch_probes sizes the
         internal batches only; flags may hold CRT_RADIANCE_PLAIN: the same bits either way. The scene
         must be uploaded to `device`. env, sampler: as radiance_async's (crt_probes_env_async,
-        crt_probes_env_sampled_async)."""
+        crt_probes_env_sampled_async). lights: as radiance_async's (crt_probes_lights_async)."""
         prm = self._probe_params(samples, mode, max_depth, background, t_min, base_seed, batch_probes, flags)
+        if lights:
+            check(lib().crt_probes_lights_async(self._h, device, C.c_void_p(points_ptr or None),
+                                                C.c_void_p(normals_ptr or None), n, C.byref(prm), C.c_void_p(lights),
+                                                C.c_void_p(out_ptr or None), C.c_void_p(stream)), "crt_probes_lights_async")
+            return
         if sampler:
             check(lib().crt_probes_env_sampled_async(self._h, device, C.c_void_p(points_ptr or None),
                                                      C.c_void_p(normals_ptr or None), n, C.byref(prm),
@@ -836,18 +909,19 @@ class GpuScene:
 
     def probes(self, points, normals=None, samples: int = 1024, mode: str = "sphere", max_depth: int = 50,
                background=(0.7, 0.8, 1.0), t_min: float = 1e-5, base_seed: int = 0, batch_probes: int = 0,
-               plain: bool = False, env: Optional[Env] = None):
+               plain: bool = False, env: Optional[Env] = None, lights: Optional[LightSampler] = None):
         """Probe bake on torch tensors of a GPU: points (n, 3) float64; with mode="hemisphere", normals
         (n, 3) float64 unit vectors on the points' device (None with mode="sphere"). Runs on the
         points' device and its current stream and does not synchronise; the scene is uploaded there
         first if it is not yet (that blocks). Returns an (n, 9, 3) float64 tensor of SH coefficients
         (sphere; sh_eval evaluates them) or (n, 1, 3) of irradiance (hemisphere). env (make_env, on the
-        points' device): the environment in place of `background`, as in radiance."""
+        points' device): the environment in place of `background`, as in radiance. lights: as in radiance."""
         import torch
         if env is not None and not isinstance(env, Env):
             raise CrtError("probes: env must be an Env (make_env)")
         points, normals = self._probe_inputs("probes", points, normals, mode)
         n, device = points.shape[0], points.device.index
+        lh = _lights_on("probes", lights, env, self, device)
         view = _env_on("probes", env, device) if env is not None else None
         with torch.cuda.device(device):
             out = torch.empty((n, 9 if mode == "sphere" else 1, 3), dtype=torch.float64, device=points.device)
@@ -858,7 +932,7 @@ class GpuScene:
                                   t_min=t_min, base_seed=base_seed, batch_probes=batch_probes,
                                   flags=CRT_RADIANCE_PLAIN if plain else 0,
                                   stream=torch.cuda.current_stream(device).cuda_stream, env=view,
-                                  sampler=(env.sampler or 0) if env is not None else 0)
+                                  sampler=(env.sampler or 0) if env is not None else 0, lights=lh)
             return out
 
     def probe_rays(self, points, normals=None, samples: int = 1024, mode: str = "sphere", base_seed: int = 0):
@@ -951,12 +1025,17 @@ class GpuScene:
             return rays, states
 
     def render_lens_async(self, device: int, cam: Camera, lens: Lens, out_ptr: int, stream: int = 0,
-                          env: Optional[EnvView] = None, sampler: int = 0) -> None:
+                          env: Optional[EnvView] = None, sampler: int = 0, lights: int = 0) -> None:
         """Enqueue a whole-frame render through `lens` (crt_render_lens_async) into the device buffer
         at out_ptr (image_h * image_w * 3 doubles): the rays of lens_rays, traced as radiance_async
         traces them and summed per pixel in render_async's order. The scene must be uploaded to
         `device`. env, sampler: as radiance_async's (crt_render_lens_env_async,
-        crt_render_lens_env_sampled_async)."""
+        crt_render_lens_env_sampled_async). lights: as radiance_async's (crt_render_lens_lights_async)."""
+        if lights:
+            check(lib().crt_render_lens_lights_async(self._h, device, C.byref(cam), C.byref(lens), C.c_void_p(lights),
+                                                     C.c_void_p(out_ptr or None), C.c_void_p(stream)),
+                  "crt_render_lens_lights_async")
+            return
         if sampler:
             check(lib().crt_render_lens_env_sampled_async(self._h, device, C.byref(cam), C.byref(lens),
                                                           C.c_void_p(sampler), C.c_void_p(out_ptr or None),
@@ -970,21 +1049,23 @@ class GpuScene:
         check(lib().crt_render_lens_async(self._h, device, C.byref(cam), C.byref(lens), C.c_void_p(out_ptr or None),
                                           C.c_void_p(stream)), "crt_render_lens_async")
 
-    def render_lens(self, cam: Camera, lens: Lens, device: int = 0, env: Optional[Env] = None):
+    def render_lens(self, cam: Camera, lens: Lens, device: int = 0, env: Optional[Env] = None,
+                    lights: Optional[LightSampler] = None):
         """Whole-frame render through `lens` (make_lens) into an (h, w, 3) float64 torch tensor on
         `device`. Runs on that device's current stream and does not synchronise; the scene is uploaded
         there first if it is not yet (that blocks). With kind "pinhole" the frame is render_async's,
         bit for bit. env (make_env, on `device`): the environment in place of cam.background, as in
-        radiance."""
+        radiance. lights: as in radiance."""
         import torch
         if not isinstance(cam, Camera) or not isinstance(lens, Lens):
             raise CrtError("render_lens: cam must be a resolved Camera (resolve_camera) and lens a Lens (make_lens)")
+        lh = _lights_on("render_lens", lights, env, self, device)
         view = _env_on("render_lens", env, device) if env is not None else None
         with torch.cuda.device(device):
             out = torch.empty((cam.image_h, cam.image_w, 3), dtype=torch.float64, device=torch.device("cuda", device))
             self.upload(device)
             self.render_lens_async(device, cam, lens, out.data_ptr(), torch.cuda.current_stream(device).cuda_stream,
-                                   env=view, sampler=(env.sampler or 0) if env is not None else 0)
+                                   env=view, sampler=(env.sampler or 0) if env is not None else 0, lights=lh)
             return out
 
     def render_lens_pass(self, device: int, cam: Camera, lens: Lens, first: int, count: int, sum_ptr: int,

@@ -155,6 +155,16 @@ class EnvSamplerView(C.Structure):
 assert C.sizeof(EnvSamplerView) == 120
 
 
+class LightSamplerView(C.Structure):
+    """struct crt_light_sampler_view: L, the device pointers of the tables and W."""
+    _fields_ = [("num_lights", C.c_uint32), ("device", C.c_int32), ("prim", C.c_void_p), ("ref", C.c_void_p),
+                ("sorted_ref", C.c_void_p), ("w", C.c_void_p), ("cdf", C.c_void_p), ("sorted_w", C.c_void_p),
+                ("W", C.c_double)]
+
+
+assert C.sizeof(LightSamplerView) == 64
+
+
 class LaunchPlan(C.Structure):
     _fields_ = ([(n, C.c_uint32) for n in ("kernel", "klass", "entry_bytes", "five_waves", "prim_mode", "plain_route",
                                            "depth", "block")] + [("num_nodes", C.c_uint64)] +
@@ -283,6 +293,16 @@ EXPORTS = {
     "crt_render_lens_env_sampled_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), C.c_void_p, C.c_void_p,
                                                     C.c_void_p]),
     "crt_render_lens_env_sampled": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), P(EnvView), C.c_void_p]),
+    "crt_light_sampler_create": (C.c_int, [C.c_void_p, C.c_int, P(C.c_void_p)]),
+    "crt_light_sampler_free": (C.c_int, [C.c_void_p]),
+    "crt_light_sampler_view": (C.c_int, [C.c_void_p, P(LightSamplerView)]),
+    "crt_radiance_lights_async": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                            P(RadianceParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "crt_probes_lights_async": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                          P(ProbeParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "crt_render_lens_lights_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
+    "crt_render_lens_lights": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), C.c_void_p]),
     "crt_render_lens_pass_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), C.c_uint32, C.c_uint32,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "crt_lens_centre_rays_async": (C.c_int, [C.c_int, P(Camera), P(Lens), C.c_void_p, C.c_void_p]),

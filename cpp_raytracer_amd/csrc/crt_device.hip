@@ -31,6 +31,7 @@
 #include "crt_schlick.h"
 #include "crt_env.h"
 #include "crt_env_sampler.h"
+#include "crt_light_sampler.h"
 
 #pragma clang fp contract(off)
 
@@ -1967,7 +1968,10 @@ struct ShadeOut {
     uint32_t kind;
 };
 
-template <bool LS, bool SPH = false, bool QONLY = false, bool FAST = false, bool NEE = false>
+// NEE == 2 (the lights instances, light_segment): a light hit adds nothing here; ex->kind tells the
+// caller, which weights the emission itself (it needs the light's true normal: for an emitting
+// sphere slot M.emit[0] is the emission, not 1 / r, so n below is not that normal).
+template <bool LS, bool SPH = false, bool QONLY = false, bool FAST = false, int NEE = 0>
 __device__ __forceinline__ bool shade(const SceneView& S, const CamView& C, Path& P, bool hit,
                                       uint32_t ref, double t, double acc[3], ShadeOut* ex = nullptr) {
     if (!hit) {
@@ -1984,6 +1988,10 @@ __device__ __forceinline__ bool shade(const SceneView& S, const CamView& C, Path
     const uint32_t kind = M.kind;
     const bool lam = kind == CRT_LAMBERTIAN, met = kind == CRT_METAL, die = kind == CRT_DIELECTRIC;
     if (!(lam || met || die)) {  // DiffuseLight: emits, never scatters (material.h:248-263)
+        if constexpr (NEE == 2) {
+            ex->kind = kind;
+            return true;
+        }
         acc[0] = acc[0] + P.T[0] * M.emit[0];
         acc[1] = acc[1] + P.T[1] * M.emit[1];
         acc[2] = acc[2] + P.T[2] * M.emit[2];
@@ -2056,7 +2064,7 @@ __device__ __forceinline__ bool shade(const SceneView& S, const CamView& C, Path
     P.o[0] = p[0]; P.o[1] = p[1]; P.o[2] = p[2];
     P.d[0] = nd[0]; P.d[1] = nd[1]; P.d[2] = nd[2];
     P.depth -= 1;
-    if constexpr (NEE) {
+    if constexpr (NEE != 0) {
         ex->n[0] = n[0]; ex->n[1] = n[1]; ex->n[2] = n[2];
         ex->kind = kind;
     }
@@ -3189,8 +3197,14 @@ struct RadianceEnv : Radiance {
 struct RadianceNee : RadianceEnv {
     EnvTables tb;
 };
-template <bool ENV, bool NEE = false>
-using RadianceOf = std::conditional_t<NEE, RadianceNee, std::conditional_t<ENV, RadianceEnv, Radiance>>;
+// The lights instances' launch (crt_radiance_lights_async): the light sampler's tables, in the
+// kernel arguments as well (no LDS: scene_layout decides as without a sampler).
+struct RadianceLights : Radiance {
+    LightTables tb;
+};
+template <bool ENV, bool NEE = false, bool LGT = false>
+using RadianceOf = std::conditional_t<LGT, RadianceLights,
+                                      std::conditional_t<NEE, RadianceNee, std::conditional_t<ENV, RadianceEnv, Radiance>>>;
 
 // A path that ends in a miss under an environment: 0 + T * E(P.d) (crt_env.h) where shade's miss
 // branch gives 0 + T * bg
@@ -3281,6 +3295,139 @@ __device__ __forceinline__ bool nee_segment(const SceneView& S, const CamView& C
     return false;
 }
 
+// What a path of the lights instances carries besides its Path (include/crt_render.h, the lights
+// estimator): Nee's fields with the sample's cosine in place of its weight, and the sampled light's
+// slot reference.
+struct LNee {
+    double acc[3];
+    double pb;
+    double nd[3];
+    double cs;
+    uint32_t lref;
+    bool has_pb;
+    bool shadow;
+};
+
+__device__ __forceinline__ void nee_start(LNee& N) {
+    N.acc[0] = 0; N.acc[1] = 0; N.acc[2] = 0;
+    N.has_pb = false;
+    N.shadow = false;
+}
+
+template <bool SPH>
+__device__ __forceinline__ const DevMaterial& slot_material(const SceneView& S, uint32_t ref) {
+    return (!SPH && (ref & kRefQuad)) ? S.quad_mrec[ref & ~kRefQuad] : S.sphere_mrec[ref];
+}
+
+// light_pdf of the hit at t of the ray (o, d) on the light in slot ref, a shadow ray's and a bounce
+// ray's alike: the hit's own record (the true normal, IR off), the slot's area, its w by search
+template <bool LS, bool SPH>
+__device__ __forceinline__ double light_hit_pdf(const SceneView& S, const LightTables& Tb, uint32_t ref, const double o[3],
+                                                const double d[3], double t) {
+    double p[3], n[3];
+    bool front;
+    (void)hit_record<LS, false, SPH>(S, ref, o, d, t, p, n, front);
+    double A;
+    bool outside = true;
+    if (!SPH && (ref & kRefQuad)) {
+        const uint32_t i = ref & ~kRefQuad;
+        if constexpr (LS) {
+            const DevQuad q = lds_rec<DevQuad>(S.quads_lds + (i << 7));
+            A = light_area_quad(q.s1, q.s2);
+        } else {
+            A = light_area_quad(S.quads[i].s1, S.quads[i].s2);
+        }
+    } else {
+        const double r = sphere_at<LS>(S, ref).r;
+        A = light_area_sphere(r);
+        outside = front == (r > 0);
+    }
+    return light_pdf(light_weight(Tb, ref), Tb.W, A, t, n, d, outside);
+}
+
+__device__ __forceinline__ void light_add(const DevMaterial& M, const Path& P, double f, double acc[3]) {
+    acc[0] = acc[0] + (P.T[0] * M.emit[0]) * f;
+    acc[1] = acc[1] + (P.T[1] * M.emit[1]) * f;
+    acc[2] = acc[2] + (P.T[2] * M.emit[2]) * f;
+}
+
+// nee_segment with the scene's lights in place of the map: one finished segment of a path of the
+// lights instances. A shadow segment is an ordinary closest-hit segment towards the sampled point;
+// it counts only when what it found is the sampled light's own slot.
+template <bool LS, bool SPH>
+__device__ __forceinline__ bool light_segment(const SceneView& S, const CamView& C, const RadianceLights& Q, Path& P,
+                                              LNee& N, bool found, uint32_t ref, double tmax) {
+    constexpr double kPi = 3.141592653589793;
+    if (N.shadow) {
+        if (found && ref == N.lref) {
+            const double pl = light_hit_pdf<LS, SPH>(S, Q.tb, ref, P.o, P.d, tmax);
+            if (pl > 0 && pl < __builtin_inf()) {
+                const double pbs = N.cs / kPi;
+                light_add(slot_material<SPH>(S, ref), P, pbs / (pl + pbs), N.acc);
+            }
+        }
+        P.d[0] = N.nd[0]; P.d[1] = N.nd[1]; P.d[2] = N.nd[2];
+        N.shadow = false;
+        return false;
+    }
+    if (!found) {  // nothing samples the background: no weight
+        N.acc[0] = N.acc[0] + P.T[0] * C.bg[0];
+        N.acc[1] = N.acc[1] + P.T[1] * C.bg[1];
+        N.acc[2] = N.acc[2] + P.T[2] * C.bg[2];
+        return true;
+    }
+    ShadeOut X;
+    X.kind = 0;
+    if (shade<LS, SPH, false, false, 2>(S, C, P, true, ref, tmax, N.acc, &X)) {
+        if (X.kind == CRT_DIFFUSE_LIGHT) {  // weighted against the sampler unless pb is none
+            double f = 1.0;
+            if (N.has_pb) {
+                const double sum = light_hit_pdf<LS, SPH>(S, Q.tb, ref, P.o, P.d, tmax) + N.pb;
+                f = sum > 0 ? N.pb / sum : 0.0;
+            }
+            light_add(slot_material<SPH>(S, ref), P, f, N.acc);
+        }
+        return true;  // a light, or absorbed
+    }
+    if (P.depth == 0) return true;
+    if (X.kind != CRT_LAMBERTIAN) {
+        N.has_pb = false;
+        return false;
+    }
+    const double xi1 = rnd_01(P.rng);
+    const uint32_t lref = Q.tb.ref[light_pick(Q.tb, xi1)];
+    double pt[3], u[3] = {0, 0, 0};
+    const bool quad = !SPH && (lref & kRefQuad);
+    if (quad) {
+        const double xi2 = rnd_01(P.rng);
+        const double xi3 = rnd_01(P.rng);
+        const uint32_t i = lref & ~kRefQuad;
+        if constexpr (LS) {
+            const DevQuad q = lds_rec<DevQuad>(S.quads_lds + (i << 7));
+            light_point(q.v, q.s1, q.s2, xi2, xi3, pt);
+        } else {
+            light_point(S.quads[i].v, S.quads[i].s1, S.quads[i].s2, xi2, xi3, pt);
+        }
+    } else {
+        random_unit_vector<false>(P.rng, u[0], u[1], u[2]);
+        const DevSphere sp = sphere_at<LS>(S, lref);
+        light_point(sp.c, sp.r, u, pt);
+    }
+    const double ds[3] = {pt[0] - P.o[0], pt[1] - P.o[1], pt[2] - P.o[2]};
+    const double cs = dot3(X.n, ds) / sqrt(dot3(ds, ds));
+    N.pb = (dot3(X.n, P.d) / sqrt(dot3(P.d, P.d))) / kPi;
+    N.has_pb = true;
+    // a point on a sphere's far side is hidden by its near side: no ray
+    if (cs > 0 && (quad || dot3(u, ds) < 0)) {
+        N.nd[0] = P.d[0]; N.nd[1] = P.d[1]; N.nd[2] = P.d[2];
+        P.d[0] = ds[0]; P.d[1] = ds[1]; P.d[2] = ds[2];
+        N.cs = cs;
+        N.lref = lref;
+        N.shadow = true;
+    }
+    return false;
+}
+
 // path `ray` of a launch, before its first segment. False: the caller's ray is outside the query
 // contract (crt_ray_class.h) and must not be traced; shade's miss branch then gives 0 + 1 * bg.
 __device__ __forceinline__ bool load_path(const Radiance& Q, uint32_t ray, Path& P) {
@@ -3297,8 +3444,9 @@ __device__ __forceinline__ bool load_path(const Radiance& Q, uint32_t ray, Path&
 // [first, first + gridDim.x * kBlock) of the call. Scattered rays go to trace() as they are: it is
 // the reference's sequence for any ray. ENV: a miss ends the path with env_miss instead of shade.
 // NEE (on top of ENV): every finished segment goes through nee_segment, shadow segments included.
-template <bool ENV = false, bool NEE = false>
-__global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, CamView C, RadianceOf<ENV, NEE> Q, uint32_t first,
+// LGT (without ENV or NEE): the same through light_segment (crt_radiance_lights_async).
+template <bool ENV = false, bool NEE = false, bool LGT = false>
+__global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, CamView C, RadianceOf<ENV, NEE, LGT> Q, uint32_t first,
                                                                 uint32_t* __restrict__ gstack) {
     const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
     if (slot >= Q.n - first) return;
@@ -3310,14 +3458,17 @@ __global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, Cam
     bool traced = load_path(Q, i, P);
     LaneCounters ctr{};
     double acc[3] = {0, 0, 0};
-    [[maybe_unused]] Nee N;
-    if constexpr (NEE) nee_start(N);
+    [[maybe_unused]] std::conditional_t<LGT, LNee, Nee> N;
+    if constexpr (NEE || LGT) nee_start(N);
     while (true) {
         double tmax = __builtin_inf();
         uint32_t ref = 0;
         const bool found = traced && trace<uint32_t, false>(S, st, P.o, P.d, C.t_min, tmax, ref, ctr);
         traced = true;
-        if constexpr (NEE) {
+        if constexpr (LGT) {
+            if (light_segment<false, false>(S, C, Q, P, N, found, ref, tmax)) break;
+            continue;
+        } else if constexpr (NEE) {
             if (nee_segment<false, false>(S, C, Q, P, N, found, ref, tmax)) break;
             continue;
         } else if constexpr (ENV) {
@@ -3328,7 +3479,7 @@ __global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, Cam
         }
         if (shade<false>(S, C, P, found, ref, tmax, acc) || P.depth == 0) break;
     }
-    if constexpr (NEE) {
+    if constexpr (NEE || LGT) {
         acc[0] = N.acc[0]; acc[1] = N.acc[1]; acc[2] = N.acc[2];
     }
     double* dst = Q.rgb + 3 * static_cast<size_t>(i);
@@ -3351,9 +3502,11 @@ __global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, Cam
 // bounce may leave a shadow ray in P; it runs through the same ray_setup, walk_round and leaf_step
 // rounds as any segment (closest hit: only "any hit" enters), and nee_segment then puts the saved
 // scattered direction back. The lane's Nee stays in registers across all of it.
-template <typename SE, bool GSTACK, bool LSCENE, int PM, bool ENV = false, bool NEE = false>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NEE ? CRT_WAVES_PER_EU_NEE : LSCENE ? CRT_WAVES_PER_EU_LDS : CRT_WAVES_PER_EU, 8))) void radiance_kernel(
-    SceneView Sg, CamView C, Work W, RadianceOf<ENV, NEE> Q, SE* __restrict__ gstack) {
+// LGT (without ENV or NEE): the same with light_segment and its LNee (crt_radiance_lights_async); the
+// shadow ray ends on the sampled light or on what hides it, a closest hit either way.
+template <typename SE, bool GSTACK, bool LSCENE, int PM, bool ENV = false, bool NEE = false, bool LGT = false>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((NEE || LGT) ? CRT_WAVES_PER_EU_NEE : LSCENE ? CRT_WAVES_PER_EU_LDS : CRT_WAVES_PER_EU, 8))) void radiance_kernel(
+    SceneView Sg, CamView C, Work W, RadianceOf<ENV, NEE, LGT> Q, SE* __restrict__ gstack) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr bool kSphOnly = PM == 0;
     SceneView S = Sg;
@@ -3376,12 +3529,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NEE ? CR
     Path P;
     Trav R;
     R.state = kIdle;
-    [[maybe_unused]] Nee N;
+    [[maybe_unused]] std::conditional_t<LGT, LNee, Nee> N;
     bool need = true, cont = false;
     while (true) {
         set_prio<kPrioInit>();
         bool start = draw_batch(Q.queue, Q.batches, Q.n, lane, need, dry, b_base, b_cnt, b_pos, ray);
-        if constexpr (NEE) {
+        if constexpr (NEE || LGT) {
             if (start) nee_start(N);
         }
         if (start && !load_path(Q, ray, P)) {  // outside the contract: a miss, never traced
@@ -3411,7 +3564,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NEE ? CR
         if (R.state == kDone) {
             double acc[3] = {0, 0, 0};
             bool ended = true;
-            if constexpr (NEE) {
+            if constexpr (LGT) {
+                ended = light_segment<LSCENE, kSphOnly>(S, CL, Q, P, N, R.found, R.ref, R.tmax);
+                acc[0] = N.acc[0]; acc[1] = N.acc[1]; acc[2] = N.acc[2];
+            } else if constexpr (NEE) {
                 ended = nee_segment<LSCENE, kSphOnly>(S, CL, Q, P, N, R.found, R.ref, R.tmax);
                 acc[0] = N.acc[0]; acc[1] = N.acc[1]; acc[2] = N.acc[2];
             } else if constexpr (ENV) {
@@ -4898,15 +5054,15 @@ int device_trace_host(crt_scene* s, int device, const double* rays, size_t n, co
 
 // ---- radiance queries (crt_radiance_async) -----------------------------------------------------
 // One radiance_kernel launch (persistent_grid: its grid and scratch)
-template <typename SE, bool GSTACK, bool LSCENE, int PM, bool ENV, bool NEE>
+template <typename SE, bool GSTACK, bool LSCENE, int PM, bool ENV, bool NEE, bool LGT>
 static int launch_radiance(const crt_scene* s, int device, dev::Work W, size_t lds, const dev::CamView& C,
-                           dev::RadianceOf<ENV, NEE> Q, hipMemPool_t pool, hipStream_t stream) {
+                           dev::RadianceOf<ENV, NEE, LGT> Q, hipMemPool_t pool, hipStream_t stream) {
     lds = lds_tail(W, lds, radiance_tail(GSTACK, LSCENE));
-    const void* kfn = reinterpret_cast<const void*>(dev::radiance_kernel<SE, GSTACK, LSCENE, PM, ENV, NEE>);
+    const void* kfn = reinterpret_cast<const void*>(dev::radiance_kernel<SE, GSTACK, LSCENE, PM, ENV, NEE, LGT>);
     uint32_t blocks = 0;
     SE* gstack = nullptr;
     if (const int rc = persistent_grid(s, device, kfn, lds, Q.batches, GSTACK, pool, stream, blocks, gstack, Q.queue)) return rc;
-    hipLaunchKernelGGL((dev::radiance_kernel<SE, GSTACK, LSCENE, PM, ENV, NEE>), dim3(blocks), dim3(dev::kBlock), lds, stream,
+    hipLaunchKernelGGL((dev::radiance_kernel<SE, GSTACK, LSCENE, PM, ENV, NEE, LGT>), dim3(blocks), dim3(dev::kBlock), lds, stream,
                        view_of(s->dev[device]), C, W, Q, gstack);
     const hipError_t e = hipGetLastError();
     (void)hipFreeAsync(Q.queue, stream);
@@ -4916,38 +5072,38 @@ static int launch_radiance(const crt_scene* s, int device, dev::Work W, size_t l
 }
 
 // CRT_RADIANCE_PLAIN: plain_radiance_kernel (plain_launches)
-template <bool ENV, bool NEE>
-static int launch_plain_radiance(const crt_scene* s, int device, const dev::CamView& C, const dev::RadianceOf<ENV, NEE>& Q,
+template <bool ENV, bool NEE, bool LGT>
+static int launch_plain_radiance(const crt_scene* s, int device, const dev::CamView& C, const dev::RadianceOf<ENV, NEE, LGT>& Q,
                                  hipMemPool_t pool, hipStream_t st) {
     const dev::SceneView S = view_of(s->dev[device]);
     return plain_launches(s, Q.n, pool, st, "plain_radiance_kernel", [&](uint32_t blocks, uint32_t first, uint32_t* stacks) {
-        hipLaunchKernelGGL((dev::plain_radiance_kernel<ENV, NEE>), dim3(blocks), dim3(dev::kBlock), 0, st, S, C, Q, first, stacks);
+        hipLaunchKernelGGL((dev::plain_radiance_kernel<ENV, NEE, LGT>), dim3(blocks), dim3(dev::kBlock), 0, st, S, C, Q, first, stacks);
     });
 }
 
 // dispatch_trace's classes; every class takes the fast route (a path is many segments per queue
 // visit, unlike a single ray: DESIGN section 6e)
-template <typename SE, bool ENV, bool NEE>
+template <typename SE, bool ENV, bool NEE, bool LGT>
 static int dispatch_radiance(const crt_scene* s, int device, dev::Work W, const dev::CamView& C,
-                             const dev::RadianceOf<ENV, NEE>& Q, hipMemPool_t pool, hipStream_t st) {
+                             const dev::RadianceOf<ENV, NEE, LGT>& Q, hipMemPool_t pool, hipStream_t st) {
     const Layout L = scene_layout<SE>(s, W, camera_extra(), false);
     return by_class(L.cls, W.sphere_only != 0, [&](auto gstack, auto lscene, auto pm) {
-        return launch_radiance<SE, decltype(gstack)::value, decltype(lscene)::value, decltype(pm)::value, ENV, NEE>(s, device, W, L.lds, C, Q, pool, st);
+        return launch_radiance<SE, decltype(gstack)::value, decltype(lscene)::value, decltype(pm)::value, ENV, NEE, LGT>(s, device, W, L.lds, C, Q, pool, st);
     });
 }
 
 // the route of one call: the plain kernel, or the fast one for the scene's class and entry width
-template <bool ENV, bool NEE = false>
+template <bool ENV, bool NEE = false, bool LGT = false>
 static int route_radiance(const crt_scene* s, int device, const crt_radiance_params* prm, const dev::CamView& C,
-                          const dev::RadianceOf<ENV, NEE>& Q, hipMemPool_t pool, hipStream_t st) {
-    if (prm->flags & CRT_RADIANCE_PLAIN) return launch_plain_radiance<ENV, NEE>(s, device, C, Q, pool, st);
+                          const dev::RadianceOf<ENV, NEE, LGT>& Q, hipMemPool_t pool, hipStream_t st) {
+    if (prm->flags & CRT_RADIANCE_PLAIN) return launch_plain_radiance<ENV, NEE, LGT>(s, device, C, Q, pool, st);
     // device_trace's scene classes and interval rules; 0 <= t_min <= 2^100 here (crt_radiance_async)
     const DeviceCopy& c = s->dev[device];
     dev::Work W{};
     class_flags(s, flags_of(c), c.f32_ok, true, W);
     W.tmin32 = static_cast<float>(prm->t_min);
-    if (u16_entries(s)) return dispatch_radiance<uint16_t, ENV, NEE>(s, device, W, C, Q, pool, st);
-    return dispatch_radiance<uint32_t, ENV, NEE>(s, device, W, C, Q, pool, st);
+    if (u16_entries(s)) return dispatch_radiance<uint16_t, ENV, NEE, LGT>(s, device, W, C, Q, pool, st);
+    return dispatch_radiance<uint32_t, ENV, NEE, LGT>(s, device, W, C, Q, pool, st);
 }
 
 // env: null, or the call's environment (checked by crt_host.cpp; its texels on `device`): the ENV
@@ -4956,7 +5112,7 @@ static int route_radiance(const crt_scene* s, int device, const crt_radiance_par
 // and tables the NEE instances read; env is not used then.
 int device_radiance(const crt_scene* s, int device, const double* d_rays, size_t n, const uint32_t* d_states,
                     const crt_radiance_params* prm, const crt_env* env, double* d_rgb, void* stream,
-                    const crt_env_sampler* smp) {
+                    const crt_env_sampler* smp, const crt_light_sampler* lights) {
     int rc = check_device(device);
     if (rc) return rc;
     if (!s->dev[device].valid)
@@ -4984,6 +5140,12 @@ int device_radiance(const crt_scene* s, int device, const double* d_rays, size_t
     hipMemPool_t pool = nullptr;
     rc = pass_pool(device, &pool);
     if (rc) return rc;
+    if (lights) {  // of this scene on `device` (crt_host.cpp checks it); env and smp are null
+        dev::RadianceLights QL{};
+        static_cast<dev::Radiance&>(QL) = Q;
+        QL.tb = LightTables{lights->ref, lights->cdf, lights->sref, lights->sw, lights->W, lights->L};
+        return route_radiance<false, false, true>(s, device, prm, C, QL, pool, st);
+    }
     if (smp) {
         Q.env = smp->env;
         Q.tb = EnvTables{smp->w, smp->c, smp->m, smp->W};

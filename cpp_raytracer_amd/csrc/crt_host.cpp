@@ -1887,6 +1887,93 @@ int crt_render_lens_env_sampled(crt_scene* s, int device, const crt_camera* cam,
     return device_render_lens_host(s, device, cam, lens, env, rgb, true);
 }
 
+// ---- samplers of the scene's own lights: the rules below, then the calls' own, before any device
+// work; the *_lights entries are the plain entries with the sampler as one more argument -----------
+static int check_light_sampler(const std::string& who, const crt_light_sampler* smp, const crt_scene* s, int device) {
+    if (!smp) return fail(CRT_E_INVALID, who + "lights is null");
+    if (smp->scene != s) return fail(CRT_E_INVALID, who + "the light sampler was built for another scene");
+    if (smp->device != device)
+        return fail(CRT_E_INVALID, who + "the light sampler was built on device " + std::to_string(smp->device));
+    return CRT_OK;
+}
+
+int crt_light_sampler_create(const crt_scene* s, int device, crt_light_sampler** out) {
+    clear_error();
+    const std::string who = "crt_light_sampler_create: ";
+    if (!out) return fail(CRT_E_INVALID, who + "out is null");
+    *out = nullptr;
+    if (!s) return fail(CRT_E_INVALID, who + "scene is null");
+    if (device < 0 || device >= kMaxDevices || !s->dev[device].valid)
+        return fail(CRT_E_INVALID, who + "the scene is not resident on device " + std::to_string(device));
+    return device_light_sampler_create(s, device, out);
+}
+
+int crt_light_sampler_free(crt_light_sampler* lights) {
+    clear_error();
+    return device_light_sampler_free(lights);
+}
+
+int crt_light_sampler_view(const crt_light_sampler* lights, struct crt_light_sampler_view* out) {
+    clear_error();
+    if (!lights) return fail(CRT_E_INVALID, "crt_light_sampler_view: lights is null");
+    if (!out) return fail(CRT_E_INVALID, "crt_light_sampler_view: out is null");
+    out->num_lights = lights->L;
+    out->device = lights->device;
+    out->prim = lights->prim;
+    out->ref = lights->ref;
+    out->sorted_ref = lights->sref;
+    out->w = lights->w;
+    out->cdf = lights->cdf;
+    out->sorted_w = lights->sw;
+    out->W = lights->W;
+    return CRT_OK;
+}
+
+int crt_radiance_lights_async(const crt_scene* s, int device, const double* d_rays, size_t n, const uint32_t* d_states,
+                              const crt_radiance_params* params, const crt_light_sampler* lights, double* d_rgb,
+                              void* stream) {
+    clear_error();
+    const std::string who = "crt_radiance_lights_async: ";
+    int rc = check_radiance(who, s, d_rays, "d_rays", n, params, d_rgb, "d_rgb");
+    if (rc == CRT_OK) rc = check_light_sampler(who, lights, s, device);
+    if (rc) return rc;
+    if (n == 0) return CRT_OK;  // no work
+    return device_radiance(s, device, d_rays, n, d_states, params, nullptr, d_rgb, stream, nullptr, lights);
+}
+
+int crt_probes_lights_async(const crt_scene* s, int device, const double* d_points, const double* d_normals, size_t n,
+                            const crt_probe_params* params, const crt_light_sampler* lights, double* d_coeff,
+                            void* stream) {
+    clear_error();
+    const std::string who = "crt_probes_lights_async: ";
+    int rc = check_probes(who, true, s, d_points, "d_points", d_normals, "d_normals", n, params);
+    if (rc == CRT_OK) rc = check_light_sampler(who, lights, s, device);
+    if (rc) return rc;
+    if (n && !d_coeff) return fail(CRT_E_INVALID, who + "d_coeff is null (the output is required)");
+    if (n == 0) return CRT_OK;  // no work
+    return device_probes(s, device, d_points, d_normals, n, params, nullptr, d_coeff, stream, nullptr, lights);
+}
+
+int crt_render_lens_lights_async(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens,
+                                 const crt_light_sampler* lights, double* d_rgb, void* stream) {
+    clear_error();
+    const std::string who = "crt_render_lens_lights_async: ";
+    int rc = check_lens(who, true, s, cam, lens, true);
+    if (rc == CRT_OK) rc = check_light_sampler(who, lights, s, device);
+    if (rc) return rc;
+    if (!d_rgb) return fail(CRT_E_INVALID, who + "d_rgb is null (the output is required)");
+    return device_render_lens(s, device, cam, lens, nullptr, d_rgb, stream, nullptr, lights);
+}
+
+int crt_render_lens_lights(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, double* rgb) {
+    clear_error();
+    const std::string who = "crt_render_lens_lights: ";
+    const int rc = check_lens(who, true, s, cam, lens, true);
+    if (rc) return rc;
+    if (!rgb) return fail(CRT_E_INVALID, who + "rgb is null (the output is required)");
+    return device_render_lens_host(s, device, cam, lens, nullptr, rgb, false, true);
+}
+
 // ---- lens renders in passes: check_lens's rules, then the pass's (check_pass), the adaptive
 // parameters' and the denoiser's, all before any device work ------------------------------------
 int crt_render_lens_pass_async(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens,

@@ -368,6 +368,17 @@ struct crt_env_sampler {
     double W;
 };
 
+// crt_light_sampler (include/crt_render.h): the tables of one scene's lights on one device, one
+// allocation (w first). Pick order is ascending flattened primitive index.
+struct crt_light_sampler {
+    const crt_scene* scene;
+    int device;
+    uint32_t L;
+    double *w, *cdf, *sw;          // pick order, pick order, sref's order
+    uint32_t *prim, *ref, *sref;   // pick order, pick order, ascending
+    double W;
+};
+
 namespace crt {
 // The one device allocation of a scene copy (device_upload): 256-byte aligned sub-arrays in this
 // order; crt_scene_info reports its total as device_bytes.
@@ -446,10 +457,12 @@ int device_trace_host(crt_scene* s, int device, const double* rays, size_t n, co
 // env (here, in device_probes and in device_render_lens): null for the constant background, or a
 // checked crt_env whose texels are on `device` (the host form of the lens render uploads them).
 // smp (the same three): null, or the sampler of the *_env_sampled entries, built on `device`; env is
-// then its recorded crt_env and the launch is the NEE instances'
+// then its recorded crt_env and the launch is the NEE instances'.
+// lights (the same three): null, or the light sampler of the *_lights entries, of this scene on
+// `device`; env and smp are null then and the launch is the lights instances'
 int device_radiance(const crt_scene* s, int device, const double* d_rays, size_t n, const uint32_t* d_states,
                     const crt_radiance_params* prm, const crt_env* env, double* d_rgb, void* stream,
-                    const crt_env_sampler* smp = nullptr);
+                    const crt_env_sampler* smp = nullptr, const crt_light_sampler* lights = nullptr);
 int device_radiance_host(crt_scene* s, int device, const double* rays, size_t n, const uint32_t* states,
                          const crt_radiance_params* prm, double* rgb);
 // crt_launch_plan: the layout steps and the launchers' additions of the three scene kernels, run on
@@ -464,7 +477,7 @@ int device_probe_rays(int device, const double* d_points, const double* d_normal
                       const crt_probe_params* prm, double* d_rays, uint32_t* d_states, void* stream);
 int device_probes(const crt_scene* s, int device, const double* d_points, const double* d_normals, size_t n,
                   const crt_probe_params* prm, const crt_env* env, double* d_coeff, void* stream,
-                  const crt_env_sampler* smp = nullptr);
+                  const crt_env_sampler* smp = nullptr, const crt_light_sampler* lights = nullptr);
 int device_probes_host(crt_scene* s, int device, const double* points, const double* normals, size_t n,
                        const crt_probe_params* prm, double* coeff);
 int device_sh_eval(int device, const double* d_coeff, size_t num_probes, const uint32_t* d_index,
@@ -475,14 +488,19 @@ int device_sh_eval(int device, const double* d_coeff, size_t num_probes, const u
 int device_lens_rays(int device, const crt_camera* cam, const crt_lens* lens, uint32_t first_sample,
                      uint32_t num_samples, double* d_rays, uint32_t* d_states, void* stream);
 int device_render_lens(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, const crt_env* env,
-                       double* d_rgb, void* stream, const crt_env_sampler* smp = nullptr);
+                       double* d_rgb, void* stream, const crt_env_sampler* smp = nullptr,
+                       const crt_light_sampler* lights = nullptr);
 // sampled: a sampler is built on the uploaded texels for the call (crt_render_lens_env_sampled)
 int device_render_lens_host(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, const crt_env* env,
-                            double* rgb, bool sampled = false);
+                            double* rgb, bool sampled = false, bool lights = false);
 // luminance samplers of an environment (crt_env_sampler.hip; crt_host.cpp checks the arguments): the
 // tables on `device`, built blocking; CRT_E_INVALID when their total is not positive and finite
 int device_env_sampler_create(int device, const crt_env* env, crt_env_sampler** out);
 int device_env_sampler_free(crt_env_sampler* smp);
+// samplers of the scene's lights (crt_light_sampler.hip; crt_host.cpp checks the arguments): built
+// blocking from the copy on `device`; CRT_E_INVALID without a light or a usable total weight
+int device_light_sampler_create(const crt_scene* s, int device, crt_light_sampler** out);
+int device_light_sampler_free(crt_light_sampler* smp);
 // lens renders in passes: one pass into running sums (blocks != null: the blocks at `first` only; it
 // then waits for the stream once), the rays through the pixel centres, and the first-hit features
 int device_render_lens_pass(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, uint32_t first,

@@ -591,7 +591,7 @@ int device_lens_rays(int device, const crt_camera* cam, const crt_lens* lens, ui
 }
 
 int device_render_lens(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, const crt_env* env,
-                       double* d_rgb, void* stream, const crt_env_sampler* smp) {
+                       double* d_rgb, void* stream, const crt_env_sampler* smp, const crt_light_sampler* lights) {
     int rc = device_check(device);
     if (rc) return rc;
     if (!s->dev[device].valid)
@@ -627,7 +627,7 @@ int device_render_lens(const crt_scene* s, int device, const crt_camera* cam, co
         double* rgb = reinterpret_cast<double*>(scratch + records * 48);
         uint32_t* states = reinterpret_cast<uint32_t*>(scratch + records * (48 + 24));
         hipError_t e = ln::launch_rays(V, lens->kind, first, static_cast<uint32_t>(records), 0, spp, rays, states, st);
-        if (e == hipSuccess) rc = device_radiance(s, device, rays, records, states, &rp, env, rgb, st, smp);
+        if (e == hipSuccess) rc = device_radiance(s, device, rays, records, states, &rp, env, rgb, st, smp, lights);
         if (e == hipSuccess && rc == CRT_OK) {
             const dim3 grid((count + ln::kWavesPerBlock - 1) / ln::kWavesPerBlock), block(64 * ln::kWavesPerBlock);
             hipLaunchKernelGGL(ln::lens_reduce_kernel, grid, block, 0, st, rgb, count, spp, L, inv_spp, d_rgb + first * 3);
@@ -801,9 +801,10 @@ int device_lens_features(const crt_scene* s, int device, const crt_camera* cam, 
 // crt_render_lens: device_render_lens for a host array, blocking: the render on a stream of its
 // own, one copy back. env (null: none) has its texels in host memory here: uploaded for the call,
 // freed after it. sampled: once the texels have arrived a sampler is built on them (blocking), the
-// render goes through it, and it is freed with them
+// render goes through it, and it is freed with them. lights (env is null then): a light sampler of
+// the uploaded scene is built for the call (crt_render_lens_lights) and freed after it
 int device_render_lens_host(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, const crt_env* env,
-                            double* rgb, bool sampled) {
+                            double* rgb, bool sampled, bool lights) {
     int rc = device_upload(s, device);
     if (rc) return rc;
     DeviceGuard g(device);
@@ -826,7 +827,9 @@ int device_render_lens_host(crt_scene* s, int device, const crt_camera* cam, con
         e = hipStreamSynchronize(st);
         if (e == hipSuccess) rc = device_env_sampler_create(device, &d_env, &smp);
     }
-    if (e == hipSuccess && rc == CRT_OK) rc = device_render_lens(s, device, cam, lens, env ? &d_env : nullptr, d_rgb, st, smp);
+    crt_light_sampler* lsmp = nullptr;
+    if (e == hipSuccess && lights) rc = device_light_sampler_create(s, device, &lsmp);
+    if (e == hipSuccess && rc == CRT_OK) rc = device_render_lens(s, device, cam, lens, env ? &d_env : nullptr, d_rgb, st, smp, lsmp);
     if (e == hipSuccess && rc == CRT_OK) e = hipMemcpyAsync(rgb, d_rgb, bytes, hipMemcpyDeviceToHost, st);
     if (st) {
         const hipError_t se = hipStreamSynchronize(st);
@@ -834,6 +837,7 @@ int device_render_lens_host(crt_scene* s, int device, const crt_camera* cam, con
         (void)hipStreamDestroy(st);
     }
     (void)device_env_sampler_free(smp);
+    (void)device_light_sampler_free(lsmp);
     (void)hipFree(d_rgb);
     (void)hipFree(d_texels);
     if (rc) return rc;

@@ -208,7 +208,7 @@ int device_probe_rays(int device, const double* d_points, const double* d_normal
 
 int device_probes(const crt_scene* s, int device, const double* d_points, const double* d_normals, size_t n,
                   const crt_probe_params* prm, const crt_env* env, double* d_coeff, void* stream,
-                  const crt_env_sampler* smp) {
+                  const crt_env_sampler* smp, const crt_light_sampler* lights) {
     int rc = device_check(device);
     if (rc) return rc;
     if (!s->dev[device].valid)
@@ -245,7 +245,7 @@ int device_probes(const crt_scene* s, int device, const double* d_points, const 
         uint32_t* states = reinterpret_cast<uint32_t*>(scratch + records * (48 + 24));
         hipError_t e = pb::launch_rays(d_points, d_normals, static_cast<uint32_t>(first), static_cast<uint32_t>(records),
                                        prm, rays, states, st);
-        if (e == hipSuccess) rc = device_radiance(s, device, rays, records, states, &rp, env, rgb, st, smp);
+        if (e == hipSuccess) rc = device_radiance(s, device, rays, records, states, &rp, env, rgb, st, smp, lights);
         if (e == hipSuccess && rc == CRT_OK) {
             const dim3 grid((count + pb::kWavesPerBlock - 1) / pb::kWavesPerBlock), block(64 * pb::kWavesPerBlock);
             double* out = d_coeff + first * K * 3;

@@ -145,6 +145,21 @@ struct Environment {
     }
 };
 
+// Extension (not in the reference): the world's own lights as something to sample, for
+// Camera::render_lens(world, lens, lights) (crt_render_lens_lights): every Lambertian bounce also sends
+// a shadow ray to a point on a DiffuseLight primitive, weighted against the bounce's own light hits
+// (next-event estimation with MIS), so a small light is no longer found by chance alone. The world must
+// hold at least one light. A Lights belongs to the world it was made of.
+struct Lights {
+    const void* world = nullptr;
+    template <typename T>
+    static Lights of(const T& world) {
+        Lights l;
+        l.world = &world;
+        return l;
+    }
+};
+
 class Camera {
     size_t image_w = 1280, image_h = 720;
     double viewport_w = 0, viewport_h = 0;
@@ -424,12 +439,15 @@ class Camera {
         return img;
     }
 
-    Image render_scene_lens(const crt_api::GpuScene& g, const Lens& lens, const Environment* env = nullptr) {
+    Image render_scene_lens(const crt_api::GpuScene& g, const Lens& lens, const Environment* env = nullptr,
+                            bool lights = false) {
         init();
         resolved.base_seed = SeedSeqGenerator::get_instance().next_seed();
         const crt_lens l = lens.as_crt();
         std::vector<double> rgb(image_w * image_h * 3);
-        if (env) {
+        if (lights) {
+            if (crt_render_lens_lights(g.get(), 0, &resolved, &l, rgb.data())) crt_api::die("crt_render_lens_lights");
+        } else if (env) {
             const crt_env e = env->as_crt();
             if (env->importance) {
                 if (crt_render_lens_env_sampled(g.get(), 0, &resolved, &l, &e, rgb.data())) crt_api::die("crt_render_lens_env_sampled");
@@ -676,6 +694,22 @@ public:
         } else {
             crt_api::GpuScene s(world, 32, 12, true);
             return render_scene_lens(s, lens, &env);
+        }
+    }
+    // Extension (not in the reference): render_lens with the world's own lights sampled (crt_render_lens_lights).
+    Image render_lens(const BVH& world, const Lens& lens, const Lights& lights) {
+        if (lights.world != &world) crt_api::die("Camera::render_lens: the Lights were made of another world");
+        return render_scene_lens(world.gpu_scene(), lens, nullptr, true);
+    }
+    template <typename T>
+    requires std::is_base_of_v<Hittable, T>
+    Image render_lens(const T& world, const Lens& lens, const Lights& lights) {
+        if (lights.world != &world) crt_api::die("Camera::render_lens: the Lights were made of another world");
+        if constexpr (std::is_same_v<T, Scene>) {
+            return render_scene_lens(BVH(world).gpu_scene(), lens, nullptr, true);
+        } else {
+            crt_api::GpuScene s(world, 32, 12, true);
+            return render_scene_lens(s, lens, nullptr, true);
         }
     }
 

@@ -951,6 +951,99 @@ int crt_render_lens_env_sampled_async(const crt_scene* scene, int device, const 
 int crt_render_lens_env_sampled(crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens,
                                 const crt_env* env, double* rgb);
 
+/* ---- the scene's own lights sampled: next-event estimation with MIS --------------------------
+ * In the radiance, probe and lens calls a path finds a DiffuseLight only by bouncing into it. A
+ * crt_light_sampler draws points on the scene's emitting primitives, and the *_lights entries send a
+ * shadow ray to one at every Lambertian bounce and combine it with the bounce's own light hits by
+ * the balance heuristic. An addition to the ABI (no existing call changes, CRT_ABI_VERSION stays).
+ * Tables are doubles; every operation below is an IEEE f64 + - * /, a sqrt or a comparison; nothing
+ * is fused; dot products are (a0 b0 + a1 b1) + a2 b2; pi is the double 3.141592653589793.
+ *
+ * crt_light_sampler_create blocks. The scene must be resident on `device` (crt_scene_upload). The
+ * lights are the flattened primitives whose material is CRT_DIFFUSE_LIGHT (a Box gives its six
+ * parallelograms), listed in ascending flattened primitive index, the index crt_hit.prim reports,
+ * so a pick does not depend on the BVH parameters. For light i:
+ *   e = color * param per channel;  Y = (0.2126 * e0 + 0.7152 * e1) + 0.0722 * e2, then
+ *   Y = Y > 0 ? Y : 0 (NaN and negatives give 0);
+ *   A = sqrt(cr . cr) with cr = s1 x s2 = (s1y s2z - s1z s2y, s1z s2x - s1x s2z, s1x s2y - s1y s2x)
+ *   for a parallelogram, A = (4.0 * pi) * (r * r) for a sphere;
+ *   w[i] = Y * A;  cdf[0] = 0.0 + w[0],  cdf[i] = cdf[i - 1] + w[i];  W = cdf[L - 1].
+ * The sums are sequential in that order. Beside them the sampler keeps the lights' slot references
+ * (what a hit's ref is: the slot's index in its kind's array, the high bit set for a parallelogram)
+ * sorted ascending with w in the same order, so a hit finds its light's w by binary search.
+ * CRT_E_INVALID (the message names the rule): scene or out NULL; a scene not resident on `device`;
+ * a scene with no light; !(W > 0 && W < inf).
+ * crt_light_sampler_view gives L, the device pointers and W. crt_light_sampler_free(NULL) is CRT_OK.
+ * The sampler reads the scene's device copy at every call: free it before the scene.
+ *
+ * light_pick(xi1) = the number of entries with cdf[k] <= xi1 * W, clamped to L - 1 (the clamp covers
+ *   the largest rnd_01 value, which exceeds 1, and NaN).
+ * light_point(i, state): parallelogram: xi2, xi3 = crt_rand_double(state, 0, 1) in that order,
+ *   p = (v + s1 * xi2) + s2 * xi3 per component. Sphere: u = random_unit_vector(state) (the rejection
+ *   loop of the Lambertian scatter: its draw count varies), p = c + u * |r|. Neither uses sin or cos:
+ *   that is why spheres are sampled by area over the whole surface and not by the cone they subtend.
+ * light_pdf, the solid-angle density with which the sampler produces the point where a ray (o, d)
+ *   actually hit light j at t, with the hit's normal n (either side) and front flag, the same
+ *   function for shadow hits and bounce hits: v = d * t, vv = v . v,
+ *   pl = ((w_j / W) / A_j) * ((vv * sqrt(vv)) / |n . v|); pl = 0 where w_j is not > 0; for a sphere
+ *   pl = 0 unless the hit is on the geometric outside, front == (r > 0) (hollow spheres have r < 0).
+ *
+ * The estimator is crt_radiance_async's integrator with a constant background and these additions.
+ * A path carries acc, +0 per channel at its start, and pb, "none" at its start and after a Metal or
+ * Dielectric bounce.
+ *   Light hit on an ordinary segment: f = 1.0 if pb is none, else pl = light_pdf(hit) and
+ *     f = (pl + pb) > 0 ? pb / (pl + pb) : 0.0; acc = acc + (T * emit) * f, the path ends.
+ *   Lambertian bounce, after the material's own draws, the throughput multiply and the depth
+ *   decrement, if depth left > 0: xi1 = crt_rand_double(state, 0, 1) (always drawn);
+ *     i = light_pick(xi1); p_l = light_point(i) (its draws are always made); d_s = p_l - o, o the hit
+ *     point; c_s = (n . d_s) / sqrt(d_s . d_s), n the hit normal facing the ray;
+ *     pb = ((n . nd) / sqrt(nd . nd)) / pi for the scattered direction nd. No shadow ray is sent if
+ *     !(c_s > 0) (NaN and a zero-length d_s fall here) or, for a sphere, if !(u . d_s < 0) (a point
+ *     on the far side, which the near side hides). Otherwise the segment from o along d_s over
+ *     (t_min, +inf) is traced as any segment is, closest hit. It contributes only if it finds a hit
+ *     whose ref is light i's slot: then pl = light_pdf(that hit), pb_s = c_s / pi, and if
+ *     pl > 0 && pl < inf, acc = acc + (T * emit_i) * (pb_s / (pl + pb_s)). Any other hit, or none,
+ *     adds nothing (a nearer light k that hides light i drops the sample; the bounce strategy's hit
+ *     on k is weighted with k's own density, so the two weights sum to 1 wherever a contribution is
+ *     not zero). The path then goes on along nd.
+ *   Metal or Dielectric bounce: pb = none.
+ *   Escape: acc = acc + T * background, no weight (nothing samples the background).
+ *   The output is acc: absorbed paths and paths out of depth write what they gathered.
+ * A path with no Lambertian bounce, and every path with max_depth == 1, gets crt_radiance_async's
+ * bytes. Rays the query contract refuses stay first-segment misses. Neither the grid nor the route
+ * (CRT_RADIANCE_PLAIN) changes a bit.
+ *
+ * The *_lights entries are crt_radiance_async, crt_probes_async, crt_render_lens_async and
+ * crt_render_lens with the sampler as one more argument: same buffers, same rules. CRT_E_INVALID in
+ * addition, before any device work: lights NULL; a sampler of another scene; a sampler built on
+ * another device. max_depth == 0 is still a memset. The probes' and the lens frames' first segments
+ * have pb = none. Lights together with an environment are not offered. */
+typedef struct crt_light_sampler crt_light_sampler;
+struct crt_light_sampler_view {    /* the entry below has the same name: no typedef, say `struct` */
+    uint32_t num_lights;            /* L */
+    int32_t device;
+    const uint32_t *prim, *ref;     /* DEVICE, pick order: flattened primitive index, slot reference */
+    const uint32_t* sorted_ref;     /* DEVICE: the slot references ascending */
+    const double *w, *cdf;          /* DEVICE, pick order */
+    const double* sorted_w;         /* DEVICE: w in sorted_ref's order */
+    double W;
+};                                  /* 64 bytes */
+int crt_light_sampler_create(const crt_scene* scene, int device, crt_light_sampler** out);
+int crt_light_sampler_free(crt_light_sampler* lights);
+int crt_light_sampler_view(const crt_light_sampler* lights, struct crt_light_sampler_view* out);
+int crt_radiance_lights_async(const crt_scene* scene, int device, const double* d_rays, size_t n,
+                              const uint32_t* d_states, const crt_radiance_params* params,
+                              const crt_light_sampler* lights, double* d_rgb, void* stream);
+int crt_probes_lights_async(const crt_scene* scene, int device, const double* d_points,
+                            const double* d_normals, size_t n, const crt_probe_params* params,
+                            const crt_light_sampler* lights, double* d_coeff, void* stream);
+int crt_render_lens_lights_async(const crt_scene* scene, int device, const crt_camera* cam,
+                                 const crt_lens* lens, const crt_light_sampler* lights, double* d_rgb,
+                                 void* stream);
+/* crt_render_lens with the lights sampled: uploads the scene if needed, builds a sampler, renders,
+ * frees it. crt_light_sampler_create's rules hold. */
+int crt_render_lens_lights(crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens, double* rgb);
+
 /* ---- lens renders in passes ------------------------------------------------------------------
  * A lens render cut into passes, with the state the camera-agnostic calls read: crt_noise_estimate,
  * crt_adaptive_update, crt_pixel_variance_async and crt_denoise_async take d_sum, d_noise, block
