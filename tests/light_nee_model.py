@@ -163,6 +163,10 @@ class Trace:
     hits_plain: list = field(default_factory=list)      # path: a light hit with pb none (f = 1)
     after_specular: list = field(default_factory=list)  # path: a hits_plain after a Metal or Dielectric bounce
     lambertian: set = field(default_factory=set)        # paths that scattered off a Lambertian at least once
+    missed: list = field(default_factory=list)          # path: the half of dropped whose shadow ray hit nothing
+    unweighable: list = field(default_factory=list)     # path: the other half: its light reached, pl not in (0, inf)
+    picks: list = field(default_factory=list)           # (path, light index, xi1) of every sample drawn
+    inside_hits: list = field(default_factory=list)     # path: a light hit with pb set on a sphere's inside (pl = 0)
 
 
 def ray_color(orc, scene, rays, states, max_depth, background, t_min, tb, crt=None, bvh=None):
@@ -215,6 +219,8 @@ def ray_color(orc, scene, rays, states, max_depth, background, t_min, tb, crt=No
                         tr.after_specular.append(i)
                 else:
                     pl = float(pdf(tb, li, h["t"][j], h["normal"][j], d[i], h["front_face"][j] != 0)[0])
+                    if tb.kind[li] == SPHERE and (h["front_face"][j] != 0) != (tb.geom[li][1] > 0):
+                        tr.inside_hits.append(i)
                     s = pl + pb[i]
                     f = pb[i] / s if s > 0 else 0.0
                     tr.hits_weighted.append((i, f))
@@ -243,6 +249,7 @@ def ray_color(orc, scene, rays, states, max_depth, background, t_min, tb, crt=No
                 continue
             rng[i], xi1 = crt.rand_double(rng[i], 0.0, 1.0)
             li = int(pick(tb, xi1)[0])
+            tr.picks.append((i, li, xi1))
             rng[i], p, u = point(crt, tb, li, rng[i])
             oi = o[i].tolist()
             ds = [p[k] - oi[k] for k in range(3)]
@@ -264,6 +271,7 @@ def ray_color(orc, scene, rays, states, max_depth, background, t_min, tb, crt=No
                 if p != int(tb.prim[li]):
                     if p < 0:
                         tr.dropped.append(i)
+                        tr.missed.append(i)
                     elif p in tb.of_prim:
                         tr.hidden_light.append(i)
                     else:
@@ -272,6 +280,7 @@ def ray_color(orc, scene, rays, states, max_depth, background, t_min, tb, crt=No
                 pl = float(pdf(tb, li, hs["t"][j], hs["normal"][j], ds, hs["front_face"][j] != 0)[0])
                 if not (pl > 0 and pl < math.inf):
                     tr.dropped.append(i)
+                    tr.unweighable.append(i)
                     continue
                 pbs = cs / PI
                 f = pbs / (pl + pbs)
