@@ -129,6 +129,9 @@ class Trace:
     escapes_weighted: list = field(default_factory=list)  # (path, f): an escape with pb not none
     escapes_plain: list = field(default_factory=list)  # path: an escape with pb none (f = 1)
     lambertian: set = field(default_factory=set)       # paths that scattered off a Lambertian at least once
+    below: list = field(default_factory=list)          # path: of nee_skipped, c_s <= 0 (asked first)
+    zero_pdf: list = field(default_factory=list)       # path: of nee_skipped, c_s > 0 and pe_s <= 0
+    picks: list = field(default_factory=list)          # (path, row r, column k, (xi1..xi4), d_s as 3 floats) per sample
 
 
 def ray_color(orc, scene, rays, states, max_depth, background, t_min, env, tb, crt=None, bvh=None):
@@ -227,6 +230,10 @@ def ray_color(orc, scene, rays, states, max_depth, background, t_min, env, tb, c
                 has_pb[lam] = True
                 go = (cs > 0) & (pes > 0)
             tr.nee_skipped.extend(lam[~go].tolist())
+            tr.below.extend(lam[~(cs > 0)].tolist())
+            tr.zero_pdf.extend(lam[(cs > 0) & ~(pes > 0)].tolist())
+            tr.picks.extend(zip(lam.tolist(), *(a.tolist() for a in pick(env, tb, xi[:, 0], xi[:, 1])), map(tuple, xi.tolist()),
+                                map(tuple, ds.tolist())))
             if go.any():
                 s_i, s_d = lam[go], ds[go]
                 with np.errstate(all="ignore"):
