@@ -27,12 +27,13 @@
 //   lens_centre_rays_kernel / lens_feature_kernel  the ray through every pixel's centre, and
 //                       crt_feature records from the crt_hit records device_trace gives for them
 // The host side cuts the frame into batches of whole pixels in row-major order whose scratch (rays,
-// radiance, states: 76 bytes a record) comes from the pass pool; nothing is carried between batches.
+// radiance, states: 76 bytes a record) is a buffer kept per device (LensScratch); nothing is carried between batches.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
 #include <limits>
+#include <mutex>
 #include <string>
 
 #include "crt_internal.h"
@@ -577,6 +578,69 @@ static uint64_t lens_batch_size(const crt_lens* lens, uint64_t spp) {
     return std::max<uint64_t>(b, 1);
 }
 
+// The batch scratch of the lens renders (rays, radiance, states): a buffer of the library's own, one kept per
+// device and grown on demand, not a block of the stream-ordered pass pool. A whole-frame batch is larger than what
+// the pool keeps reserved; the runtime then maps more memory into the pool for the call and gives it back after
+// it (reserved 32 -> 64 -> 32 MiB at every call, whatever the release threshold), and the first accesses of the
+// call's kernels to such a block went wrong on the MI355X: rays the generator had written were read as what the
+// memory held before, for the first 1024 batches or so of the radiance kernel. Memory from
+// hipMalloc showed none of it.
+// take(): the kept buffer if it is large enough and no other call holds it, after the work of its last user (an
+// event, waited for on the caller's stream); else a fresh allocation. give(): records the event and keeps the
+// buffer, or, for a fresh one, keeps it in place of a smaller kept one (which is freed once its last user is
+// done) or frees it once the stream is done (two calls at once on one device: rare, and it blocks).
+struct LensScratch {
+    std::mutex mu;
+    char* ptr = nullptr;
+    size_t bytes = 0;
+    hipEvent_t done = nullptr;
+    bool held = false;
+};
+static LensScratch g_lens_scratch[kMaxDevices];
+
+static hipError_t lens_scratch_take(int device, size_t bytes, hipStream_t st, char** out) {
+    LensScratch& c = g_lens_scratch[device];
+    {
+        std::lock_guard<std::mutex> lk(c.mu);
+        if (c.ptr && c.bytes >= bytes && !c.held) {
+            const hipError_t e = hipStreamWaitEvent(st, c.done, 0);
+            if (e != hipSuccess) return e;
+            c.held = true;
+            *out = c.ptr;
+            return hipSuccess;
+        }
+    }
+    return hipMalloc(reinterpret_cast<void**>(out), bytes);
+}
+
+static void lens_scratch_give(int device, char* p, size_t bytes, hipStream_t st) {
+    LensScratch& c = g_lens_scratch[device];
+    std::unique_lock<std::mutex> lk(c.mu);
+    if (p == c.ptr) {
+        (void)hipEventRecord(c.done, st);
+        c.held = false;
+        return;
+    }
+    if (!c.held && bytes > c.bytes) {  // the fresh buffer takes the kept one's place
+        char* old = c.ptr;
+        hipEvent_t ev = c.done;
+        if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) ev = nullptr;
+        if (ev) {
+            if (old) (void)hipEventSynchronize(ev);
+            (void)hipEventRecord(ev, st);
+            c.ptr = p;
+            c.bytes = bytes;
+            c.done = ev;
+            lk.unlock();
+            if (old) (void)hipFree(old);
+            return;
+        }
+    }
+    lk.unlock();
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(p);
+}
+
 int device_lens_rays(int device, const crt_camera* cam, const crt_lens* lens, uint32_t first_sample,
                      uint32_t num_samples, double* d_rays, uint32_t* d_states, void* stream) {
     const int rc = device_check(device);
@@ -603,10 +667,6 @@ int device_render_lens(const crt_scene* s, int device, const crt_camera* cam, co
         HIP_TRY(hipMemsetAsync(d_rgb, 0, pixels * 3 * sizeof(double), st));
         return CRT_OK;
     }
-    void* pool_v = nullptr;
-    rc = device_pass_pool(device, &pool_v);
-    if (rc) return rc;
-    hipMemPool_t pool = static_cast<hipMemPool_t>(pool_v);
     crt_radiance_params rp{};
     rp.max_depth = cam->max_depth;
     rp.base_seed = cam->base_seed;  // unused: every path has a state
@@ -622,7 +682,7 @@ int device_render_lens(const crt_scene* s, int device, const crt_camera* cam, co
         const size_t records = static_cast<size_t>(count) * spp;
         // one allocation: the rays, the radiance, then the states
         char* scratch = nullptr;
-        HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void**>(&scratch), records * (48 + 24 + 4), pool, st));
+        HIP_TRY(lens_scratch_take(device, records * (48 + 24 + 4), st, &scratch));
         double* rays = reinterpret_cast<double*>(scratch);
         double* rgb = reinterpret_cast<double*>(scratch + records * 48);
         uint32_t* states = reinterpret_cast<uint32_t*>(scratch + records * (48 + 24));
@@ -633,7 +693,7 @@ int device_render_lens(const crt_scene* s, int device, const crt_camera* cam, co
             hipLaunchKernelGGL(ln::lens_reduce_kernel, grid, block, 0, st, rgb, count, spp, L, inv_spp, d_rgb + first * 3);
             e = hipGetLastError();
         }
-        (void)hipFreeAsync(scratch, st);
+        lens_scratch_give(device, scratch, records * (48 + 24 + 4), st);
         if (e != hipSuccess) return fail(CRT_E_HIP, std::string("lens kernels: ") + hipGetErrorString(e));
         if (rc) return rc;
     }
@@ -705,7 +765,7 @@ int device_render_lens_pass(const crt_scene* s, int device, const crt_camera* ca
         double* rgb = nullptr;
         hipError_t e = hipSuccess;
         if (trace) {  // one allocation: the rays, the radiance, then the states
-            e = hipMallocFromPoolAsync(reinterpret_cast<void**>(&scratch), records * (48 + 24 + 4), pool, st);
+            e = lens_scratch_take(device, records * (48 + 24 + 4), st, &scratch);
             if (e == hipSuccess) {
                 double* rays = reinterpret_cast<double*>(scratch);
                 rgb = reinterpret_cast<double*>(scratch + records * 48);
@@ -725,7 +785,7 @@ int device_render_lens_pass(const crt_scene* s, int device, const crt_camera* ca
             }
             e = hipGetLastError();
         }
-        if (scratch) (void)hipFreeAsync(scratch, st);
+        if (scratch) lens_scratch_give(device, scratch, records * (48 + 24 + 4), st);
         if (e != hipSuccess) rc = fail(CRT_E_HIP, std::string("lens pass kernels: ") + hipGetErrorString(e));
     }
     if (list) (void)hipFreeAsync(list, st);

@@ -789,8 +789,9 @@ int crt_lens_rays_async(int device, const crt_camera* cam, const crt_lens* lens,
  * floating-point atomics are used. With kind PINHOLE the frame is crt_render_async's, bit for bit.
  * Batches: consecutive whole pixels in row-major order, batch_pixels of them (0: the most whose
  * scratch of 76 bytes a record stays at or under 256 MiB; never fewer than one pixel, never more than
- * 2^31 - 1 records), each generated, traced, reduced and freed in order on `stream`, scratch from the
- * pass pool. Nothing is carried between batches.
+ * 2^31 - 1 records), each generated, traced and reduced in order on `stream`, in a scratch buffer the
+ * library keeps per device (grown on demand; a second call on the device while one is being enqueued
+ * allocates its own and waits for its stream before freeing it). Nothing is carried between batches.
  * max_depth == 0 writes +0 everywhere with a memset and launches nothing. The scene must be resident
  * on `device` (CRT_E_NOT_UPLOADED). CRT_E_INVALID, checked before any device work (the message names
  * the rule): scene, cam, lens or d_rgb NULL; unknown kind; unknown flags; a component of right, up
@@ -1084,8 +1085,8 @@ int crt_render_lens_lights(crt_scene* scene, int device, const crt_camera* cam, 
  * active pixels (4 bytes); active_hint is accepted for symmetry with crt_render_pass_masked_async
  * and sizes nothing. Without d_blocks the call only enqueues on `stream`.
  * Batches: whole pixels, lens->batch_pixels of them (0: as crt_render_lens_async's, for num_samples
- * records a pixel), each generated, traced, accumulated and freed in order; scratch from the pass
- * pool. max_depth == 0: every L_s is +0; the pass makes the additions above with +0 and launches
+ * records a pixel), each generated, traced and accumulated in order, in crt_render_lens_async's
+ * scratch buffer. max_depth == 0: every L_s is +0; the pass makes the additions above with +0 and launches
  * no trace. The scene must be resident on `device` (CRT_E_NOT_UPLOADED). */
 int crt_render_lens_pass_async(const crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens,
                                uint32_t first_sample, uint32_t num_samples, double* d_sum, double* d_noise,
