@@ -22,7 +22,7 @@ from ._capi import (CRT_BOX, CRT_DIELECTRIC, CRT_DIFFUSE_LIGHT, CRT_LAMBERTIAN, 
                     DenoiseParams, RenderStats, SceneInfo, Tiling, TraceParams, CRT_TRACE_ANY, CRT_TRACE_PLAIN,
                     RadianceParams, CRT_RADIANCE_PLAIN, ProbeParams, CRT_PROBE_SPHERE, CRT_PROBE_HEMISPHERE,
                     CRT_SH_RADIANCE, CRT_SH_IRRADIANCE, Lens, CRT_LENS_PINHOLE, CRT_LENS_ORTHOGRAPHIC,
-                    CRT_LENS_EQUIRECT, CRT_LENS_FISHEYE, CRT_LENS_CUBE, EnvView, EnvSamplerView, LightSamplerView, CRT_ENV_NEAREST, CRT_ENV_BILINEAR,
+                    CRT_LENS_EQUIRECT, CRT_LENS_FISHEYE, CRT_LENS_CUBE, EnvView, EnvSamplerView, LightSamplerView, LightingView, CRT_ENV_NEAREST, CRT_ENV_BILINEAR,
                     check, lib)
 
 __all__ = [
@@ -36,7 +36,7 @@ __all__ = [
     "Lens", "make_lens", "CRT_LENS_PINHOLE", "CRT_LENS_ORTHOGRAPHIC", "CRT_LENS_EQUIRECT", "CRT_LENS_FISHEYE",
     "CRT_LENS_CUBE", "LensRender",
     "Env", "EnvView", "EnvSamplerView", "EnvTables", "make_env", "CRT_ENV_NEAREST", "CRT_ENV_BILINEAR",
-    "LightSampler", "LightSamplerView", "LightTables",
+    "LightSampler", "LightSamplerView", "LightTables", "Lighting", "LightingView",
     "CRT_LAMBERTIAN", "CRT_METAL", "CRT_DIELECTRIC", "CRT_DIFFUSE_LIGHT",
     "CRT_SPHERE", "CRT_PARALLELOGRAM", "CRT_BOX",
 ]
@@ -294,6 +294,42 @@ def _lights_on(who: str, lights, env, scene, device: int) -> int:
     if lights.scene is not scene or lights.device != device:
         raise CrtError(f"{who}: the LightSampler belongs to another scene or device (it is on device {lights.device})")
     return lights.handle
+
+
+class Lighting:
+    """What lights a radiance, probe or lens call (lighting=): two independent choices. env: None (the
+    constant background) or an Env (make_env), whose importance decides between the sampled and the
+    plain map. lights: None or a LightSampler (GpuScene.light_sampler). With both, every Lambertian
+    bounce samples the map and the lights, each weighted against the bounce (include/crt_render.h,
+    crt_lighting). The object keeps both alive; Lighting() with nothing set is the unlit call."""
+
+    def __init__(self, env: Optional["Env"] = None, lights: Optional["LightSampler"] = None):
+        if env is not None and not isinstance(env, Env):
+            raise CrtError("Lighting: env must be an Env (make_env)")
+        if lights is not None and not isinstance(lights, LightSampler):
+            raise CrtError("Lighting: lights must be a LightSampler (GpuScene.light_sampler)")
+        self.env, self.lights = env, lights
+
+
+def _lighting_on(who: str, lighting, env, lights, scene, device: int) -> Optional[LightingView]:
+    """The crt_lighting of lighting= for a call of `scene` on `device` (None without one), after the
+    front end's rules: not with env= or lights=; the members' own rules as env= and lights= have them."""
+    if lighting is None:
+        return None
+    if env is not None or lights is not None:
+        raise ValueError(f"{who}: lighting= cannot be combined with env= or lights=")
+    if not isinstance(lighting, Lighting):
+        raise CrtError(f"{who}: lighting must be a Lighting")
+    view = LightingView()
+    if lighting.env is not None:
+        ev = _env_on(who, lighting.env, device)
+        if lighting.env.sampler:
+            view.sampler = lighting.env.sampler
+        else:
+            view.env = C.pointer(ev)  # the structure keeps ev alive
+    if lighting.lights is not None:
+        view.lights = _lights_on(who, lighting.lights, None, scene, device)
+    return view
 
 
 def _env_texels_ok(t) -> bool:
@@ -779,7 +815,8 @@ class GpuScene:
 
     def radiance_async(self, device: int, rays_ptr: int, n: int, out_ptr: int, states_ptr: int = 0, *,
                        max_depth: int, background, t_min: float = 1e-5, base_seed: int = 0, flags: int = 0,
-                       stream: int = 0, env: Optional[EnvView] = None, sampler: int = 0, lights: int = 0) -> None:
+                       stream: int = 0, env: Optional[EnvView] = None, sampler: int = 0, lights: int = 0,
+                       lighting: Optional[LightingView] = None) -> None:
         """Enqueue a radiance query on device buffers (crt_radiance_async): n rays of 6 doubles at
         rays_ptr, each the first segment of one path of ray_color with `max_depth` bounces over
         (t_min, inf). Path i's LCG state is the uint32 states_ptr[i], or sample_seed(base_seed, i, 0)
@@ -789,9 +826,18 @@ class GpuScene:
         a miss see it in place of `background` (crt_radiance_env_async). sampler: a crt_env_sampler
         handle built on `device` (Env.sampler) in place of env (crt_radiance_env_sampled_async). lights: a
         crt_light_sampler handle of this scene on `device` (LightSampler.handle), without env or sampler
-        (crt_radiance_lights_async)."""
+        (crt_radiance_lights_async). lighting: a LightingView (crt_lighting) in place of all three: an
+        environment and the lights together (crt_radiance_lit_async)."""
         prm = RadianceParams(max_depth, base_seed & 0xFFFFFFFF, _capi.D3(*[float(v) for v in background]), t_min,
                              flags, 0)
+        if lighting is not None:
+            if env is not None or sampler or lights:
+                raise ValueError("radiance_async: lighting= cannot be combined with env=, sampler= or lights=")
+            check(lib().crt_radiance_lit_async(self._h, device, C.c_void_p(rays_ptr or None), n,
+                                               C.c_void_p(states_ptr or None), C.byref(prm), C.byref(lighting),
+                                               C.c_void_p(out_ptr or None), C.c_void_p(stream)),
+                  "crt_radiance_lit_async")
+            return
         if lights:
             check(lib().crt_radiance_lights_async(self._h, device, C.c_void_p(rays_ptr or None), n,
                                                   C.c_void_p(states_ptr or None), C.byref(prm), C.c_void_p(lights),
@@ -816,14 +862,15 @@ class GpuScene:
 
     def radiance(self, rays, states=None, max_depth: int = 50, background=(0.7, 0.8, 1.0), t_min: float = 1e-5,
                  base_seed: int = 0, plain: bool = False, env: Optional[Env] = None,
-                 lights: Optional[LightSampler] = None):
+                 lights: Optional[LightSampler] = None, lighting: Optional[Lighting] = None):
         """Path-traced radiance of the caller's rays on torch tensors of a GPU: rays (n, 6) float64,
         states None or an (n,) int32 tensor on the rays' device whose bits are the paths' LCG states
         (None: sample_seed(base_seed, i, 0)). Runs on the rays' device and its current stream and
         does not synchronise; the scene is uploaded there first if it is not yet (that blocks).
         Returns an (n, 3) float64 tensor. env (make_env, on the rays' device): the environment that
         paths leaving the scene see in place of `background`. lights (light_sampler, of the
-        rays' device; not with env): every Lambertian bounce also samples the scene's lights (MIS)."""
+        rays' device; not with env): every Lambertian bounce also samples the scene's lights (MIS).
+        lighting (a Lighting; not with env or lights): an environment and the lights together."""
         import torch
         if env is not None and not isinstance(env, Env):
             raise CrtError("radiance: env must be an Env (make_env)")
@@ -831,6 +878,7 @@ class GpuScene:
             raise CrtError("radiance: rays must be an (n, 6) float64 tensor on a GPU")
         rays = rays.contiguous()
         n, device = rays.shape[0], rays.device.index
+        lit = _lighting_on("radiance", lighting, env, lights, self, device)
         lh = _lights_on("radiance", lights, env, self, device)
         view = _env_on("radiance", env, device) if env is not None else None
         if states is not None:
@@ -847,7 +895,7 @@ class GpuScene:
                                     background=background, t_min=t_min, base_seed=base_seed,
                                     flags=CRT_RADIANCE_PLAIN if plain else 0,
                                     stream=torch.cuda.current_stream(device).cuda_stream, env=view,
-                                    sampler=(env.sampler or 0) if env is not None else 0, lights=lh)
+                                    sampler=(env.sampler or 0) if env is not None else 0, lights=lh, lighting=lit)
             return out
 
     @staticmethod
@@ -862,7 +910,7 @@ class GpuScene:
     def probes_async(self, device: int, points_ptr: int, normals_ptr: int, n: int, out_ptr: int, *, samples: int,
                      mode=CRT_PROBE_SPHERE, max_depth: int, background, t_min: float = 1e-5, base_seed: int = 0,
                      batch_probes: int = 0, flags: int = 0, stream: int = 0, env: Optional[EnvView] = None,
-                     sampler: int = 0, lights: int = 0) -> None:
+                     sampler: int = 0, lights: int = 0, lighting: Optional[LightingView] = None) -> None:
         """Enqueue a probe bake on device buffers (crt_probes_async): n points of 3 doubles at
         points_ptr, with CRT_PROBE_HEMISPHERE their unit normals at normals_ptr (0 with
         CRT_PROBE_SPHERE). `samples` directions a probe are drawn on the device, path-traced as
@@ -870,8 +918,16 @@ class GpuScene:
         bands 0..2 per channel) or n x 1 x 3 (irradiance) go to out_ptr. batch_probes sizes the
         internal batches only; flags may hold CRT_RADIANCE_PLAIN: the same bits either way. The scene
         must be uploaded to `device`. env, sampler: as radiance_async's (crt_probes_env_async,
-        crt_probes_env_sampled_async). lights: as radiance_async's (crt_probes_lights_async)."""
+        crt_probes_env_sampled_async). lights: as radiance_async's (crt_probes_lights_async). lighting: as
+        radiance_async's (crt_probes_lit_async)."""
         prm = self._probe_params(samples, mode, max_depth, background, t_min, base_seed, batch_probes, flags)
+        if lighting is not None:
+            if env is not None or sampler or lights:
+                raise ValueError("probes_async: lighting= cannot be combined with env=, sampler= or lights=")
+            check(lib().crt_probes_lit_async(self._h, device, C.c_void_p(points_ptr or None),
+                                             C.c_void_p(normals_ptr or None), n, C.byref(prm), C.byref(lighting),
+                                             C.c_void_p(out_ptr or None), C.c_void_p(stream)), "crt_probes_lit_async")
+            return
         if lights:
             check(lib().crt_probes_lights_async(self._h, device, C.c_void_p(points_ptr or None),
                                                 C.c_void_p(normals_ptr or None), n, C.byref(prm), C.c_void_p(lights),
@@ -909,18 +965,21 @@ class GpuScene:
 
     def probes(self, points, normals=None, samples: int = 1024, mode: str = "sphere", max_depth: int = 50,
                background=(0.7, 0.8, 1.0), t_min: float = 1e-5, base_seed: int = 0, batch_probes: int = 0,
-               plain: bool = False, env: Optional[Env] = None, lights: Optional[LightSampler] = None):
+               plain: bool = False, env: Optional[Env] = None, lights: Optional[LightSampler] = None,
+               lighting: Optional[Lighting] = None):
         """Probe bake on torch tensors of a GPU: points (n, 3) float64; with mode="hemisphere", normals
         (n, 3) float64 unit vectors on the points' device (None with mode="sphere"). Runs on the
         points' device and its current stream and does not synchronise; the scene is uploaded there
         first if it is not yet (that blocks). Returns an (n, 9, 3) float64 tensor of SH coefficients
         (sphere; sh_eval evaluates them) or (n, 1, 3) of irradiance (hemisphere). env (make_env, on the
-        points' device): the environment in place of `background`, as in radiance. lights: as in radiance."""
+        points' device): the environment in place of `background`, as in radiance. lights, lighting: as in
+        radiance."""
         import torch
         if env is not None and not isinstance(env, Env):
             raise CrtError("probes: env must be an Env (make_env)")
         points, normals = self._probe_inputs("probes", points, normals, mode)
         n, device = points.shape[0], points.device.index
+        lit = _lighting_on("probes", lighting, env, lights, self, device)
         lh = _lights_on("probes", lights, env, self, device)
         view = _env_on("probes", env, device) if env is not None else None
         with torch.cuda.device(device):
@@ -932,7 +991,7 @@ class GpuScene:
                                   t_min=t_min, base_seed=base_seed, batch_probes=batch_probes,
                                   flags=CRT_RADIANCE_PLAIN if plain else 0,
                                   stream=torch.cuda.current_stream(device).cuda_stream, env=view,
-                                  sampler=(env.sampler or 0) if env is not None else 0, lights=lh)
+                                  sampler=(env.sampler or 0) if env is not None else 0, lights=lh, lighting=lit)
             return out
 
     def probe_rays(self, points, normals=None, samples: int = 1024, mode: str = "sphere", base_seed: int = 0):
@@ -1025,12 +1084,21 @@ class GpuScene:
             return rays, states
 
     def render_lens_async(self, device: int, cam: Camera, lens: Lens, out_ptr: int, stream: int = 0,
-                          env: Optional[EnvView] = None, sampler: int = 0, lights: int = 0) -> None:
+                          env: Optional[EnvView] = None, sampler: int = 0, lights: int = 0,
+                          lighting: Optional[LightingView] = None) -> None:
         """Enqueue a whole-frame render through `lens` (crt_render_lens_async) into the device buffer
         at out_ptr (image_h * image_w * 3 doubles): the rays of lens_rays, traced as radiance_async
         traces them and summed per pixel in render_async's order. The scene must be uploaded to
         `device`. env, sampler: as radiance_async's (crt_render_lens_env_async,
-        crt_render_lens_env_sampled_async). lights: as radiance_async's (crt_render_lens_lights_async)."""
+        crt_render_lens_env_sampled_async). lights: as radiance_async's (crt_render_lens_lights_async).
+        lighting: as radiance_async's (crt_render_lens_lit_async)."""
+        if lighting is not None:
+            if env is not None or sampler or lights:
+                raise ValueError("render_lens_async: lighting= cannot be combined with env=, sampler= or lights=")
+            check(lib().crt_render_lens_lit_async(self._h, device, C.byref(cam), C.byref(lens), C.byref(lighting),
+                                                  C.c_void_p(out_ptr or None), C.c_void_p(stream)),
+                  "crt_render_lens_lit_async")
+            return
         if lights:
             check(lib().crt_render_lens_lights_async(self._h, device, C.byref(cam), C.byref(lens), C.c_void_p(lights),
                                                      C.c_void_p(out_ptr or None), C.c_void_p(stream)),
@@ -1050,32 +1118,45 @@ class GpuScene:
                                           C.c_void_p(stream)), "crt_render_lens_async")
 
     def render_lens(self, cam: Camera, lens: Lens, device: int = 0, env: Optional[Env] = None,
-                    lights: Optional[LightSampler] = None):
+                    lights: Optional[LightSampler] = None, lighting: Optional[Lighting] = None):
         """Whole-frame render through `lens` (make_lens) into an (h, w, 3) float64 torch tensor on
         `device`. Runs on that device's current stream and does not synchronise; the scene is uploaded
         there first if it is not yet (that blocks). With kind "pinhole" the frame is render_async's,
         bit for bit. env (make_env, on `device`): the environment in place of cam.background, as in
-        radiance. lights: as in radiance."""
+        radiance. lights, lighting: as in radiance."""
         import torch
         if not isinstance(cam, Camera) or not isinstance(lens, Lens):
             raise CrtError("render_lens: cam must be a resolved Camera (resolve_camera) and lens a Lens (make_lens)")
+        lit = _lighting_on("render_lens", lighting, env, lights, self, device)
         lh = _lights_on("render_lens", lights, env, self, device)
         view = _env_on("render_lens", env, device) if env is not None else None
         with torch.cuda.device(device):
             out = torch.empty((cam.image_h, cam.image_w, 3), dtype=torch.float64, device=torch.device("cuda", device))
             self.upload(device)
             self.render_lens_async(device, cam, lens, out.data_ptr(), torch.cuda.current_stream(device).cuda_stream,
-                                   env=view, sampler=(env.sampler or 0) if env is not None else 0, lights=lh)
+                                   env=view, sampler=(env.sampler or 0) if env is not None else 0, lights=lh,
+                                   lighting=lit)
             return out
 
     def render_lens_pass(self, device: int, cam: Camera, lens: Lens, first: int, count: int, sum_ptr: int,
                          noise_ptr: int = 0, out_ptr: int = 0, blocks_ptr: int = 0, active_hint: int = 0,
-                         stream: int = 0) -> None:
+                         stream: int = 0, lighting=None) -> None:
         """Samples [first, first + count) of a cam.samples_per_pixel lens render of the whole frame into
         the running sums at sum_ptr (crt_render_lens_pass_async; render_pass's buffers and boundaries).
         With blocks_ptr (one uint32 per 16 x 4 block of the frame) only the blocks whose word equals
         `first` are generated and traced, and the call waits for the stream once to read how many
-        pixels that is; without it the call only enqueues. active_hint never changes the result."""
+        pixels that is; without it the call only enqueues. active_hint never changes the result.
+        lighting: a Lighting (or a LightingView) of this scene on `device`: the samples are lit by it
+        (crt_render_lens_pass_lit_async); Lighting() with nothing set gives the unlit pass's bytes."""
+        if lighting is not None:
+            lit = lighting if isinstance(lighting, LightingView) else _lighting_on("render_lens_pass", lighting, None,
+                                                                                   None, self, device)
+            check(lib().crt_render_lens_pass_lit_async(self._h, device, C.byref(cam), C.byref(lens), C.byref(lit), first,
+                                                       count, C.c_void_p(sum_ptr or None), C.c_void_p(noise_ptr or None),
+                                                       C.c_void_p(out_ptr or None), C.c_void_p(blocks_ptr or None),
+                                                       min(active_hint, 0xFFFFFFFF), C.c_void_p(stream)),
+                  "crt_render_lens_pass_lit_async")
+            return
         check(lib().crt_render_lens_pass_async(self._h, device, C.byref(cam), C.byref(lens), first, count,
                                                C.c_void_p(sum_ptr or None), C.c_void_p(noise_ptr or None),
                                                C.c_void_p(out_ptr or None), C.c_void_p(blocks_ptr or None),
@@ -1105,7 +1186,7 @@ class GpuScene:
     def render_lens_passes(self, cam: Camera, lens: Lens, threshold: Optional[float] = None, min_samples: int = 0,
                            samples_per_pass: int = 0, params: Optional[DenoiseParams] = None, denoise: bool = False,
                            callback=None, preview: bool = False, noisy: bool = False, counts: bool = False,
-                           device: int = 0):
+                           device: int = 0, lighting: Optional[Lighting] = None):
         """Blocking lens render in passes on `device` (crt_render_lens_passes): plain passes, or with
         `threshold` adaptive ones (render_adaptive's rule); with denoise=True (or `params`) the frame is
         filtered (a cube map one face at a time). Returns render_denoised's shape: (frame, unfiltered
@@ -1114,8 +1195,16 @@ class GpuScene:
         needs denoise). callback(samples_done, samples_total, active_blocks, total_blocks, noisy,
         frame) runs after every pass; a true return stops the render. preview=True (needs
         `threshold`; min_samples >= the job's samples renders plain passes) hands every call the
-        frames of the state so far (views of the returned arrays), else both are None."""
+        frames of the state so far (views of the returned arrays), else both are None. lighting (a
+        Lighting): every pass is lit by it (crt_render_lens_passes_lit: the call copies the map's texels
+        to the host and makes its own samplers for its duration; the features keep the background)."""
         denoise = denoise or params is not None
+        if lighting is not None and not isinstance(lighting, Lighting):
+            raise CrtError("render_lens_passes: lighting must be a Lighting")
+        if lighting is not None and lighting.lights is not None and (lighting.lights.scene is not self or
+                                                                     lighting.lights.device != device):
+            raise CrtError("render_lens_passes: the LightSampler belongs to another scene or device (it is on device "
+                           f"{lighting.lights.device})")
         if preview and threshold is None:
             raise CrtError("render_lens_passes: preview needs an adaptive render (threshold; min_samples >= the job's "
                            "samples renders plain passes)")
@@ -1142,14 +1231,25 @@ class GpuScene:
                 return 1
 
         fn = _capi.DENOISED_FN(trampoline) if callback is not None else _capi.DENOISED_FN()
-        rc = lib().crt_render_lens_passes(self._h, device, C.byref(cam), C.byref(lens),
-                                          C.byref(ad) if ad is not None else None,
-                                          C.byref(prm) if prm is not None else None, fn, None,
-                                          raw.ctypes.data if noisy else None, out.ctypes.data, blocks.ctypes.data,
-                                          C.byref(rendered))
+        tail = (C.byref(ad) if ad is not None else None, C.byref(prm) if prm is not None else None, fn, None,
+                raw.ctypes.data if noisy else None, out.ctypes.data, blocks.ctypes.data, C.byref(rendered))
+        if lighting is not None:
+            what = "crt_render_lens_passes_lit"
+            host_env, texels = None, None
+            if lighting.env is not None:
+                view = _env_on("render_lens_passes", lighting.env, device)
+                texels = np.ascontiguousarray(lighting.env.texels.cpu().numpy())  # the entry takes HOST texels
+                host_env = EnvView(texels.ctypes.data, view.face_size, view.filter, view.right, view.up, view.forward)
+            rc = lib().crt_render_lens_passes_lit(self._h, device, C.byref(cam), C.byref(lens),
+                                                  C.byref(host_env) if host_env is not None else None,
+                                                  1 if lighting.env is not None and lighting.env.sampler else 0,
+                                                  1 if lighting.lights is not None else 0, *tail)
+        else:
+            what = "crt_render_lens_passes"
+            rc = lib().crt_render_lens_passes(self._h, device, C.byref(cam), C.byref(lens), *tail)
         if raised:
             raise raised[0]
-        check(rc, "crt_render_lens_passes")
+        check(rc, what)
         return (out, raw, int(rendered.value), blocks) if counts else (out, raw, int(rendered.value))
 
 

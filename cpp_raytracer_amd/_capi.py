@@ -165,6 +165,14 @@ class LightSamplerView(C.Structure):
 assert C.sizeof(LightSamplerView) == 64
 
 
+class LightingView(C.Structure):
+    """crt_lighting: a plain environment or a sampler's handle, and a light sampler's handle."""
+    _fields_ = [("env", C.POINTER(EnvView)), ("sampler", C.c_void_p), ("lights", C.c_void_p), ("reserved", C.c_uint64)]
+
+
+assert C.sizeof(LightingView) == 32
+
+
 class LaunchPlan(C.Structure):
     _fields_ = ([(n, C.c_uint32) for n in ("kernel", "klass", "entry_bytes", "five_waves", "prim_mode", "plain_route",
                                            "depth", "block")] + [("num_nodes", C.c_uint64)] +
@@ -309,6 +317,20 @@ EXPORTS = {
     "crt_lens_features_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), C.c_void_p, C.c_void_p]),
     "crt_render_lens_passes": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), P(AdaptiveParams), P(DenoiseParams),
                                          DENOISED_FN, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint64)]),
+    "crt_radiance_lit_async": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                         P(RadianceParams), P(LightingView), C.c_void_p, C.c_void_p]),
+    "crt_probes_lit_async": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                       P(ProbeParams), P(LightingView), C.c_void_p, C.c_void_p]),
+    "crt_render_lens_lit_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), P(LightingView), C.c_void_p,
+                                            C.c_void_p]),
+    "crt_render_lens_pass_lit_async": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), P(LightingView), C.c_uint32,
+                                                 C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_uint32, C.c_void_p]),
+    "crt_render_lens_lit": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), P(EnvView), C.c_int, C.c_int,
+                                      C.c_void_p]),
+    "crt_render_lens_passes_lit": (C.c_int, [C.c_void_p, C.c_int, P(Camera), P(Lens), P(EnvView), C.c_int, C.c_int,
+                                             P(AdaptiveParams), P(DenoiseParams), DENOISED_FN, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint64)]),
     "crt_ppm_values": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "crt_ppm_write": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "crt_render_guard": (C.c_int, [C.c_void_p, C.c_int, P(C.c_uint64), C.c_int]),

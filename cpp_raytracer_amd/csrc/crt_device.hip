@@ -3202,8 +3202,14 @@ struct RadianceNee : RadianceEnv {
 struct RadianceLights : Radiance {
     LightTables tb;
 };
+// The lit instances' launch (crt_radiance_lit_async: an environment and the lights together): the
+// environment, its sampler's tables where it has one (ENV, NEE, LGT; unused in ENV, LGT) and the light
+// sampler's tables, all in the kernel arguments (no LDS: scene_layout decides as without them).
+struct RadianceLit : RadianceNee {
+    LightTables ltb;
+};
 template <bool ENV, bool NEE = false, bool LGT = false>
-using RadianceOf = std::conditional_t<LGT, RadianceLights,
+using RadianceOf = std::conditional_t<LGT, std::conditional_t<ENV, RadianceLit, RadianceLights>,
                                       std::conditional_t<NEE, RadianceNee, std::conditional_t<ENV, RadianceEnv, Radiance>>>;
 
 // A path that ends in a miss under an environment: 0 + T * E(P.d) (crt_env.h) where shade's miss
@@ -3428,6 +3434,144 @@ __device__ __forceinline__ bool light_segment(const SceneView& S, const CamView&
     return false;
 }
 
+// What a path of the lit instances (an environment and the scene's lights together) carries besides
+// its Path (include/crt_render.h, the lit estimator). The light sample's draws are made after the map
+// sample's shadow segment has come back (no segment draws a number: the values are the same), so
+// across that segment the lane keeps the bounce's normal and not a second direction; w is the map
+// sample's weight across a map segment and the light sample's cosine across a light segment.
+struct Lit {
+    double acc[3];
+    double pb;
+    double nd[3];
+    double n[3];
+    double w;
+    uint32_t lref;
+    uint32_t shadow;  // kLitNone, or the segment being traced is a shadow segment: kLitMap, kLitLight
+    bool has_pb;
+};
+constexpr uint32_t kLitNone = 0, kLitMap = 1, kLitLight = 2;
+
+__device__ __forceinline__ void nee_start(Lit& N) {
+    N.acc[0] = 0; N.acc[1] = 0; N.acc[2] = 0;
+    N.has_pb = false;
+    N.shadow = kLitNone;
+}
+
+// nee_segment and light_segment joined: one finished segment of a path of the lit instances. SMP: the
+// environment has a sampler (a map sample a Lambertian bounce, escapes weighted against it); without
+// one the environment is found by escapes alone, as in the ENV instances. A Lambertian bounce may
+// leave the map sample's shadow ray in P, then the light sample's, then the scattered ray.
+template <bool LS, bool SPH, bool SMP>
+__device__ __forceinline__ bool lit_segment(const SceneView& S, const CamView& C, const RadianceLit& Q, Path& P, Lit& N,
+                                            bool found, uint32_t ref, double tmax) {
+    constexpr double kPi = 3.141592653589793;
+    if (N.shadow == kLitLight) {  // counts only when it found the sampled light's own slot
+        if (found && ref == N.lref) {
+            const double pl = light_hit_pdf<LS, SPH>(S, Q.ltb, ref, P.o, P.d, tmax);
+            if (pl > 0 && pl < __builtin_inf()) {
+                const double pbs = N.w / kPi;
+                light_add(slot_material<SPH>(S, ref), P, pbs / (pl + pbs), N.acc);
+            }
+        }
+        P.d[0] = N.nd[0]; P.d[1] = N.nd[1]; P.d[2] = N.nd[2];
+        N.shadow = kLitNone;
+        return false;
+    }
+    if (N.shadow == kLitMap) {  // any hit occludes; a free segment adds the sample; the light sample follows
+        if (!found) nee_add(Q.env, C, P, N.w, N.acc);
+        N.shadow = kLitNone;
+    } else {
+        if (!found) {  // escape along d, weighted against the map's sampler if there is one and pb is not none
+            double f = 1.0;
+            if constexpr (SMP) {
+                if (N.has_pb) {
+                    const double sum = env_pdf(Q.env, Q.tb, P.d) + N.pb;
+                    f = sum > 0 ? N.pb / sum : 0.0;
+                }
+                nee_add(Q.env, C, P, f, N.acc);
+            } else {
+                env_miss(Q.env, C, P, N.acc);
+            }
+            return true;
+        }
+        ShadeOut X;
+        X.kind = 0;
+        if (shade<LS, SPH, false, false, 2>(S, C, P, true, ref, tmax, N.acc, &X)) {
+            if (X.kind == CRT_DIFFUSE_LIGHT) {  // weighted against the light sampler unless pb is none
+                double f = 1.0;
+                if (N.has_pb) {
+                    const double sum = light_hit_pdf<LS, SPH>(S, Q.ltb, ref, P.o, P.d, tmax) + N.pb;
+                    f = sum > 0 ? N.pb / sum : 0.0;
+                }
+                light_add(slot_material<SPH>(S, ref), P, f, N.acc);
+            }
+            return true;  // a light, or absorbed
+        }
+        if (P.depth == 0) return true;
+        if (X.kind != CRT_LAMBERTIAN) {
+            N.has_pb = false;
+            return false;
+        }
+        N.n[0] = X.n[0]; N.n[1] = X.n[1]; N.n[2] = X.n[2];
+        N.nd[0] = P.d[0]; N.nd[1] = P.d[1]; N.nd[2] = P.d[2];
+        bool ray_e = false;
+        if constexpr (SMP) {
+            const double xi1 = rnd_01(P.rng);
+            const double xi2 = rnd_01(P.rng);
+            const double xi3 = rnd_01(P.rng);
+            const double xi4 = rnd_01(P.rng);
+            double de[3];
+            env_sample(Q.env, Q.tb, xi1, xi2, xi3, xi4, de);
+            const double ce = dot3(N.n, de) / sqrt(dot3(de, de));
+            const double pbe = ce / kPi;
+            const double pe = env_pdf(Q.env, Q.tb, de);
+            ray_e = ce > 0 && pe > 0;
+            if (ray_e) {
+                P.d[0] = de[0]; P.d[1] = de[1]; P.d[2] = de[2];
+                N.w = pbe / (pe + pbe);
+            }
+        }
+        N.pb = (dot3(N.n, N.nd) / sqrt(dot3(N.nd, N.nd))) / kPi;
+        N.has_pb = true;
+        if (ray_e) {
+            N.shadow = kLitMap;
+            return false;
+        }
+    }
+    // the light sample of the bounce at P.o with the normal N.n
+    const double xi1 = rnd_01(P.rng);
+    const uint32_t lref = Q.ltb.ref[light_pick(Q.ltb, xi1)];
+    double pt[3], u[3] = {0, 0, 0};
+    const bool quad = !SPH && (lref & kRefQuad);
+    if (quad) {
+        const double xi2 = rnd_01(P.rng);
+        const double xi3 = rnd_01(P.rng);
+        const uint32_t i = lref & ~kRefQuad;
+        if constexpr (LS) {
+            const DevQuad q = lds_rec<DevQuad>(S.quads_lds + (i << 7));
+            light_point(q.v, q.s1, q.s2, xi2, xi3, pt);
+        } else {
+            light_point(S.quads[i].v, S.quads[i].s1, S.quads[i].s2, xi2, xi3, pt);
+        }
+    } else {
+        random_unit_vector<false>(P.rng, u[0], u[1], u[2]);
+        const DevSphere sp = sphere_at<LS>(S, lref);
+        light_point(sp.c, sp.r, u, pt);
+    }
+    const double dl[3] = {pt[0] - P.o[0], pt[1] - P.o[1], pt[2] - P.o[2]};
+    const double cl = dot3(N.n, dl) / sqrt(dot3(dl, dl));
+    // a point on a sphere's far side is hidden by its near side: no ray
+    if (cl > 0 && (quad || dot3(u, dl) < 0)) {
+        P.d[0] = dl[0]; P.d[1] = dl[1]; P.d[2] = dl[2];
+        N.w = cl;
+        N.lref = lref;
+        N.shadow = kLitLight;
+    } else {
+        P.d[0] = N.nd[0]; P.d[1] = N.nd[1]; P.d[2] = N.nd[2];
+    }
+    return false;
+}
+
 // path `ray` of a launch, before its first segment. False: the caller's ray is outside the query
 // contract (crt_ray_class.h) and must not be traced; shade's miss branch then gives 0 + 1 * bg.
 __device__ __forceinline__ bool load_path(const Radiance& Q, uint32_t ray, Path& P) {
@@ -3445,6 +3589,7 @@ __device__ __forceinline__ bool load_path(const Radiance& Q, uint32_t ray, Path&
 // the reference's sequence for any ray. ENV: a miss ends the path with env_miss instead of shade.
 // NEE (on top of ENV): every finished segment goes through nee_segment, shadow segments included.
 // LGT (without ENV or NEE): the same through light_segment (crt_radiance_lights_async).
+// ENV and LGT, with or without NEE: the same through lit_segment (crt_radiance_lit_async).
 template <bool ENV = false, bool NEE = false, bool LGT = false>
 __global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, CamView C, RadianceOf<ENV, NEE, LGT> Q, uint32_t first,
                                                                 uint32_t* __restrict__ gstack) {
@@ -3458,14 +3603,17 @@ __global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, Cam
     bool traced = load_path(Q, i, P);
     LaneCounters ctr{};
     double acc[3] = {0, 0, 0};
-    [[maybe_unused]] std::conditional_t<LGT, LNee, Nee> N;
+    [[maybe_unused]] std::conditional_t<LGT, std::conditional_t<ENV, Lit, LNee>, Nee> N;
     if constexpr (NEE || LGT) nee_start(N);
     while (true) {
         double tmax = __builtin_inf();
         uint32_t ref = 0;
         const bool found = traced && trace<uint32_t, false>(S, st, P.o, P.d, C.t_min, tmax, ref, ctr);
         traced = true;
-        if constexpr (LGT) {
+        if constexpr (LGT && ENV) {
+            if (lit_segment<false, false, NEE>(S, C, Q, P, N, found, ref, tmax)) break;
+            continue;
+        } else if constexpr (LGT) {
             if (light_segment<false, false>(S, C, Q, P, N, found, ref, tmax)) break;
             continue;
         } else if constexpr (NEE) {
@@ -3504,6 +3652,8 @@ __global__ __launch_bounds__(kBlock) void plain_radiance_kernel(SceneView S, Cam
 // scattered direction back. The lane's Nee stays in registers across all of it.
 // LGT (without ENV or NEE): the same with light_segment and its LNee (crt_radiance_lights_async); the
 // shadow ray ends on the sampled light or on what hides it, a closest hit either way.
+// ENV and LGT, with or without NEE: lit_segment and its Lit (crt_radiance_lit_async); a bounce may run
+// two shadow segments through these rounds before the saved scattered direction comes back.
 template <typename SE, bool GSTACK, bool LSCENE, int PM, bool ENV = false, bool NEE = false, bool LGT = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((NEE || LGT) ? CRT_WAVES_PER_EU_NEE : LSCENE ? CRT_WAVES_PER_EU_LDS : CRT_WAVES_PER_EU, 8))) void radiance_kernel(
     SceneView Sg, CamView C, Work W, RadianceOf<ENV, NEE, LGT> Q, SE* __restrict__ gstack) {
@@ -3529,7 +3679,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((NEE || 
     Path P;
     Trav R;
     R.state = kIdle;
-    [[maybe_unused]] std::conditional_t<LGT, LNee, Nee> N;
+    [[maybe_unused]] std::conditional_t<LGT, std::conditional_t<ENV, Lit, LNee>, Nee> N;
     bool need = true, cont = false;
     while (true) {
         set_prio<kPrioInit>();
@@ -3564,7 +3714,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((NEE || 
         if (R.state == kDone) {
             double acc[3] = {0, 0, 0};
             bool ended = true;
-            if constexpr (LGT) {
+            if constexpr (LGT && ENV) {
+                ended = lit_segment<LSCENE, kSphOnly, NEE>(S, CL, Q, P, N, R.found, R.ref, R.tmax);
+                acc[0] = N.acc[0]; acc[1] = N.acc[1]; acc[2] = N.acc[2];
+            } else if constexpr (LGT) {
                 ended = light_segment<LSCENE, kSphOnly>(S, CL, Q, P, N, R.found, R.ref, R.tmax);
                 acc[0] = N.acc[0]; acc[1] = N.acc[1]; acc[2] = N.acc[2];
             } else if constexpr (NEE) {
@@ -5140,7 +5293,19 @@ int device_radiance(const crt_scene* s, int device, const double* d_rays, size_t
     hipMemPool_t pool = nullptr;
     rc = pass_pool(device, &pool);
     if (rc) return rc;
-    if (lights) {  // of this scene on `device` (crt_host.cpp checks it); env and smp are null
+    if (lights && (env || smp)) {  // the lit instances; with smp, env is its recorded copy
+        dev::RadianceLit QT{};
+        static_cast<dev::Radiance&>(QT) = Q;
+        QT.ltb = LightTables{lights->ref, lights->cdf, lights->sref, lights->sw, lights->W, lights->L};
+        if (smp) {
+            QT.env = smp->env;
+            QT.tb = EnvTables{smp->w, smp->c, smp->m, smp->W};
+            return route_radiance<true, true, true>(s, device, prm, C, QT, pool, st);
+        }
+        QT.env = *env;
+        return route_radiance<true, false, true>(s, device, prm, C, QT, pool, st);
+    }
+    if (lights) {  // of this scene on `device` (crt_host.cpp checks it)
         dev::RadianceLights QL{};
         static_cast<dev::Radiance&>(QL) = Q;
         QL.tb = LightTables{lights->ref, lights->cdf, lights->sref, lights->sw, lights->W, lights->L};

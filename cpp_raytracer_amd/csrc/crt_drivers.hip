@@ -767,13 +767,49 @@ int render_denoised_devices(crt_scene* s, const crt_camera* cam, int num_devices
 // filter are the reference camera's, unchanged. Every pass writes the lane's frame (a skipped block's
 // pixels included), so the frame is current whenever the loop ends. With `denoise` the features are
 // taken once, before the first pass, and a CUBE frame is filtered one face at a time.
+// The lighting of crt_render_lens_passes_lit, made once before the first pass and freed with the
+// call: the environment's texels uploaded (blocking), a sampler on them, a sampler of the lights.
+namespace {
+struct CallLighting {
+    double* texels = nullptr;
+    crt_env env{};
+    bool have_env = false;
+    crt_env_sampler* smp = nullptr;
+    crt_light_sampler* lights = nullptr;
+    int make(crt_scene* s, int device, const crt_env* host_env, bool importance, bool want_lights) {
+        if (host_env) {
+            const size_t bytes = size_t{6} * host_env->face_size * host_env->face_size * 3 * sizeof(double);
+            env = *host_env;
+            HIP_TRY(hipMalloc(&texels, bytes));
+            HIP_TRY(hipMemcpy(texels, host_env->texels, bytes, hipMemcpyHostToDevice));
+            env.texels = texels;
+            have_env = true;
+            if (importance) {
+                const int rc = device_env_sampler_create(device, &env, &smp);
+                if (rc) return rc;
+            }
+        }
+        return want_lights ? device_light_sampler_create(s, device, &lights) : CRT_OK;
+    }
+    ~CallLighting() {
+        (void)device_env_sampler_free(smp);
+        (void)device_light_sampler_free(lights);
+        (void)hipFree(texels);
+    }
+};
+}  // namespace
+
 int render_lens_passes(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens,
                        const crt_adaptive_params* adaptive, const crt_denoise_params* denoise, crt_denoised_fn fn,
-                       void* user, double* h_noisy, double* h_rgb, uint32_t* h_block_samples, uint64_t* samples_rendered) {
+                       void* user, double* h_noisy, double* h_rgb, uint32_t* h_block_samples, uint64_t* samples_rendered,
+                       const crt_env* env, bool importance, bool lights) {
     const std::string who = "lens passes";
     int rc = device_upload(s, device);
     if (rc) return rc;
     DeviceGuard g(device);
+    CallLighting lit;  // declared before the lane: freed after the lane's stream has been drained
+    rc = lit.make(s, device, env, importance, lights);
+    if (rc) return rc;
     const uint32_t N = cam->samples_per_pixel, W = cam->image_w, H = cam->image_h;
     const uint64_t per_pass = pass_len(N, sample_chunk_len(N), adaptive ? adaptive->samples_per_pass : 0);
     const bool want_preview = adaptive && (adaptive->flags & CRT_PROGRESS_PREVIEW) != 0 && fn;
@@ -821,7 +857,8 @@ int render_lens_passes(crt_scene* s, int device, const crt_camera* cam, const cr
     bool have_frames = false;
     while (rc == CRT_OK && done < N) {
         const uint32_t count = static_cast<uint32_t>(std::min<uint64_t>(per_pass, N - done));
-        rc = device_render_lens_pass(s, device, cam, lens, done, count, l.sum, l.noise, l.rgb, l.blocks, l.stream);
+        rc = device_render_lens_pass(s, device, cam, lens, done, count, l.sum, l.noise, l.rgb, l.blocks, l.stream,
+                                     lit.have_env ? &lit.env : nullptr, lit.smp, lit.lights);
         if (rc != CRT_OK) break;
         done += count;
         if (adaptive)

@@ -2016,18 +2016,13 @@ int crt_lens_features_async(const crt_scene* s, int device, const crt_camera* ca
     return device_lens_features(s, device, cam, lens, d_feat, stream);
 }
 
-int crt_render_lens_passes(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens,
-                           const crt_adaptive_params* adaptive, const crt_denoise_params* denoise, crt_denoised_fn fn,
-                           void* user, double* h_noisy, double* h_rgb, uint32_t* h_block_samples,
-                           uint64_t* samples_rendered) {
-    clear_error();
-    if (samples_rendered) *samples_rendered = 0;
-    const std::string who = "crt_render_lens_passes: ";
-    int rc = check_lens(who, true, s, cam, lens, true);
-    if (rc) return rc;
+// crt_render_lens_passes' rules after check_lens's (crt_render_lens_passes_lit shares them)
+static int check_lens_passes(const std::string& who, const char* fn, const crt_camera* cam,
+                             const crt_adaptive_params* adaptive, const crt_denoise_params* denoise,
+                             const double* h_noisy, const double* h_rgb) {
     if (!h_rgb) return fail(CRT_E_INVALID, who + "h_rgb is null (the output is required)");
     if (denoise) {
-        rc = check_denoise_params("crt_render_lens_passes", denoise);
+        const int rc = check_denoise_params(fn, denoise);
         if (rc) return rc;
     } else if (h_noisy) {
         return fail(CRT_E_INVALID, who + "h_noisy must be null without denoise (h_rgb is the unfiltered frame)");
@@ -2041,8 +2036,132 @@ int crt_render_lens_passes(crt_scene* s, int device, const crt_camera* cam, cons
     }
     if (static_cast<uint64_t>(cam->image_w) * cam->image_h > 0x7fffffffull)
         return fail(CRT_E_INVALID, who + "frame has more than 2^31-1 pixels");
+    return CRT_OK;
+}
+
+int crt_render_lens_passes(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens,
+                           const crt_adaptive_params* adaptive, const crt_denoise_params* denoise, crt_denoised_fn fn,
+                           void* user, double* h_noisy, double* h_rgb, uint32_t* h_block_samples,
+                           uint64_t* samples_rendered) {
+    clear_error();
+    if (samples_rendered) *samples_rendered = 0;
+    const std::string who = "crt_render_lens_passes: ";
+    int rc = check_lens(who, true, s, cam, lens, true);
+    if (rc == CRT_OK) rc = check_lens_passes(who, "crt_render_lens_passes", cam, adaptive, denoise, h_noisy, h_rgb);
+    if (rc) return rc;
     return render_lens_passes(s, device, cam, lens, adaptive, denoise, fn, user, h_noisy, h_rgb, h_block_samples,
                               samples_rendered);
+}
+
+// ---- an environment and the lights together (crt_lighting): the call's own rules, then the
+// lighting's, member by member with the rules of the entry that takes that member alone, all before
+// any device work. The *_lit entries forward to the internals the other entries use -----------------
+static int check_lighting(const std::string& who, const crt_lighting* lit, const crt_scene* s, int device) {
+    if (!lit) return fail(CRT_E_INVALID, who + "lighting is null");
+    if (lit->env && lit->sampler)
+        return fail(CRT_E_INVALID, who + "lighting->env and lighting->sampler are both set (one environment a call)");
+    if (lit->reserved != 0) return fail(CRT_E_INVALID, who + "lighting->reserved must be 0");
+    int rc = CRT_OK;
+    if (lit->env) rc = check_env(who, lit->env);
+    if (rc == CRT_OK && lit->sampler) rc = check_sampler(who, lit->sampler, device);
+    if (rc == CRT_OK && lit->lights) rc = check_light_sampler(who, lit->lights, s, device);
+    return rc;
+}
+
+// the environment device_radiance takes for a lighting: the plain one, or the sampler's recorded copy
+static const crt_env* lighting_env(const crt_lighting* lit) { return lit->sampler ? &lit->sampler->env : lit->env; }
+
+static int check_host_lighting(const std::string& who, const crt_env* env, int importance, int lights) {
+    if (importance != 0 && importance != 1) return fail(CRT_E_INVALID, who + "importance must be 0 or 1");
+    if (lights != 0 && lights != 1) return fail(CRT_E_INVALID, who + "lights must be 0 or 1");
+    if (importance && !env) return fail(CRT_E_INVALID, who + "importance needs env (there is no map to sample)");
+    if (env) return importance ? check_sampler_env(who, env) : check_env(who, env);
+    return CRT_OK;
+}
+
+int crt_radiance_lit_async(const crt_scene* s, int device, const double* d_rays, size_t n, const uint32_t* d_states,
+                           const crt_radiance_params* params, const crt_lighting* lighting, double* d_rgb, void* stream) {
+    clear_error();
+    const std::string who = "crt_radiance_lit_async: ";
+    int rc = check_radiance(who, s, d_rays, "d_rays", n, params, d_rgb, "d_rgb");
+    if (rc == CRT_OK) rc = check_lighting(who, lighting, s, device);
+    if (rc) return rc;
+    if (n == 0) return CRT_OK;  // no work
+    return device_radiance(s, device, d_rays, n, d_states, params, lighting_env(lighting), d_rgb, stream, lighting->sampler,
+                           lighting->lights);
+}
+
+int crt_probes_lit_async(const crt_scene* s, int device, const double* d_points, const double* d_normals, size_t n,
+                         const crt_probe_params* params, const crt_lighting* lighting, double* d_coeff, void* stream) {
+    clear_error();
+    const std::string who = "crt_probes_lit_async: ";
+    int rc = check_probes(who, true, s, d_points, "d_points", d_normals, "d_normals", n, params);
+    if (rc == CRT_OK) rc = check_lighting(who, lighting, s, device);
+    if (rc) return rc;
+    if (n && !d_coeff) return fail(CRT_E_INVALID, who + "d_coeff is null (the output is required)");
+    if (n == 0) return CRT_OK;  // no work
+    return device_probes(s, device, d_points, d_normals, n, params, lighting_env(lighting), d_coeff, stream,
+                         lighting->sampler, lighting->lights);
+}
+
+int crt_render_lens_lit_async(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens,
+                              const crt_lighting* lighting, double* d_rgb, void* stream) {
+    clear_error();
+    const std::string who = "crt_render_lens_lit_async: ";
+    int rc = check_lens(who, true, s, cam, lens, true);
+    if (rc == CRT_OK) rc = check_lighting(who, lighting, s, device);
+    if (rc) return rc;
+    if (!d_rgb) return fail(CRT_E_INVALID, who + "d_rgb is null (the output is required)");
+    return device_render_lens(s, device, cam, lens, lighting_env(lighting), d_rgb, stream, lighting->sampler,
+                              lighting->lights);
+}
+
+int crt_render_lens_pass_lit_async(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens,
+                                   const crt_lighting* lighting, uint32_t first_sample, uint32_t num_samples,
+                                   double* d_sum, double* d_noise, double* d_rgb, uint32_t* d_blocks,
+                                   uint32_t active_hint, void* stream) {
+    clear_error();
+    const char* fn = "crt_render_lens_pass_lit_async";
+    const std::string who = std::string(fn) + ": ";
+    int rc = check_lens(who, true, s, cam, lens, true);
+    if (rc) return rc;
+    rc = check_pass(fn, s, cam, first_sample, num_samples, d_sum);
+    if (rc) return rc;
+    if (static_cast<uint64_t>(cam->image_w) * cam->image_h > 0x7fffffffull)
+        return fail(CRT_E_INVALID, who + "frame has more than 2^31-1 pixels");
+    if (d_blocks && first_sample + num_samples >= CRT_BLOCK_STOPPED)
+        return fail(CRT_E_INVALID, who + "sample counts must stay below 2^31");
+    rc = check_lighting(who, lighting, s, device);
+    if (rc) return rc;
+    (void)active_hint;  // as crt_render_lens_pass_async's: nothing is sized by the hint
+    return device_render_lens_pass(s, device, cam, lens, first_sample, num_samples, d_sum, d_noise, d_rgb, d_blocks, stream,
+                                   lighting_env(lighting), lighting->sampler, lighting->lights);
+}
+
+int crt_render_lens_lit(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, const crt_env* env,
+                        int importance, int lights, double* rgb) {
+    clear_error();
+    const std::string who = "crt_render_lens_lit: ";
+    int rc = check_lens(who, true, s, cam, lens, true);
+    if (rc == CRT_OK) rc = check_host_lighting(who, env, importance, lights);
+    if (rc) return rc;
+    if (!rgb) return fail(CRT_E_INVALID, who + "rgb is null (the output is required)");
+    return device_render_lens_host(s, device, cam, lens, env, rgb, importance != 0, lights != 0);
+}
+
+int crt_render_lens_passes_lit(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, const crt_env* env,
+                               int importance, int lights, const crt_adaptive_params* adaptive,
+                               const crt_denoise_params* denoise, crt_denoised_fn fn, void* user, double* h_noisy,
+                               double* h_rgb, uint32_t* h_block_samples, uint64_t* samples_rendered) {
+    clear_error();
+    if (samples_rendered) *samples_rendered = 0;
+    const std::string who = "crt_render_lens_passes_lit: ";
+    int rc = check_lens(who, true, s, cam, lens, true);
+    if (rc == CRT_OK) rc = check_host_lighting(who, env, importance, lights);
+    if (rc == CRT_OK) rc = check_lens_passes(who, "crt_render_lens_passes_lit", cam, adaptive, denoise, h_noisy, h_rgb);
+    if (rc) return rc;
+    return render_lens_passes(s, device, cam, lens, adaptive, denoise, fn, user, h_noisy, h_rgb, h_block_samples,
+                              samples_rendered, env, importance != 0, lights != 0);
 }
 
 int crt_closest_hits(crt_scene* s, int device, const double* rays, size_t n, double t_min,

@@ -459,7 +459,7 @@ int device_trace_host(crt_scene* s, int device, const double* rays, size_t n, co
 // smp (the same three): null, or the sampler of the *_env_sampled entries, built on `device`; env is
 // then its recorded crt_env and the launch is the NEE instances'.
 // lights (the same three): null, or the light sampler of the *_lights entries, of this scene on
-// `device`; env and smp are null then and the launch is the lights instances'
+// `device`: the lights instances' launch, or with an env or smp the lit instances' (crt_lighting)
 int device_radiance(const crt_scene* s, int device, const double* d_rays, size_t n, const uint32_t* d_states,
                     const crt_radiance_params* prm, const crt_env* env, double* d_rgb, void* stream,
                     const crt_env_sampler* smp = nullptr, const crt_light_sampler* lights = nullptr);
@@ -505,7 +505,8 @@ int device_light_sampler_free(crt_light_sampler* smp);
 // then waits for the stream once), the rays through the pixel centres, and the first-hit features
 int device_render_lens_pass(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, uint32_t first,
                             uint32_t count, double* d_sum, double* d_noise, double* d_rgb, uint32_t* d_blocks,
-                            void* stream);
+                            void* stream, const crt_env* env = nullptr, const crt_env_sampler* smp = nullptr,
+                            const crt_light_sampler* lights = nullptr);
 int device_lens_centre_rays(int device, const crt_camera* cam, const crt_lens* lens, double* d_rays, void* stream);
 int device_lens_features(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, crt_feature* d_feat,
                          void* stream);
@@ -592,5 +593,6 @@ int render_denoised_devices(crt_scene* s, const crt_camera* cam, int num_devices
                             double* h_rgb, uint32_t* h_block_samples, uint64_t* samples_rendered);
 int render_lens_passes(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens,
                        const crt_adaptive_params* adaptive, const crt_denoise_params* denoise, crt_denoised_fn fn,
-                       void* user, double* h_noisy, double* h_rgb, uint32_t* h_block_samples, uint64_t* samples_rendered);
+                       void* user, double* h_noisy, double* h_rgb, uint32_t* h_block_samples, uint64_t* samples_rendered,
+                       const crt_env* env = nullptr, bool importance = false, bool lights = false);
 }  // namespace crt

@@ -704,9 +704,10 @@ int device_render_lens(const crt_scene* s, int device, const crt_camera* cam, co
 // or of the pixels of the blocks whose word equals `first`, in batches of whole pixels as
 // device_render_lens's: generate, trace, accumulate, free. A masked pass lists its pixels first and
 // waits for `stream` once to read their number (the radiance query needs its record count on the host).
+// env, smp and lights are device_radiance's (crt_render_lens_pass_lit_async); all null: none.
 int device_render_lens_pass(const crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, uint32_t first,
                             uint32_t count, double* d_sum, double* d_noise, double* d_rgb, uint32_t* d_blocks,
-                            void* stream) {
+                            void* stream, const crt_env* env, const crt_env_sampler* smp, const crt_light_sampler* lights) {
     int rc = device_check(device);
     if (rc) return rc;
     if (!s->dev[device].valid)
@@ -771,7 +772,7 @@ int device_render_lens_pass(const crt_scene* s, int device, const crt_camera* ca
                 rgb = reinterpret_cast<double*>(scratch + records * 48);
                 uint32_t* states = reinterpret_cast<uint32_t*>(scratch + records * (48 + 24));
                 e = ln::launch_rays(V, lens->kind, at, static_cast<uint32_t>(records), first, count, rays, states, st, entries);
-                if (e == hipSuccess) rc = device_radiance(s, device, rays, records, states, &rp, nullptr, rgb, st);
+                if (e == hipSuccess) rc = device_radiance(s, device, rays, records, states, &rp, env, rgb, st, smp, lights);
             }
         }
         if (e == hipSuccess && rc == CRT_OK) {
@@ -861,8 +862,8 @@ int device_lens_features(const crt_scene* s, int device, const crt_camera* cam, 
 // crt_render_lens: device_render_lens for a host array, blocking: the render on a stream of its
 // own, one copy back. env (null: none) has its texels in host memory here: uploaded for the call,
 // freed after it. sampled: once the texels have arrived a sampler is built on them (blocking), the
-// render goes through it, and it is freed with them. lights (env is null then): a light sampler of
-// the uploaded scene is built for the call (crt_render_lens_lights) and freed after it
+// render goes through it, and it is freed with them. lights: a light sampler of the uploaded scene
+// is built for the call (crt_render_lens_lights, crt_render_lens_lit) and freed after it
 int device_render_lens_host(crt_scene* s, int device, const crt_camera* cam, const crt_lens* lens, const crt_env* env,
                             double* rgb, bool sampled, bool lights) {
     int rc = device_upload(s, device);
@@ -888,7 +889,7 @@ int device_render_lens_host(crt_scene* s, int device, const crt_camera* cam, con
         if (e == hipSuccess) rc = device_env_sampler_create(device, &d_env, &smp);
     }
     crt_light_sampler* lsmp = nullptr;
-    if (e == hipSuccess && lights) rc = device_light_sampler_create(s, device, &lsmp);
+    if (e == hipSuccess && rc == CRT_OK && lights) rc = device_light_sampler_create(s, device, &lsmp);
     if (e == hipSuccess && rc == CRT_OK) rc = device_render_lens(s, device, cam, lens, env ? &d_env : nullptr, d_rgb, st, smp, lsmp);
     if (e == hipSuccess && rc == CRT_OK) e = hipMemcpyAsync(rgb, d_rgb, bytes, hipMemcpyDeviceToHost, st);
     if (st) {

@@ -160,6 +160,15 @@ struct Lights {
     }
 };
 
+// Extension (not in the reference): what lights a lens render, two independent choices: an Environment
+// (its importance decides between the sampled and the plain map) or none, and the world's Lights or none
+// (crt_render_lens_lit, crt_render_lens_passes_lit). With both, every Lambertian bounce samples the map
+// and the lights, each weighted against the bounce. Both are borrowed for the call.
+struct Lighting {
+    const Environment* env = nullptr;
+    const Lights* lights = nullptr;
+};
+
 class Camera {
     size_t image_w = 1280, image_h = 720;
     double viewport_w = 0, viewport_h = 0;
@@ -439,13 +448,20 @@ class Camera {
         return img;
     }
 
+    // lit: over crt_render_lens_lit whatever is set (Camera::render_lens(world, lens, Lighting))
     Image render_scene_lens(const crt_api::GpuScene& g, const Lens& lens, const Environment* env = nullptr,
-                            bool lights = false) {
+                            bool lights = false, bool lit = false) {
         init();
         resolved.base_seed = SeedSeqGenerator::get_instance().next_seed();
         const crt_lens l = lens.as_crt();
         std::vector<double> rgb(image_w * image_h * 3);
-        if (lights) {
+        if (lit) {
+            crt_env e{};
+            if (env) e = env->as_crt();
+            if (crt_render_lens_lit(g.get(), 0, &resolved, &l, env ? &e : nullptr, env && env->importance ? 1 : 0, lights ? 1 : 0,
+                                    rgb.data()))
+                crt_api::die("crt_render_lens_lit");
+        } else if (lights) {
             if (crt_render_lens_lights(g.get(), 0, &resolved, &l, rgb.data())) crt_api::die("crt_render_lens_lights");
         } else if (env) {
             const crt_env e = env->as_crt();
@@ -466,6 +482,10 @@ class Camera {
         return img;
     }
 
+    static void check_lighting(const void* world, const Lighting& lit) {
+        if (lit.lights && lit.lights->world != world) crt_api::die("Camera::render_lens: the Lights were made of another world");
+    }
+
     // render_scene_lens in passes (crt_render_lens_passes): the callback ticks the bar and asks on_pass
     struct LensPassCtx {
         ProgressBar<>* bar;
@@ -481,7 +501,7 @@ class Camera {
     // with adaptive_threshold >= 0 an adaptive render, then the denoiser (a cube map one face at a time)
     Image render_scene_lens_passes(const crt_api::GpuScene& g, const Lens& lens, bool progressive, size_t samples_per_pass,
                                    const std::function<bool(size_t, size_t)>& on_pass, const DenoiseOptions& opt,
-                                   double adaptive_threshold) {
+                                   double adaptive_threshold, const Lighting* lit = nullptr) {
         init();
         resolved.base_seed = SeedSeqGenerator::get_instance().next_seed();
         const crt_lens l = lens.as_crt();
@@ -504,18 +524,27 @@ class Camera {
         std::vector<double> rgb(image_w * image_h * 3);
         uint64_t rendered = 0;
         int rc;
+        // under a Lighting: the same loop over crt_render_lens_passes_lit, the lighting made once for the call
+        crt_env e{};
+        if (lit && lit->env) e = lit->env->as_crt();
+        const crt_env* pe = lit && lit->env ? &e : nullptr;
+        const int importance = lit && lit->env && lit->env->importance ? 1 : 0, lights = lit && lit->lights ? 1 : 0;
         if (progressive) {
             ProgressBar<> bar((samples_per_pixel + per_pass - 1) / per_pass,
                               "Rendering " + std::to_string(image_w) + " x " + std::to_string(image_h) + " lens image (" +
                                   std::to_string(samples_per_pixel) + " spp) in passes");
             LensPassCtx ctx{&bar, &on_pass};
-            rc = crt_render_lens_passes(g.get(), 0, &resolved, &l, &ap, nullptr, lens_pass, &ctx, nullptr, rgb.data(),
-                                        nullptr, &rendered);
+            rc = lit ? crt_render_lens_passes_lit(g.get(), 0, &resolved, &l, pe, importance, lights, &ap, nullptr, lens_pass, &ctx,
+                                                  nullptr, rgb.data(), nullptr, &rendered)
+                     : crt_render_lens_passes(g.get(), 0, &resolved, &l, &ap, nullptr, lens_pass, &ctx, nullptr, rgb.data(),
+                                              nullptr, &rendered);
         } else {
             std::cout << "Rendering " << image_w << " x " << image_h << " lens image (" << (adaptive ? "up to " : "")
                       << samples_per_pixel << " spp" << (adaptive ? ", adaptive" : "") << ", denoised)" << std::endl;
-            rc = crt_render_lens_passes(g.get(), 0, &resolved, &l, adaptive ? &ap : nullptr, &dp, nullptr, nullptr, nullptr,
-                                        rgb.data(), nullptr, &rendered);
+            rc = lit ? crt_render_lens_passes_lit(g.get(), 0, &resolved, &l, pe, importance, lights, adaptive ? &ap : nullptr, &dp,
+                                                  nullptr, nullptr, nullptr, rgb.data(), nullptr, &rendered)
+                     : crt_render_lens_passes(g.get(), 0, &resolved, &l, adaptive ? &ap : nullptr, &dp, nullptr, nullptr, nullptr,
+                                              rgb.data(), nullptr, &rendered);
         }
         if (rc) crt_api::die("Camera::render_lens passes");
         const double mean = static_cast<double>(rendered) / static_cast<double>(image_w * image_h);
@@ -710,6 +739,59 @@ public:
         } else {
             crt_api::GpuScene s(world, 32, 12, true);
             return render_scene_lens(s, lens, nullptr, true);
+        }
+    }
+
+    // Extension (not in the reference): render_lens under a Lighting, an Environment and the world's Lights
+    // together or either alone (crt_render_lens_lit), and the same in passes and denoised
+    // (crt_render_lens_passes_lit); with nothing set they are the calls without a Lighting.
+    Image render_lens(const BVH& world, const Lens& lens, const Lighting& lit) {
+        check_lighting(&world, lit);
+        return render_scene_lens(world.gpu_scene(), lens, lit.env, lit.lights != nullptr, true);
+    }
+    template <typename T>
+    requires std::is_base_of_v<Hittable, T>
+    Image render_lens(const T& world, const Lens& lens, const Lighting& lit) {
+        check_lighting(&world, lit);
+        if constexpr (std::is_same_v<T, Scene>) {
+            return render_scene_lens(BVH(world).gpu_scene(), lens, lit.env, lit.lights != nullptr, true);
+        } else {
+            crt_api::GpuScene s(world, 32, 12, true);
+            return render_scene_lens(s, lens, lit.env, lit.lights != nullptr, true);
+        }
+    }
+    Image render_lens_progressive(const BVH& world, const Lens& lens, const Lighting& lit, size_t samples_per_pass = 0,
+                                  std::function<bool(size_t done, size_t total)> on_pass = {}) {
+        check_lighting(&world, lit);
+        return render_scene_lens_passes(world.gpu_scene(), lens, true, samples_per_pass, on_pass, {}, -1, &lit);
+    }
+    template <typename T>
+    requires std::is_base_of_v<Hittable, T>
+    Image render_lens_progressive(const T& world, const Lens& lens, const Lighting& lit, size_t samples_per_pass = 0,
+                                  std::function<bool(size_t done, size_t total)> on_pass = {}) {
+        check_lighting(&world, lit);
+        if constexpr (std::is_same_v<T, Scene>) {
+            return render_scene_lens_passes(BVH(world).gpu_scene(), lens, true, samples_per_pass, on_pass, {}, -1, &lit);
+        } else {
+            crt_api::GpuScene s(world, 32, 12, true);
+            return render_scene_lens_passes(s, lens, true, samples_per_pass, on_pass, {}, -1, &lit);
+        }
+    }
+    Image render_lens_denoised(const BVH& world, const Lens& lens, const Lighting& lit, DenoiseOptions options = {},
+                               double adaptive_threshold = -1) {
+        check_lighting(&world, lit);
+        return render_scene_lens_passes(world.gpu_scene(), lens, false, 0, {}, options, adaptive_threshold, &lit);
+    }
+    template <typename T>
+    requires std::is_base_of_v<Hittable, T>
+    Image render_lens_denoised(const T& world, const Lens& lens, const Lighting& lit, DenoiseOptions options = {},
+                               double adaptive_threshold = -1) {
+        check_lighting(&world, lit);
+        if constexpr (std::is_same_v<T, Scene>) {
+            return render_scene_lens_passes(BVH(world).gpu_scene(), lens, false, 0, {}, options, adaptive_threshold, &lit);
+        } else {
+            crt_api::GpuScene s(world, 32, 12, true);
+            return render_scene_lens_passes(s, lens, false, 0, {}, options, adaptive_threshold, &lit);
         }
     }
 

@@ -14,7 +14,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import (CRT_BLOCK_STOPPED, CRT_LENS_CUBE, FEATURE_DTYPE, Camera, CrtError, GpuScene, Lens, adaptive_update,
+from . import (CRT_BLOCK_STOPPED, CRT_LENS_CUBE, FEATURE_DTYPE, Camera, CrtError, GpuScene, Lens, Lighting, adaptive_update,
                block_count, denoise, denoise_params, noise_estimate, pixel_variance, sample_chunk_len)
 from .progressive import _resume_job
 
@@ -25,10 +25,12 @@ class LensRender:
     """Samples [0, cam.samples_per_pixel) of `scene` through `lens` on `device`, a step at a time, on
     the device's current stream. threshold=None: every pixel gets every sample. Otherwise a block
     stops once the sum of its pixels' standard errors is at most `threshold` times the sum of their
-    means, not before min_samples samples (AdaptiveRender's rule)."""
+    means, not before min_samples samples (AdaptiveRender's rule). lighting (a Lighting of this scene
+    on `device`): every pass is lit by it (crt_render_lens_pass_lit_async); state() does not store it,
+    so resume() takes the same one again."""
 
     def __init__(self, scene: GpuScene, cam: Camera, lens: Lens, threshold: Optional[float] = None, min_samples: int = 0,
-                 device: int = 0):
+                 device: int = 0, lighting=None):
         import torch
         if not isinstance(cam, Camera) or not isinstance(lens, Lens):
             raise CrtError("LensRender: cam must be a resolved Camera (resolve_camera) and lens a Lens (make_lens)")
@@ -36,7 +38,10 @@ class LensRender:
             raise CrtError("LensRender: samples_per_pixel is 0")
         if threshold is not None and not (threshold >= 0 and np.isfinite(threshold)):
             raise CrtError("LensRender: threshold must be finite and >= 0")
+        if lighting is not None and not isinstance(lighting, Lighting):
+            raise CrtError("LensRender: lighting must be a Lighting")
         self.scene, self.cam, self.lens, self.device = scene, cam, lens, device
+        self.lighting = lighting
         self.threshold = None if threshold is None else float(threshold)
         self.min_samples = int(min_samples)
         self.chunk_len = sample_chunk_len(cam.samples_per_pixel)
@@ -80,7 +85,8 @@ class LensRender:
         st = self._stream()
         blocks = self._blocks.data_ptr() if self._blocks is not None else 0
         self.scene.render_lens_pass(self.device, self.cam, self.lens, self.samples_done, count, self._sum.data_ptr(),
-                                    self._noise.data_ptr(), self._out.data_ptr(), blocks, self.active_blocks, st)
+                                    self._noise.data_ptr(), self._out.data_ptr(), blocks, self.active_blocks, st,
+                                    lighting=self.lighting)
         self.samples_done += count
         if self._blocks is not None:
             self.active_blocks = adaptive_update(self.device, self.cam, self._noise.data_ptr(), blocks, self.samples_done,
@@ -175,9 +181,9 @@ class LensRender:
         return d
 
     @classmethod
-    def resume(cls, scene: GpuScene, cam: Camera, lens: Lens, state: dict, device: int = 0) -> "LensRender":
+    def resume(cls, scene: GpuScene, cam: Camera, lens: Lens, state: dict, device: int = 0, lighting=None) -> "LensRender":
         """Continue the render of a state() checkpoint of this job: the same samples per pixel, base
-        seed, frame size and lens as `cam` and `lens`."""
+        seed, frame size and lens as `cam` and `lens`, and the lighting the job had (it is not stored)."""
         import torch
         done, tiling, rows, total = _resume_job("LensRender", cam, state)
         if tiling is not None:
@@ -189,7 +195,7 @@ class LensRender:
             raise CrtError("LensRender.resume: the state has no noise state of the job's shape")
         adaptive = "blocks" in state
         r = cls(scene, cam, lens, float(state["threshold"]) if adaptive else None,
-                int(state["min_samples"]) if adaptive else 0, device)
+                int(state["min_samples"]) if adaptive else 0, device, lighting)
         r._sum.copy_(torch.from_numpy(np.ascontiguousarray(total)))
         r._noise.copy_(torch.from_numpy(np.ascontiguousarray(noise.astype(np.float64))))
         r.samples_done = done

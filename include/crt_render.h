@@ -1018,7 +1018,7 @@ int crt_render_lens_env_sampled(crt_scene* scene, int device, const crt_camera* 
  * crt_render_lens with the sampler as one more argument: same buffers, same rules. CRT_E_INVALID in
  * addition, before any device work: lights NULL; a sampler of another scene; a sampler built on
  * another device. max_depth == 0 is still a memset. The probes' and the lens frames' first segments
- * have pb = none. Lights together with an environment are not offered. */
+ * have pb = none. Lights together with an environment: the *_lit entries (below). */
 typedef struct crt_light_sampler crt_light_sampler;
 struct crt_light_sampler_view {    /* the entry below has the same name: no typedef, say `struct` */
     uint32_t num_lights;            /* L */
@@ -1135,6 +1135,97 @@ int crt_render_lens_passes(crt_scene* scene, int device, const crt_camera* cam, 
                            const crt_adaptive_params* adaptive, const crt_denoise_params* denoise,
                            crt_denoised_fn fn, void* user, double* h_noisy, double* h_rgb,
                            uint32_t* h_block_samples, uint64_t* samples_rendered);
+
+/* ---- an environment and the scene's lights together, also in passes ---------------------------
+ * The two next-event estimators above under one argument, and the lens passes with it. An addition to
+ * the ABI (no existing call changes, CRT_ABI_VERSION stays). Every operation is an IEEE f64 + - * /,
+ * a sqrt or a comparison; nothing is fused; dot products are (a0 b0 + a1 b1) + a2 b2; pi is the
+ * double 3.141592653589793. env_sample, env_pdf, light_pick, light_point and light_pdf are the
+ * functions of the two sections above, unchanged.
+ *
+ * A lighting is two independent choices: the environment (none: the constant background; a plain
+ * crt_env; or a crt_env_sampler) and the lights (none, or a crt_light_sampler). A path carries acc,
+ * +0 per channel at its start, and pb, "none" at its start and after a Metal or Dielectric bounce.
+ *   A segment ends on a DiffuseLight: without a light sampler acc = acc + T * emit. With one, f = 1.0
+ *     if pb is none, else pl = light_pdf(hit) and f = (pl + pb) > 0 ? pb / (pl + pb) : 0.0;
+ *     acc = acc + (T * emit) * f. The path ends.
+ *   A segment escapes along d: with no environment acc = acc + T * background; with a plain one
+ *     acc = acc + T * E(d); with a sampler f = 1.0 if pb is none, else pe = env_pdf(d) and
+ *     f = (pe + pb) > 0 ? pb / (pe + pb) : 0.0; acc = acc + (T * E(d)) * f. The path ends.
+ *   Metal or Dielectric bounce: pb = none.
+ *   Lambertian bounce at o with the normal n facing the ray, after the material's own draws, the
+ *   throughput multiply and the depth decrement, if depth left > 0, in this order:
+ *     1. With an env sampler: xi1..xi4 = crt_rand_double(state, 0, 1) (always drawn);
+ *        d_e = env_sample(xi); c_e = (n . d_e) / sqrt(d_e . d_e); pe = env_pdf(d_e);
+ *        ray_e = c_e > 0 && pe > 0.
+ *     2. With a light sampler: xi1 (always drawn); i = light_pick(xi1); p_l = light_point(i) (its
+ *        draws are always made); d_l = p_l - o; c_l = (n . d_l) / sqrt(d_l . d_l);
+ *        ray_l = c_l > 0 && (light i is a parallelogram || u . d_l < 0).
+ *     3. pb = ((n . nd) / sqrt(nd . nd)) / pi for the scattered direction nd.
+ *     4. If ray_e: the segment from o along d_e over (t_min, +inf) is traced; any hit occludes. If it
+ *        is free, pb_e = c_e / pi and acc = acc + (T * E(d_e)) * (pb_e / (pe + pb_e)).
+ *     5. If ray_l: the segment along d_l is traced, closest hit. It counts only if the hit's ref is
+ *        light i's slot: then pl = light_pdf(that hit), pb_l = c_l / pi, and if pl > 0 && pl < inf,
+ *        acc = acc + (T * emit_i) * (pb_l / (pl + pb_l)).
+ *     6. The path goes on along nd.
+ *   The output is acc: absorbed paths and paths out of depth write what they gathered.
+ * All of step 1's draws precede step 2's, and acc receives step 4's term before step 5's. No segment
+ * draws a number, so an implementation may make step 2's draws after step 4's segment has returned
+ * (to hold less across it): the values are the same.
+ * Each sample is weighted against pb alone, and that is not an omission. A direction from o either
+ * ends on a primitive or leaves the scene, so the map and the lights are disjoint emitters: the map's
+ * sampler never produces a contribution a light could also have produced, nor the reverse. On each
+ * emitter exactly two strategies compete, that emitter's own sampler and the bounce, and the balance
+ * heuristic over those two is complete: wherever a contribution is not zero, the two weights sum to 1.
+ * Consequences: a lighting with only a sampler gives crt_radiance_env_sampled_async's bytes, with only
+ * lights crt_radiance_lights_async's, with only a plain env crt_radiance_env_async's, with nothing
+ * crt_radiance_async's (the entries below forward to the same launches). Every path without a
+ * Lambertian bounce, and every path with max_depth == 1, gets crt_radiance_env_async's bytes, or
+ * crt_radiance_async's without an environment. Rays the query contract refuses stay first-segment
+ * misses with f = 1. Neither the grid nor the route (CRT_RADIANCE_PLAIN) changes a bit.
+ *
+ * The *_lit entries are crt_radiance_async, crt_probes_async, crt_render_lens_async and
+ * crt_render_lens_pass_async with the lighting as one more argument: same buffers, same rules.
+ * CRT_E_INVALID in addition, before any device work (the message names the rule): lighting NULL; env
+ * and sampler both set; reserved != 0; for the members given, the rules of the *_env entries
+ * (crt_env's), of the *_env_sampled entries (a sampler built on another device) and of the *_lights
+ * entries (a sampler of another scene or device). max_depth == 0 is still a memset. The probes' and
+ * the lens frames' first segments have pb = none.
+ * crt_render_lens_pass_lit_async is crt_render_lens_pass_async in every rule, buffer and bit, with
+ * the lit estimator's output as L_s: accumulation, masks, the active-pixel list, the one stream wait
+ * with d_blocks and the batches are untouched. crt_lens_features_async is unchanged under a lighting:
+ * a miss keeps the constant background as its albedo. */
+typedef struct crt_lighting {          /* 32 bytes */
+    const crt_env* env;                /* plain environment (DEVICE texels), or NULL */
+    const crt_env_sampler* sampler;    /* luminance-sampled environment, or NULL; not with env */
+    const crt_light_sampler* lights;   /* the scene's lights sampled, or NULL */
+    uint64_t reserved;                 /* 0 */
+} crt_lighting;
+int crt_radiance_lit_async(const crt_scene* scene, int device, const double* d_rays, size_t n,
+                           const uint32_t* d_states, const crt_radiance_params* params,
+                           const crt_lighting* lighting, double* d_rgb, void* stream);
+int crt_probes_lit_async(const crt_scene* scene, int device, const double* d_points, const double* d_normals,
+                         size_t n, const crt_probe_params* params, const crt_lighting* lighting,
+                         double* d_coeff, void* stream);
+int crt_render_lens_lit_async(const crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens,
+                              const crt_lighting* lighting, double* d_rgb, void* stream);
+int crt_render_lens_pass_lit_async(const crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens,
+                                   const crt_lighting* lighting, uint32_t first_sample, uint32_t num_samples,
+                                   double* d_sum, double* d_noise, double* d_rgb, uint32_t* d_blocks,
+                                   uint32_t active_hint, void* stream);
+/* Blocking, host arrays: crt_render_lens and crt_render_lens_passes under a lighting made for the
+ * call. env is NULL or has its texels in HOST memory (uploaded once, freed at the end); importance
+ * and lights are 0 or 1: importance builds a crt_env_sampler on the uploaded texels
+ * (crt_env_sampler_create's rules; CRT_E_INVALID without env), lights a crt_light_sampler of the
+ * uploaded scene (crt_light_sampler_create's rules). crt_render_lens_passes_lit builds both once,
+ * before the first pass, and frees them at the end; its loop is crt_render_lens_passes'. */
+int crt_render_lens_lit(crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens,
+                        const crt_env* env, int importance, int lights, double* rgb);
+int crt_render_lens_passes_lit(crt_scene* scene, int device, const crt_camera* cam, const crt_lens* lens,
+                               const crt_env* env, int importance, int lights,
+                               const crt_adaptive_params* adaptive, const crt_denoise_params* denoise,
+                               crt_denoised_fn fn, void* user, double* h_noisy, double* h_rgb,
+                               uint32_t* h_block_samples, uint64_t* samples_rendered);
 
 /* The integers Image::send_as_ppm prints (image.h:38-56; RGB::as_string rgb.h:99-115 with its
  * defaults: Reinhard tone map by luminance, gamma 2, static_cast<int>(255.999999 * v)) for the
